@@ -46,6 +46,25 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs DIR: one DIR/<name>.npy (float64) per array, at most DUMP_LIMIT_BYTES in all.  Above the limit the point
+    coordinates are replaced by a fixed, seeded sample of their rows, whose row indices go to points_index.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    header = 4096                      # room for the .npy headers
+    total = sum(a.nbytes for a in arrays.values()) + header
+    if total > DUMP_LIMIT_BYTES:
+        P = arrays["points"]
+        room = DUMP_LIMIT_BYTES - (total - P.nbytes)
+        n_keep = min(P.shape[0], max(0, room // (P.itemsize * (P.shape[1] + 1))))
+        idx = np.sort(np.random.default_rng(0).choice(P.shape[0], size=n_keep, replace=False))
+        arrays["points"] = np.ascontiguousarray(P[idx])
+        arrays["points_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def shard_problem(arr: dict, rank: int, world: int) -> dict:
@@ -364,6 +383,8 @@ def mapper_bench(args):
     r = mapper_replay.run(arr, repeats=2)
     if r["status"] != 0:
         raise SystemExit(f"mapper replay failed: status {r['status']}: {r['stderr']}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cam_q": r["cam_q"], "cam_t": r["cam_t"], "points": r["points"]})
     rep = r["replays"][1]
     ba_ms = sum(rep["classes"][k]["total_ms"] for k in ("GBA", "LBA", "KGBA"))
     out = {"metric": "mapper-shaped BA replay: wall time of the BA calls of one incremental reconstruction", "value": ba_ms, "unit": "ms",
@@ -391,7 +412,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the host-inclusive one-shot solve and the config-D MFMA measurement")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (cameras, points, summary; bal9: intrinsics) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.config == "M":
         return mapper_bench(args)
@@ -465,6 +490,16 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # the result of the last timed step as the caller receives it, read back outside the timed region (N > 1: rank 0's
+        # cameras and its shard of the points)
+        res_q, res_t, res_P = ctx.download()
+        res = {"cam_q": res_q, "cam_t": res_t, "points": res_P,
+               "summary": [last.initial_cost, last.final_cost, last.n_successful, last.n_unsuccessful, last.termination_reason,
+                           last.pcg_iterations, last.linear_solver_used]}
+        if args.config == "Lb9":
+            res["intr_params"] = ctx.download_intrinsics()
+        dump_outputs(args.dump_outputs, res)
 
     # one extra, untimed, profiled solve: HIP-event durations per kernel class on the library's stream
     popt = capi.default_options(profile=1)

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +36,7 @@ class FakeContext:
     def __init__(self, prob, device=0): self.prob = prob; LOG.append(("ctx", device, prob.n_points, prob.n_obs))
     def comm_init(self, world, rank, uid): LOG.append(("comm", world, rank, len(uid), sum(uid)))
     def reset(self): pass
-    def run(self, opt=None): return FakeSummary()
+    def run(self, opt=None): LOG.append(("run",)); return FakeSummary()
     def download(self): return self.prob.cam_q, self.prob.cam_t, self.prob.points
     def profile(self): return {{"k_schur_pairs": (1.4, 14), "k_linearize": (1.2, 15)}}
     def close(self): pass
@@ -132,3 +133,49 @@ def test_two_ranks_on_the_collection_config(tmp_path):
     obs = [log[0][3] for log in logs]
     assert abs(obs[0] - obs[1]) <= 0.02 * sum(obs) and min(pts) > 0            # observations balanced within 1 % of the total per rank
     assert all(log[1] == ("comm", 2, rank, 128, sum(range(128))) for rank, log in enumerate(logs))
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` on one rank with the stand-in device layer: --warmup + --steps solves (+ the untimed
+    profiled one), then the cameras, points and summary of the last timed step as float64 .npy files; a second run with the
+    same arguments writes the same files (the inputs are generated from fixed seeds)."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--config", "S", "--no-cpu", "--no-extras", "--dump-outputs", str(d)]
+        script = tmp_path / "driver.py"
+        script.write_text(DRIVER.format(root=ROOT, argv=argv))
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        p = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert j["steps"] == 3 and j["warmup"] == 2 and j["lm_iterations_per_step"] == 6
+        log = eval([l for l in p.stdout.splitlines() if l.startswith("LOG")][0][4:])
+        assert log.count(("run",)) == 2 + 3 + 1
+        assert sorted(os.listdir(d)) == ["cam_q.npy", "cam_t.npy", "points.npy", "summary.npy"]
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    out = dumps[0]
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["cam_q"].shape == (12, 4) and out["cam_t"].shape == (12, 3) and out["points"].shape == (300, 3)
+    assert list(out["summary"]) == [10.0, 1.0, 5, 1, 3, 0, 1]
+    assert all(np.array_equal(out[k], dumps[1][k]) for k in out)
+
+
+def test_dump_outputs_samples_large_point_sets(tmp_path, monkeypatch):
+    """Above the size limit the points are a fixed, seeded sample of their rows, stored with the row indices."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200_000)
+    rng = np.random.default_rng(3)
+    arrays = {"cam_q": rng.normal(size=(10, 4)), "cam_t": rng.normal(size=(10, 3)), "points": rng.normal(size=(50_000, 3))}
+    for run in range(2):
+        bench.dump_outputs(str(tmp_path / f"d{run}"), arrays)
+    files = sorted(os.listdir(tmp_path / "d0"))
+    assert files == ["cam_q.npy", "cam_t.npy", "points.npy", "points_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "d0" / f) for f in files) <= 200_000
+    idx = np.load(tmp_path / "d0" / "points_index.npy")
+    P = np.load(tmp_path / "d0" / "points.npy")
+    assert idx.shape[0] == P.shape[0] > 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(P, arrays["points"][idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "d0" / "cam_q.npy"), arrays["cam_q"])
+    assert all(np.array_equal(np.load(tmp_path / "d0" / f), np.load(tmp_path / "d1" / f)) for f in files)
