@@ -391,6 +391,10 @@ int xrsfm_ba_debug_wide(xrsfm_ba_context *ctx, double huber_a, double radius, do
 int xrsfm_ba_debug_backsub(xrsfm_ba_context *ctx, double *part_model, double *part_step2, double *cand_points,
                            double *point_step, double *cand_cam_q, double *cand_cam_t);
 
+/* Whether the context currently keeps the per-observation residual and Jacobian stored (1) or recomputes them in the
+ * consumers (0, the J-free linearisation of the Cholesky path): after xrsfm_ba_run, the mode its last iterations used. */
+int xrsfm_ba_debug_stored_j(xrsfm_ba_context *ctx, int32_t *stored);
+
 #ifdef __cplusplus
 }
 #endif

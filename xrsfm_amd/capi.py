@@ -89,7 +89,7 @@ EXPORTS = [
     "xrsfm_ba_solve", "xrsfm_ba_filter_tracks", "xrsfm_ba_profile_entry", "xrsfm_ba_debug_linearize", "xrsfm_ba_debug_schur_product",
     "xrsfm_ba_debug_cholesky_solve", "xrsfm_ba_debug_set_block_pattern", "xrsfm_ba_debug_pack", "xrsfm_ba_debug_chol_plan", "xrsfm_ba_refine_pose", "xrsfm_ba_refine_pose_options", "xrsfm_ba_debug_comm_hook", "xrsfm_pg_default_options", "xrsfm_pg_solve", "xrsfm_ba_debug_pack_gram", "xrsfm_ba_debug_gram_schedule",
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
-    "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup",
+    "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j",
 ]
 
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
@@ -131,6 +131,9 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_schur_product.restype = C.c_int
     lib.xrsfm_ba_debug_cholesky_solve.argtypes = [vp, C.c_double, _c_double_p, _c_double_p]
     lib.xrsfm_ba_debug_cholesky_solve.restype = C.c_int
+    if hasattr(lib, "xrsfm_ba_debug_stored_j"):
+        lib.xrsfm_ba_debug_stored_j.argtypes = [vp, C.POINTER(C.c_int32)]
+        lib.xrsfm_ba_debug_stored_j.restype = C.c_int
     if hasattr(lib, "xrsfm_ba_debug_backsub"):      # (absent in the round-2 repro builds of tools/backsub_waves_probe.py)
         lib.xrsfm_ba_debug_backsub.argtypes = [vp] + [_c_double_p] * 6
         lib.xrsfm_ba_debug_backsub.restype = C.c_int
@@ -327,6 +330,12 @@ class Context:
         check(self.lib.xrsfm_ba_debug_schur_product(self._h, radius, _dp(x), _dp(y), _dp(b)), "debug_schur_product")
         return y, b
 
+
+    def debug_stored_j(self) -> bool:
+        """True while the context keeps the per-observation residual / Jacobian stored (False: J-free linearisation)."""
+        v = C.c_int32(0)
+        check(self.lib.xrsfm_ba_debug_stored_j(self._h, C.byref(v)), "debug_stored_j")
+        return bool(v.value)
 
     def debug_cholesky_solve(self, radius: float, want_S: bool = False):
         n = 6 * self.problem.n_cams

@@ -417,8 +417,8 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
                     for (int k = 0; k < 6; ++k) hcv[k] = hc[k];
                     gv[0] = g[0]; gv[1] = g[1]; gv[2] = g[2];
                 }
-                double F[12], E[6];
-                load_FE(d, s.slot, s.cam, s.pt, F, E);
+                double F[12], E[6], r0, r1;                 // (r: unused here, dead on the recompute path)
+                load_FE_rc(d, s.slot, s.cam, s.pt, F, E, r0, r1);
                 if (PREP) { double hf[6]; point_factor(hcv, radius, hf);
 #pragma unroll
                     for (int k = 0; k < 6; ++k) hcv[k] = hf[k]; }
@@ -625,8 +625,8 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
         }
         double Va[18];
         {
-            double Fa[12], Ea[6], o28[28];
-            load_FE(d, sa, d.slot_cam[sa], pt, Fa, Ea);
+            double Fa[12], Ea[6], o28[28], r0, r1;
+            load_FE_rc(d, sa, d.slot_cam[sa], pt, Fa, Ea, r0, r1);
             pairs_V<PREP>(Fa, Ea, hc, Va);
             pairs_diag<PREP>(Fa, Va, hc, d.gp + 3 * (size_t)pt, o28);
             double* out = d.scat + 28 * (size_t)d.slot_campos_g[sa];
@@ -641,8 +641,8 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
         const int npair = slot_pair_ptr[sa + 1] - pbase;
         for (int dd = 1; dd <= npair; ++dd) {
             const int sb = sa + dd;
-            double Fb[12], Eb[6], Vb[18];
-            load_FE(d, sb, d.slot_cam[sb], pt, Fb, Eb);
+            double Fb[12], Eb[6], Vb[18], r0, r1;
+            load_FE_rc(d, sb, d.slot_cam[sb], pt, Fb, Eb, r0, r1);
             pairs_V<PREP>(Fb, Eb, hc, Vb);
             double* out = scat2 + 36 * (size_t)pair_dst[pbase + dd - 1];
             for (int rb = 0; rb < 6; ++rb)

@@ -74,7 +74,10 @@ struct Dev {
     double* scale_c; double* scale_p;
     // linearisation (SoA over slots: component-major)
     double* rt; double* Jp;   // rt[2][n]: robustified residual; Jp[6][n]: sqrt(rho') * d r / d Pc (2x3) — the camera (2x6)
-                              // and point (2x3) blocks are rebuilt from it by load_FE() ("compressed J": 64 instead of 160 B/obs)
+                              // and point (2x3) blocks are rebuilt from it by load_FE() ("compressed J": 64 instead of 160 B/obs).
+                              // nullptr = J-free linearisation (the Cholesky path's default): k_linearize stores neither, the
+                              // consumers recompute both from the state and uv (load_FE_rc) — only the PCG path and bal9 keep them
+    double huber_a;           // Huber parameter of the current linearisation (the recomputing consumers need it)
     CamLin* camrec;           // [Nc] per-camera linearisation record (rotation matrix, scale*mask of the 6 columns)
     double* Hpp; double* gp; double* Hinv;
     double* Hc;          // [n_pts][6] lower Cholesky factor of Hinv (c00 c10 c20 c11 c21 c22): S assembly uses V = W Hc
@@ -241,19 +244,38 @@ __device__ __forceinline__ SlotCtx load_slot(const Dev& d, int tile, int lane) {
 }
 
 
+// Residual of one observation, robustified: pr (projection and d r / d Pc), rho and sw = sqrt(rho').  The one place that
+// evaluates it for the linearisation: k_linearize and the consumers that recompute what it no longer stores (obs_rj).
+__device__ __forceinline__ void robust_obs(const double (&M)[9], const double t[3], const double* intr, int model, const double Pw[3],
+                                           double u, double v, double huber_a, Proj& pr, double& rho, double& sw) {
+    project<true>(M, t, intr, model, Pw, u, v, pr);
+    double rho1;
+    rho = huber(pr.r0 * pr.r0 + pr.r1 * pr.r1, huber_a, rho1);
+    sw = sqrt(rho1);
+}
+
+// What k_linearize stores in rt / Jp for one observation, recomputed at the current state: r = sw r, j = sw d r / d Pc.
+// M: the camera's CamLin::M (quat_to_mat of the same q k_linearize converts).  The outputs leave through an empty asm, so
+// the arithmetic that consumes them is contracted exactly as it is on a loaded value (bit-identical to the stored path).
+__device__ __forceinline__ void obs_rj(const Dev& d, int slot, int cam, const double (&M)[9], const double Pw[3],
+                                       double& r0, double& r1, double (&j)[6]) {
+    const CamRec& c = d.cam[cam];
+    const double t[3] = {c.t[0], c.t[1], c.t[2]};
+    Proj pr;
+    double rho, sw;
+    robust_obs(M, t, c.intr, d.cam_model[cam], Pw, d.slot_u[slot], d.slot_v[slot], d.huber_a, pr, rho, sw);
+    r0 = pr.r0 * sw; r1 = pr.r1 * sw;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) j[k] = pr.jp[k] * sw;
+    asm("" : "+v"(r0), "+v"(r1));
+#pragma unroll
+    for (int k = 0; k < 6; ++k) asm("" : "+v"(j[k]));
+}
+
 // Rebuild the Jacobi-scaled, robustified blocks of one observation:
 //   F (2x6) = [ -2 (j x M P) * sq | j * st ],   E (2x3) = (j M) * sp        (j = rows of Jp)
-__device__ __forceinline__ void load_FE(const Dev& d, int slot, int cam, int pt, double (&F)[12], double (&E)[6]) {
-    const size_t ns = (size_t)d.n_slots;
-    double j[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
-    const CamLin& c = d.camrec[cam];
-    double M[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
-    const double* P = d.P + 3 * (size_t)pt;
-    const double P0 = P[0], P1 = P[1], P2 = P[2];
+__device__ __forceinline__ void fe_from_j(const Dev& d, const CamLin& c, const double (&M)[9], int pt, const double P0, const double P1,
+                                          const double P2, const double (&j)[6], double (&F)[12], double (&E)[6]) {
     const double rp0 = M[0] * P0 + M[1] * P1 + M[2] * P2;
     const double rp1 = M[3] * P0 + M[4] * P1 + M[5] * P2;
     const double rp2 = M[6] * P0 + M[7] * P1 + M[8] * P2;
@@ -273,6 +295,41 @@ __device__ __forceinline__ void load_FE(const Dev& d, int slot, int cam, int pt,
         E[3 * row + 1] = (a * M[1] + b * M[4] + cc * M[7]) * sp1;
         E[3 * row + 2] = (a * M[2] + b * M[5] + cc * M[8]) * sp2;
     }
+}
+
+// F / E from the stored Jp (the PCG path and k_debug_materialize with stored J)
+__device__ __forceinline__ void load_FE(const Dev& d, int slot, int cam, int pt, double (&F)[12], double (&E)[6]) {
+    const size_t ns = (size_t)d.n_slots;
+    double j[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
+    const CamLin& c = d.camrec[cam];
+    double M[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
+    const double* P = d.P + 3 * (size_t)pt;
+    fe_from_j(d, c, M, pt, P[0], P[1], P[2], j, F, E);
+}
+
+// F / E and the robustified residual r of one observation: from rt / Jp when they are stored, recomputed from the state and
+// uv otherwise (d.Jp == nullptr, a wave-uniform test).  The same F / E arithmetic either way (fe_from_j).
+__device__ __forceinline__ void load_FE_rc(const Dev& d, int slot, int cam, int pt, double (&F)[12], double (&E)[6], double& r0, double& r1) {
+    const size_t ns = (size_t)d.n_slots;
+    const CamLin& c = d.camrec[cam];
+    double M[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
+    const double* P = d.P + 3 * (size_t)pt;
+    const double Pw[3] = {P[0], P[1], P[2]};
+    double j[6];
+    if (d.Jp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
+        r0 = d.rt[slot]; r1 = d.rt[ns + slot];
+    } else {
+        obs_rj(d, slot, cam, M, Pw, r0, r1, j);
+    }
+    fe_from_j(d, c, M, pt, Pw[0], Pw[1], Pw[2], j, F, E);
 }
 
 // Per-camera linearisation record (run before every linearisation: cameras, scales and masks as they are now).
@@ -330,11 +387,9 @@ __device__ __forceinline__ void linearize_item(const Dev& d, const Item& it, int
             double M[9];
             quat_to_mat(q, M);
             Proj pr;
-            project<true>(M, t, c.intr, d.cam_model[s.cam], Pw, d.slot_u[s.slot], d.slot_v[s.slot], pr);
-            double rho1;
-            const double rho = huber(pr.r0 * pr.r0 + pr.r1 * pr.r1, huber_a, rho1);
+            double rho, sw;
+            robust_obs(M, t, c.intr, d.cam_model[s.cam], Pw, d.slot_u[s.slot], d.slot_v[s.slot], huber_a, pr, rho, sw);
             cost = cost + rho;
-            const double sw = sqrt(rho1);
             const double r0 = pr.r0 * sw, r1 = pr.r1 * sw;
             const unsigned cc = d.cam_const[s.cam];
             const double mq = (cc & 1u) ? 0.0 : sw, mt = (cc & 2u) ? 0.0 : sw;
@@ -358,10 +413,12 @@ __device__ __forceinline__ void linearize_item(const Dev& d, const Item& it, int
                 E[3 * row + 1] = (j[0] * M[1] + j[1] * M[4] + j[2] * M[7]) * mp * spk[1];
                 E[3 * row + 2] = (j[0] * M[2] + j[1] * M[5] + j[2] * M[8]) * mp * spk[2];
             }
-            const size_t ns = (size_t)d.n_slots;
-            d.rt[s.slot] = r0; d.rt[ns + s.slot] = r1;
+            if (d.Jp) {                                  // (wave-uniform: J-free linearisations store neither)
+                const size_t ns = (size_t)d.n_slots;
+                d.rt[s.slot] = r0; d.rt[ns + s.slot] = r1;
 #pragma unroll
-            for (int k = 0; k < 6; ++k) d.Jp[k * ns + s.slot] = pr.jp[k] * sw;
+                for (int k = 0; k < 6; ++k) d.Jp[k * ns + s.slot] = pr.jp[k] * sw;
+            }
             v[0] = E[0] * E[0] + E[3] * E[3]; v[1] = E[0] * E[1] + E[3] * E[4]; v[2] = E[0] * E[2] + E[3] * E[5];
             v[3] = E[1] * E[1] + E[4] * E[4]; v[4] = E[1] * E[2] + E[4] * E[5]; v[5] = E[2] * E[2] + E[5] * E[5];
             v[6] = E[0] * r0 + E[3] * r1; v[7] = E[1] * r0 + E[4] * r1; v[8] = E[2] * r0 + E[5] * r1;
@@ -648,11 +705,29 @@ __global__ __launch_bounds__(kBlock) void k_chol_segsum_v(const double* __restri
 __global__ void k_debug_materialize(Dev d, double* __restrict__ Fs, double* __restrict__ Es) {
     const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= d.n_slots || d.slot_cam[slot] < 0) return;
-    double F[12], E[6];
-    load_FE(d, slot, d.slot_cam[slot], d.slot_pt[slot], F, E);
+    double F[12], E[6], r0, r1;
+    load_FE_rc(d, slot, d.slot_cam[slot], d.slot_pt[slot], F, E, r0, r1);
     const size_t ns = (size_t)d.n_slots;
     for (int k = 0; k < 12; ++k) Fs[k * ns + slot] = F[k];
     for (int k = 0; k < 6; ++k) Es[k * ns + slot] = E[k];
+}
+
+// rt / Jp of the current linearisation as k_linearize stores them, recomputed (obs_rj): a J-free linearisation's residuals
+// for the diagnostics, and the stored J a PCG product needs after one (either output may be nullptr).
+__global__ void k_materialize_rj(Dev d, double* __restrict__ rt, double* __restrict__ Jp) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= d.n_slots || d.slot_cam[slot] < 0) return;
+    const int cam = d.slot_cam[slot];
+    const CamLin& c = d.camrec[cam];
+    double M[9];
+    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
+    const double* P = d.P + 3 * (size_t)d.slot_pt[slot];
+    const double Pw[3] = {P[0], P[1], P[2]};
+    double r0, r1, j[6];
+    obs_rj(d, slot, cam, M, Pw, r0, r1, j);
+    const size_t ns = (size_t)d.n_slots;
+    if (rt) { rt[slot] = r0; rt[ns + slot] = r1; }
+    if (Jp) for (int k = 0; k < 6; ++k) Jp[k * ns + slot] = j[k];
 }
 
 // Jacobi scaling from the column norms of the unscaled Jacobian: 1/(1+|col|).
@@ -1303,7 +1378,6 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
     const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));   // wave-uniform: item / tile records through scalar loads
     if (item >= d.n_items) return;
     const Item it = d.items[item];
-    const size_t ns = (size_t)d.n_slots;
     double model = 0.0, step2 = 0.0;
     if (it.n_tiles == 1) {
         const SlotCtx s = load_slot(d, it.first_tile, lane);
@@ -1329,9 +1403,8 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
         if (s.valid) {
             const double* yp = d.px + 6 * (size_t)s.cam;
             const double y[6] = {yp[0], yp[1], yp[2], yp[3], yp[4], yp[5]};
-            r0 = d.rt[s.slot]; r1 = d.rt[ns + s.slot];
             double F[12];
-            load_FE(d, s.slot, s.cam, s.pt, F, E);
+            load_FE_rc(d, s.slot, s.cam, s.pt, F, E, r0, r1);
             v0 = 0.0; v1 = 0.0;
 #pragma unroll
             for (int k = 0; k < 6; ++k) { v0 += F[k] * y[k]; v1 += F[6 + k] * y[k]; }
@@ -1380,8 +1453,8 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
             if (cam >= 0) {
                 pt0 = d.slot_pt[slot];
                 const double* y = d.px + 6 * (size_t)cam;
-                double F[12], E[6];
-                load_FE(d, slot, cam, pt0, F, E);
+                double F[12], E[6], r0, r1;
+                load_FE_rc(d, slot, cam, pt0, F, E, r0, r1);
                 double v0 = 0.0, v1 = 0.0;
 #pragma unroll
                 for (int k = 0; k < 6; ++k) { v0 += F[k] * y[k]; v1 += F[6 + k] * y[k]; }
@@ -1428,14 +1501,14 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
             const int cam = d.slot_cam[slot];
             if (cam >= 0) {
                 const double* y = d.px + 6 * (size_t)cam;
-                double F[12], E[6];
-                load_FE(d, slot, cam, pt0, F, E);
+                double F[12], E[6], r0, r1;
+                load_FE_rc(d, slot, cam, pt0, F, E, r0, r1);
                 double v0 = 0.0, v1 = 0.0;
 #pragma unroll
                 for (int k = 0; k < 6; ++k) { v0 += F[k] * y[k]; v1 += F[6 + k] * y[k]; }
                 const double m0 = v0 + E[0] * u[0] + E[1] * u[1] + E[2] * u[2];
                 const double m1 = v1 + E[3] * u[0] + E[4] * u[1] + E[5] * u[2];
-                model += m0 * (d.rt[slot] - 0.5 * m0) + m1 * (d.rt[ns + slot] - 0.5 * m1);
+                model += m0 * (r0 - 0.5 * m0) + m1 * (r1 - 0.5 * m1);
             }
         }
     }

@@ -193,6 +193,9 @@ struct xrsfm_ba_context {
     // Second set of linearisation buffers: every LM step linearises at the CANDIDATE point right after the back-substitution
     // (its cost is the candidate cost the step test needs, so no separate cost pass exists); an accepted step swaps the sets.
     struct LinBuf { double* rt = nullptr; double* Jp = nullptr; CamLin* camrec = nullptr; double* Hpp = nullptr; double* gp = nullptr; double* camlin = nullptr; } alt;
+    // Stored J (rt / Jp of both sets, 2 x 64 B per slot): allocated on the first run that needs it (PCG, bal9, XRSFM_BA_JFREE=0);
+    // d.rt / d.Jp and alt.rt / alt.Jp point into it while J is stored and are nullptr on a J-free run (use_stored_j)
+    double* jbuf[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<unsigned long long> pattern_keys;   // union of the ranks' off-diagonal camera pairs ((row << 32) | col), sorted
     bool have_pattern = false;
     CholHost chol;
@@ -533,6 +536,44 @@ int fetch_scalars(xrsfm_ba_context* c) {
 // the scalar block and camlin / Hpp / gp / rt / Jp of that view filled.  with_step: the partial sums the preceding
 // back-substitution left (model decrease, squared step norms, |x_cams|^2) are reduced by the same launch and, with several
 // ranks, travel in the same all-reduce: layout behind the camera block = [cost, |x_pts|^2, model, |step_pts|^2, rank slots].
+// J-free linearisation (Cholesky path): k_linearize stores no rt / Jp, k_schur_pairs and k_backsub recompute them (load_FE_rc).
+// It saves the 128 B per slot k_linearize writes and the consumers read back, and costs the recomputation in every k_schur_pairs
+// and k_backsub launch, so it pays only while there is about one consumer pass per linearisation.  A run therefore keeps J
+// stored (jfree_for_run) when the plan has per-pair / long-track items (their loop would recompute an observation once per
+// partner), and switches to stored J at its first rejected step (retries consume the same linearisation again; the current one
+// is materialised once).  Below kJfreeMinSlots the kernels are latency-bound and the bytes saved do not pay for the longer
+// chain (config S: 0.06 ms per solve slower).  XRSFM_BA_JFREE=0 keeps J stored throughout, =1 drops the size floor (read per
+// run: the A/B tests switch it inside one process).
+constexpr int kJfreeMinSlots = 1 << 20;
+int jfree_setting() {           // 0 / 1: set, -1: not set
+    const char* e = std::getenv("XRSFM_BA_JFREE");
+    return e ? (e[0] == '0' ? 0 : 1) : -1;
+}
+bool jfree_enabled() { return jfree_setting() != 0; }
+// Switch the context between stored and recomputed J.  Turning storage on allocates the buffers the first time; what they hold
+// is stale until the next linearisation, or until `materialize` recomputes them from the current one (its state and d.huber_a).
+int use_stored_j(xrsfm_ba_context* c, bool on, bool materialize = false) {
+    Dev& d = c->d;
+    if (!on) { d.rt = d.Jp = c->alt.rt = c->alt.Jp = nullptr; return 0; }
+    if (d.Jp) return 0;
+    const size_t ns = (size_t)d.n_slots;
+    for (int i = 0; i < 4; ++i) {       // (a buffer that was allocated stays: a failed call is not repeated from scratch)
+        if (c->jbuf[i]) continue;
+        if (int e = dev_alloc(c, &c->jbuf[i], ns * (i & 1 ? 6 : 2))) { c->jbuf[i] = nullptr; return e; }
+    }
+    d.rt = c->jbuf[0]; d.Jp = c->jbuf[1]; c->alt.rt = c->jbuf[2]; c->alt.Jp = c->jbuf[3];
+    if (materialize && ns) {
+        hipLaunchKernelGGL(k_materialize_rj, dim3(cdiv((long long)ns, kBlock)), dim3(kBlock), 0, c->stream, d, d.rt, d.Jp);
+        if (hipGetLastError() != hipSuccess) return XRSFM_BA_ENODEV;
+    }
+    return 0;
+}
+
+bool jfree_for_run(const xrsfm_ba_context* c, int solver) {
+    const int set = jfree_setting();
+    return solver == XRSFM_BA_SOLVER_CHOLESKY && c->chol.n_pairs_other == 0 && (set == 1 || (set < 0 && c->d.n_slots >= kJfreeMinSlots));
+}
+
 enum { LIN_SKIP_CAMLIN = 1, LIN_FINAL = 2 };    // LIN_FINAL: gradient max-norm and the hand-over to the host follow this linearisation
 int linearize(xrsfm_ba_context* c, double huber_a, const Dev& d, bool with_step, int flags = 0) {
     const Dev& own = c->d;
@@ -541,6 +582,7 @@ int linearize(xrsfm_ba_context* c, double huber_a, const Dev& d, bool with_step,
     // caller skip k_gradmax_cams / k_publish and read stale scalars)
     c->gradmax_done = false; c->published = false;
     c->step_valid = false;
+    c->d.huber_a = huber_a;         // (what the recomputing consumers of this linearisation use)
     if (d.n_cams > 0 && !(flags & LIN_SKIP_CAMLIN)) LAUNCH(c, K_SMALL, k_cam_lin, dim3(cdiv(d.n_cams, kBlock)), dim3(kBlock), 0, d);
     if (d.n_items > 0) LAUNCH(c, K_LINEARIZE, k_linearize, dim3(cdiv(d.n_items, kWavesPerBlock)), dim3(kBlock), kWavesPerBlock * kWave * 13 * sizeof(double), d, huber_a);
     if (!c->fused && d.n_cams > 0) LAUNCH(c, K_CAM_SEGSUM, k_cam_segsum<12>, dim3(d.n_cams), dim3(kBlock), 0, d.scat, d.cam_ptr_g, d.camlin, (const PcgStatus*)nullptr);
@@ -607,6 +649,7 @@ int prepare_step(xrsfm_ba_context* c, double radius, bool with_blocks = false) {
     c->step_radius = radius;
     c->step_prep = with_blocks && c->prep_fused;
     if (c->step_prep) return 0;     // Cholesky path: k_schur_pairs / k_backsub / the tile fill form what they need from Hpp, camlin and the radius
+    if (!with_blocks && !d.Jp) return XRSFM_BA_EINTERNAL;      // (k_schur_prep / k_schur_matvec read stored J: use_stored_j)
     {
         const int nbp = cdiv(d.n_pts, kBlock), nbc = cdiv((long long)d.n_cams * 6, kBlock);
         if (nbp + nbc > 0) LAUNCH(c, K_SMALL, k_point_prep, dim3(nbp + nbc), dim3(kBlock), 0, d, radius, dmin, dmax, nbp);
@@ -1592,8 +1635,8 @@ static int create_body(const xrsfm_ba_problem* p, int device, xrsfm_ba_context* 
     timer.mark("uploads");
     const size_t ns = (size_t)k.n_slots, nc = (size_t)k.n_cams, np = (size_t)k.n_pts;
     TRY(dev_alloc(c, &d.scale_c, nc * 6)); TRY(dev_alloc(c, &d.scale_p, np * 3));
-    TRY(dev_alloc(c, &d.rt, ns * 2)); TRY(dev_alloc(c, &d.Jp, ns * 6)); TRY(dev_alloc(c, &d.camrec, nc));
-    TRY(dev_alloc(c, &c->alt.rt, ns * 2)); TRY(dev_alloc(c, &c->alt.Jp, ns * 6)); TRY(dev_alloc(c, &c->alt.camrec, nc));
+    d.rt = d.Jp = nullptr;          // (stored J: use_stored_j, on the first run that needs it)
+    TRY(dev_alloc(c, &d.camrec, nc)); TRY(dev_alloc(c, &c->alt.camrec, nc));
     TRY(dev_alloc(c, &d.Hpp, np * 6)); TRY(dev_alloc(c, &d.gp, np * 3)); TRY(dev_alloc(c, &c->alt.Hpp, np * 6)); TRY(dev_alloc(c, &c->alt.gp, np * 3)); TRY(dev_alloc(c, &d.Hinv, np * 6)); TRY(dev_alloc(c, &d.Hc, np * 6));
     TRY(dev_alloc(c, &d.camlin, nc * 12 + 4 + kMaxRanks)); TRY(dev_alloc(c, &c->alt.camlin, nc * 12 + 4 + kMaxRanks)); TRY(dev_alloc(c, &d.Dc2, nc * 6)); TRY(dev_alloc(c, &d.camS, nc * 28));
     TRY(dev_alloc(c, &d.Minv, nc * 21)); TRY(dev_alloc(c, &d.b, nc * 6));
@@ -1731,6 +1774,7 @@ int xrsfm_ba_download(xrsfm_ba_context* c, double* cam_q, double* cam_t, double*
 // bal9 mode: the same trust-region loop over the 9-wide kernels of ba_wide.h.  Plain schedule — linearise, assemble,
 // factor, back-substitute, cost of the candidate, linearise again after an accepted step — through the launch-per-phase tail.
 static int linearize_wide(xrsfm_ba_context* c, double huber_a, bool scaled_pass) {
+    if (int e = use_stored_j(c, true)) return e;        // (bal9 keeps stored J)
     Dev& d = c->d;
     (void)scaled_pass;
     c->gradmax_done = false; c->published = false;
@@ -1865,6 +1909,7 @@ static int run_wide(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_s
             print_progress(opt, it, cost, 0.0, gmax, 0.0, 0.0, radius);
             if (invalid >= 5) return finish(XRSFM_BA_FAILURE, 6, cost);
             radius /= decrease; decrease *= 2.0;
+            if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
             continue;
         }
         invalid = 0;
@@ -1931,6 +1976,7 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
         return e;
     }
     if (c->wide) return run_wide(c, opt, sum);
+    if ((e = use_stored_j(c, !jfree_for_run(c, solver)))) return e;
     sum->linear_solver_used = solver;
     c->profiling = opt.profile != 0;
     for (int i = 0; i < K_COUNT; ++i) { c->prof_ms[i] = 0.0; c->prof_n[i] = 0; }
@@ -1993,6 +2039,7 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
             print_progress(opt, it, cost, 0.0, gmax, 0.0, 0.0, radius);
             if (invalid >= 5) return finish(XRSFM_BA_FAILURE, 6, cost);
             radius /= decrease; decrease *= 2.0;
+            if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
             continue;
         }
         invalid = 0;
@@ -2027,6 +2074,7 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
         } else {
             speculate = false; accepted_run = 0;
             radius /= decrease; decrease *= 2.0;
+            if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
             sum->n_unsuccessful++;
             print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, radius);
             if (radius < min_radius) return finish(XRSFM_BA_CONVERGENCE, 4, cost);
@@ -2417,6 +2465,7 @@ int xrsfm_ba_debug_linearize(xrsfm_ba_context* c, double huber_a, int use_scalin
     Dev& d = c->d;
     int e;
     if ((e = ensure_host_pack(c, 2))) return e;
+    if ((e = use_stored_j(c, !jfree_enabled()))) return e;         // (the Cholesky path's choice, like a run's)
     if ((e = init_scaling_and_linearize(c, huber_a, use_scaling != 0))) return e;
     if ((e = fetch_scalars(c))) return e;
     if (cost) *cost = 0.5 * c->h_scal[S_COST];
@@ -2428,7 +2477,16 @@ int xrsfm_ba_debug_linearize(xrsfm_ba_context* c, double huber_a, int use_scalin
         return 0;
     };
     std::vector<double> h;
-    if (r) {
+    if (r && !d.rt) {               // J-free linearisation: the residuals are materialised with the consumers' recomputation
+        double* dr = nullptr;
+        if (hipMalloc((void**)&dr, (ns ? ns : 1) * 2 * sizeof(double)) != hipSuccess) return XRSFM_BA_ENOMEM;
+        if (ns) hipLaunchKernelGGL(k_materialize_rj, dim3(cdiv((long long)ns, kBlock)), dim3(kBlock), 0, c->stream, d, dr, (double*)nullptr);
+        e = (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) ? XRSFM_BA_ENODEV : 0;
+        if (!e) e = fetch(dr, ns * 2, h);
+        (void)hipFree(dr);
+        if (e) return e;
+        for (size_t s = 0; s < ns; ++s) if (k.slot_obs[s] >= 0) { r[2 * (size_t)k.slot_obs[s]] = h[s]; r[2 * (size_t)k.slot_obs[s] + 1] = h[ns + s]; }
+    } else if (r) {
         if ((e = fetch(d.rt, ns * 2, h))) return e;
         for (size_t s = 0; s < ns; ++s) if (k.slot_obs[s] >= 0) { r[2 * (size_t)k.slot_obs[s]] = h[s]; r[2 * (size_t)k.slot_obs[s] + 1] = h[ns + s]; }
     }
@@ -2544,6 +2602,12 @@ int xrsfm_ba_download_intrinsics(xrsfm_ba_context* c, double* intr_params) {
     return XRSFM_BA_OK;
 }
 
+int xrsfm_ba_debug_stored_j(xrsfm_ba_context* c, int32_t* stored) {
+    if (!c || !stored) return XRSFM_BA_EINVAL;
+    *stored = c->d.Jp != nullptr;
+    return 0;
+}
+
 int xrsfm_ba_debug_schur_product(xrsfm_ba_context* c, double radius, const double* x, double* y, double* b) {
     if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
     if (c && c->wide) return XRSFM_BA_EINVAL;
@@ -2552,6 +2616,7 @@ int xrsfm_ba_debug_schur_product(xrsfm_ba_context* c, double radius, const doubl
     HIPCHK(hipSetDevice(c->device));
     Dev& d = c->d;
     int e;
+    if ((e = use_stored_j(c, true, true))) return e;      // (the PCG product reads stored J: materialised after a J-free linearisation)
     if ((e = prepare_step(c, radius))) return e;
     HIPCHK(hipMemsetAsync(d.st, 0, sizeof(PcgStatus), c->stream));
     const size_t n = (size_t)d.n_cams * 6;
