@@ -347,6 +347,11 @@ int xrsfm_ba_debug_pack(const xrsfm_ba_problem *problem, int32_t stats[8], int32
  * distinct camera of a Gram tile), [3] largest C, [4]/[5]/[6] items in the small-LDS Gram class / big-LDS Gram class /
  * per-pair + long class, [7] partial blocks written per pass.  tile_ncam (may be NULL): [tiles]; slot_cidx (may be NULL):
  * [slots], 255 outside Gram tiles; slot_campos_g (may be NULL): [slots], -1 for non-writers. */
+/* Tile groups of the S assembly's merged Gram launch (G tiles per workgroup) on the host-packed tables: per launch position its tile
+ * and code (index in its run | run length << 4), per tile L and the cameras / cidx of its first min(L, 4) slots ([n_tiles][4], -1
+ * beyond), stats = {positions, camera entries, camera entries kept}, cam_ptr_s [n_cams + 1]. */
+int xrsfm_ba_debug_sgroup(const xrsfm_ba_problem *problem, int G, int32_t stats[3], int32_t *pos_tile, int32_t *pos_code,
+                          int32_t *tile_stride, int32_t *tile_cams, int32_t *tile_cidx, int32_t *cam_ptr_s);
 int xrsfm_ba_debug_pack_gram(const xrsfm_ba_problem *problem, int32_t stats[8], int32_t *tile_ncam, uint8_t *slot_cidx,
                              int32_t *slot_campos_g);
 

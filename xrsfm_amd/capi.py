@@ -89,7 +89,7 @@ EXPORTS = [
     "xrsfm_ba_solve", "xrsfm_ba_filter_tracks", "xrsfm_ba_profile_entry", "xrsfm_ba_debug_linearize", "xrsfm_ba_debug_schur_product",
     "xrsfm_ba_debug_cholesky_solve", "xrsfm_ba_debug_set_block_pattern", "xrsfm_ba_debug_pack", "xrsfm_ba_debug_chol_plan", "xrsfm_ba_refine_pose", "xrsfm_ba_refine_pose_options", "xrsfm_ba_debug_comm_hook", "xrsfm_pg_default_options", "xrsfm_pg_solve", "xrsfm_ba_debug_pack_gram", "xrsfm_ba_debug_gram_schedule",
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
-    "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j",
+    "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
 ]
 
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
@@ -159,6 +159,8 @@ def load(path: str | None = None):
     lib.xrsfm_ba_refine_pose.restype = C.c_int
     lib.xrsfm_ba_debug_pack_gram.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p, _c_uint8_p, _c_int32_p]
     lib.xrsfm_ba_debug_pack_gram.restype = C.c_int
+    lib.xrsfm_ba_debug_sgroup.argtypes = [C.POINTER(CProblem), C.c_int] + [_c_int32_p] * 7
+    lib.xrsfm_ba_debug_sgroup.restype = C.c_int
     lib.xrsfm_ba_debug_chol_plan.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p]
     lib.xrsfm_ba_debug_chol_plan.restype = C.c_int
     lib.xrsfm_ba_debug_pack.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p]
@@ -598,6 +600,24 @@ def debug_gram_schedule(n_cams: int) -> dict:
     check(f(int(n_cams), C.byref(n), C.byref(na), ent.ctypes.data_as(C.POINTER(C.c_uint16))), "xrsfm_ba_debug_gram_schedule")
     e = ent[:4 * na.value]
     return dict(n_inst=n.value, n_inst_all=na.value, blocks=[(int(v & 255), int(v >> 8)) for v in e])
+
+
+def debug_sgroup(problem: ProblemArrays, G: int = 4) -> dict:
+    """Tile groups of the S assembly's merged Gram launch on the host-side packing (works without a GPU): per launch position its
+    tile and code (index in run | length << 4); per tile L and the cameras / cidx of its first slots; the compact camera pointers."""
+    st = debug_pack(problem)
+    nt, ns, nc = max(st["tiles"], 1), max(st["slots"], 1), int(problem.n_cams)
+    stats = np.zeros(3, np.int32)
+    ptile = np.zeros(nt, np.int32); pcode = np.zeros(nt, np.int32); tstride = np.zeros(nt, np.int32)
+    tcams = np.zeros((nt, 4), np.int32); tcidx = np.zeros((nt, 4), np.int32); cptr = np.zeros(nc + 1, np.int32)
+    cs = problem.c_struct()
+    p = lambda a: a.ctypes.data_as(_c_int32_p)
+    check(load().xrsfm_ba_debug_sgroup(C.byref(cs), int(G), p(stats), p(ptile), p(pcode), p(tstride), p(tcams), p(tcidx), p(cptr)),
+          "xrsfm_ba_debug_sgroup")
+    n = int(stats[0])
+    return dict(positions=n, cam_entries=int(stats[1]), cam_entries_kept=int(stats[2]), pos_tile=ptile[:n], pos_code=pcode[:n],
+                tile_stride=tstride[:st["tiles"]], tile_cams=tcams[:st["tiles"]], tile_cidx=tcidx[:st["tiles"]], cam_ptr_s=cptr,
+                gram=debug_pack_gram(problem))
 
 
 def debug_pack_gram(problem: ProblemArrays) -> dict:

@@ -106,6 +106,44 @@ __device__ __forceinline__ void pairs_diag(const double* F, const double* V, con
     o28[27] = 0.0;
 }
 
+// (round 8) A Gram tile of a group of G tiles with one tuple (ba_kernels.h: k_sgroup_table).  idx: the wave's place in its run, len: the
+// run's length (1: the tile writes its records itself, as before); base: the head of the wave's own LDS region (the staged operand, dead
+// once the products are formed), consecutive waves' regions wld doubles apart; ds0 / ds1: the lane's two halves of the diagonal-block /
+// rhs records, dofs their place in the scatter buffer (-1: the lane writes none).
+struct SGroup { int idx, len; double* base; int wld; double ds0, ds1; int dofs; };
+// The waves of a run after the products: all but the first deposit their NV values and diagonal halves at the head of their region, one
+// workgroup barrier, the first adds them in wave order, stores the diagonal records and returns true (then its Gram cells); the others
+// return false.  Every wave of a run reaches the barrier exactly once; a group of one never does (a wave that has ended does not hold
+// a barrier).
+// (NV values of W doubles each: the 4x4 form's accumulators, or the 16x16 form's 4-vectors)
+template <int NV, typename V>
+__device__ __forceinline__ bool sgroup_finish(SGroup g, V (&v)[NV], double* __restrict__ scat, int lane) {
+    constexpr int W = sizeof(V) / sizeof(double);
+    if (g.idx > 0) {
+#pragma unroll
+        for (int i = 0; i < NV * W; ++i) g.base[i * kWave + lane] = reinterpret_cast<const double*>(&v[i / W])[i % W];
+        g.base[NV * W * kWave + lane] = g.ds0;
+        g.base[(NV * W + 1) * kWave + lane] = g.ds1;
+    }
+    __syncthreads();
+    if (g.idx > 0) return false;
+    for (int j = 1; j < g.len; ++j) {
+        const double* src = g.base + (size_t)j * g.wld;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            if constexpr (W == 1) v[i] += src[i * kWave + lane];
+            else {
+#pragma unroll
+                for (int q = 0; q < W; ++q) v[i][q] += src[(i * W + q) * kWave + lane];
+            }
+        }
+        g.ds0 += src[NV * W * kWave + lane];
+        g.ds1 += src[(NV * W + 1) * kWave + lane];
+    }
+    if (g.dofs >= 0) { scat[g.dofs] = g.ds0; scat[g.dofs + 14] = g.ds1; }
+    return true;
+}
+
 // G = V V^T for a Gram tile whose operand has NI 16-row tiles (row stride Cp doubles).  The tracks are staged in `passes`
 // rounds of Th tracks (two rounds when one would not fit the small LDS class: the accumulators simply carry over); per
 // K-step of 4 every lane reads ONE value per row tile — the same register is the A operand of the products in its tile row
@@ -115,7 +153,8 @@ __device__ __forceinline__ void pairs_diag(const double* F, const double* V, con
 template <int NI, int CW = 6>
 __device__ __forceinline__ void gram_tile(double* __restrict__ Vst, int R, int Cp, int C, const int* __restrict__ dtab,
                                           double* __restrict__ scat2, int lane, const double (&V)[3 * CW], bool valid, int t, int cidx,
-                                          int T, int Th, int passes, bool dense) {
+                                          int T, int Th, int passes, bool dense, SGroup sg = SGroup{0, 1, nullptr, 0, 0.0, 0.0, -1},
+                                          double* __restrict__ scat = nullptr) {
     static_assert(NI >= 1 && NI <= 4, "a Gram tile has at most 10 cameras = 60 operand rows (ba_pack.h: kGramMaxCams)");
     const int li = lane & 15, lk = lane >> 4;
     v4d acc[NI * (NI + 1) / 2];
@@ -166,6 +205,7 @@ __device__ __forceinline__ void gram_tile(double* __restrict__ Vst, int R, int C
         __builtin_amdgcn_wave_barrier();
     }
     XBA_STAMP(0, 7);
+    if (NI <= 2 && sg.len > 1 && !sgroup_finish(sg, acc, scat, lane)) return;      // (grouped tiles have at most 4 cameras: 24 operand rows)
     // blocks (camera rb > camera ra) to their destinations: dtab[ra][rb] (fixed stride), -1 = nothing to store
     (void)C; (void)R;
     int tcol[NI], jcol[NI];
@@ -258,7 +298,8 @@ template <int CW> __device__ __forceinline__ unsigned gram_cam_of_row(unsigned r
 // destinations — element (row, col) of the tile, camera rb = row / CW > camera ra = col / CW, goes to block dtab[ra][rb] (-1: nothing).
 template <int CW, int NB>
 __device__ __forceinline__ void gram4_batch(const double* __restrict__ Vst, int R, int Cp, int C4, const unsigned short* __restrict__ ent,
-                                            const int* __restrict__ dtab, double* __restrict__ scat2, int lane) {
+                                            const int* __restrict__ dtab, double* __restrict__ scat2, int lane, SGroup sg,
+                                            double* __restrict__ scat) {
     const int i4 = lane & 3, kk = lane >> 4;
     int e[NB];
 #pragma unroll
@@ -293,6 +334,7 @@ __device__ __forceinline__ void gram4_batch(const double* __restrict__ Vst, int 
             pa[u] += 32; pb[u] += 32;
         }
     }
+    if (sg.len > 1 && !sgroup_finish(sg, acc, scat, lane)) return;      // (before the destinations: fewer registers across the barrier)
     // (the destinations of all NB values are requested before the first store: one LDS round trip, not NB in a row; unsigned
     //  arithmetic: one 64-bit multiply-add and one shift-add form an address — with ints the compiler sign-extends every term)
     int dst[NB];
@@ -313,7 +355,8 @@ __device__ __forceinline__ void gram4_batch(const double* __restrict__ Vst, int 
 template <int CW = 6>
 __device__ __forceinline__ void gram_tile4(double* __restrict__ Vst, int R, int Cp, int C, const int* __restrict__ dtab,
                                            double* __restrict__ scat2, int lane, const double (&V)[3 * CW], bool valid, int t, int cidx,
-                                           int T, bool dense, const unsigned short* __restrict__ sched, int n_inst) {
+                                           int T, bool dense, const unsigned short* __restrict__ sched, int n_inst, SGroup sg,
+                                           double* __restrict__ scat) {
     const unsigned short* ent = sched + ((lane >> 2) & 3);      // (LDS copy of the tile's schedule: gram4_sched_load / _store)
     const int C4 = (3 * T + 3) & ~3;
     if (dense) {
@@ -336,12 +379,12 @@ __device__ __forceinline__ void gram_tile4(double* __restrict__ Vst, int R, int 
     __builtin_amdgcn_wave_barrier();
     XBA_STAMP(0, 6);
     switch (n_inst) {                              // (uniform; the caller takes this path for schedules of at most kGram4MaxInst instructions)
-        case 6: gram4_batch<CW, 6>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
-        case 5: gram4_batch<CW, 5>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
-        case 4: gram4_batch<CW, 4>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
-        case 3: gram4_batch<CW, 3>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
-        case 2: gram4_batch<CW, 2>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
-        default: gram4_batch<CW, 1>(Vst, R, Cp, C4, ent, dtab, scat2, lane); break;
+        case 6: gram4_batch<CW, 6>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
+        case 5: gram4_batch<CW, 5>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
+        case 4: gram4_batch<CW, 4>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
+        case 3: gram4_batch<CW, 3>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
+        case 2: gram4_batch<CW, 2>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
+        default: gram4_batch<CW, 1>(Vst, R, Cp, C4, ent, dtab, scat2, lane, sg, scat); break;
     }
     XBA_STAMP(0, 7);
 }
@@ -360,15 +403,29 @@ __device__ __forceinline__ void gram_tile4(double* __restrict__ Vst, int R, int 
 // only the 10-camera tiles (NIK = 4: 40 accumulators, 3 waves per SIMD) keep a launch of their own.  A ragged map had four to six
 // launches per pass, most of them too small to fill the chip and run side by side on two streams; now one (tiles in descending
 // height: the long ones start first).
+// (round 8) The merged launch runs G = blockDim.x / 64 consecutive launch positions per workgroup, one wave each, in its own LDS region of
+// wld doubles; sgrp (ba_kernels.h: k_sgroup_table) names the runs of same-tuple tiles whose records are added on chip (SGroup).
+// sgrp = nullptr: every tile writes its own records.  n_list: the length of the merged launch's list.
 template <bool GRAM, bool PREP, int NIK>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu((GRAM && NIK < 4) ? 4 : (GRAM ? 3 : 2), (GRAM && NIK < 4) ? 4 : 3)))      // no instantiation may spill (tests/test_capi_cpu.py)
+__global__ __launch_bounds__((GRAM && NIK == 0) ? kWave * kSGroupMax : kWave) __attribute__((amdgpu_waves_per_eu((GRAM && NIK < 4) ? 4 : (GRAM ? 3 : 2), (GRAM && NIK < 4) ? 4 : 3)))      // no instantiation may spill (tests/test_capi_cpu.py)
 void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restrict__ slot_pair_ptr, const int* __restrict__ pair_dst,
-                   int n_obs_pairs, double* __restrict__ scat2, double radius, double* __restrict__ pair_v = nullptr, int gram4 = 1) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int lane = threadIdx.x;
+                   int n_obs_pairs, double* __restrict__ scat2, double radius, double* __restrict__ pair_v = nullptr, int gram4 = 1,
+                   const int* __restrict__ sgrp = nullptr, int n_list = 0, int wld = 0) {
+    extern __shared__ __attribute__((aligned(16))) double smem_all[];
+    constexpr bool MERGED = GRAM && NIK == 0;
+    const int lane = MERGED ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;     // (mbcnt: threadIdx.x & 63 cost a register)
+    const int wave = MERGED ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    const int pos = MERGED ? (int)blockIdx.x * (int)(blockDim.x >> 6) + wave : (int)blockIdx.x;
+    if (MERGED && pos >= n_list) return;
+    double* const smem = smem_all + (size_t)wave * wld;
     XBA_STAMP(0, 0);
+    SGroup sg{0, 1, smem, wld, 0.0, 0.0, -1};
+    if (MERGED && sgrp) {
+        const int code = __builtin_amdgcn_readfirstlane(sgrp[pos]);
+        sg.idx = code & 15; sg.len = code >> 4;
+    }
     // one launch per LDS class (ba_plan.h); the Gram classes list tiles, the other class items
-    const int entry = item_list[(GRAM && NIK == 0) ? gridDim.x - 1 - blockIdx.x : blockIdx.x];      // (merged launch: the list ascends in height)
+    const int entry = item_list[MERGED ? n_list - 1 - pos : pos];      // (merged launch: the list ascends in height)
     Item it;
     if (GRAM) { it.first_tile = entry; it.n_tiles = 1; }
     else it = d.items[entry];
@@ -388,7 +445,7 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
             if (NIK <= 2 && gram4) g4_se = gram4_sched_load<6>(C0, lane, g4_n);       // (NIK = 0: g4_n = 0 for the tiles that take the 16x16 form)
         }
         const SlotCtx s = load_slot(d, it.first_tile, lane);
-        const int cp = d.slot_campos_g[s.slot];
+        const int cp = d.slot_campos_s[s.slot];
         const int cidx_raw = GRAM ? (int)d.slot_cidx[s.slot] : 0;
         const int L = d.tile_stride[it.first_tile];
         int g_pos = kWave - 1, g_pk0 = 0, g_pk1 = 0, g_pk2 = 0;      // ragged Gram tile: the per-camera sums' tables (used far below: the loads ride with the slot record)
@@ -466,7 +523,9 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
 #pragma unroll
                                 for (int t = 0; t < 21; ++t) sum += src[t * 3 * kRedLd];
                             }
-                            d.scat[28 * (size_t)cpr + 14 * h + k] = sum;
+                            if (sg.len > 1) {                 // (grouped tile: the records wait for the group's sum, sgroup_finish)
+                                if (h == 0) { sg.ds0 = sum; sg.dofs = 28 * cpr + k; } else sg.ds1 = sum;
+                            } else d.scat[28 * (size_t)cpr + 14 * h + k] = sum;
                         }
                     } else
                     for (int q0 = 0; q0 < 14 * L; q0 += kWave) {                 // uniform trip count: the shuffle below reads lanes
@@ -478,7 +537,9 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
                             const double* src = red + r * kRedLd + k;
                             double sum = 0.0;
                             for (int t = 0; t < T; ++t) sum += src[t * L * kRedLd];
-                            d.scat[28 * (size_t)cpr + 14 * h + k] = sum;
+                            if (sg.len > 1) {                 // (grouped tiles have L <= 4: one round, q = lane)
+                                if (h == 0) { sg.ds0 = sum; sg.dofs = 28 * cpr + k; } else sg.ds1 = sum;
+                            } else d.scat[28 * (size_t)cpr + 14 * h + k] = sum;
                         }
                     }
                     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -559,14 +620,14 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
             unsigned short* sched = reinterpret_cast<unsigned short*>(dtab + kGramTabLd * kGramTabLd);
             if (NIK <= 2 && g4_n > 0 && passes == 1) {
                 gram4_sched_store(sched, g4_se, lane, g4_n);
-                gram_tile4<6>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, dense, sched, g4_n);
+                gram_tile4<6>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, dense, sched, g4_n, sg, d.scat);
             }
             else if (NIK == 0) {
-                if (R > 32) gram_tile<3>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense);
-                else if (R > 16) gram_tile<2>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense);
-                else gram_tile<1>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense);
+                if (R > 32) gram_tile<3>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense, sg, d.scat);
+                else if (R > 16) gram_tile<2>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense, sg, d.scat);
+                else gram_tile<1>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense, sg, d.scat);
             }
-            else gram_tile<(NIK > 0 ? NIK : 1)>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense);
+            else gram_tile<(NIK > 0 ? NIK : 1)>(Vst, R, Cp, C, dtab, scat2, lane, V, s.valid, t, cidx, T, Th, passes, dense, sg, d.scat);
             XBA_STAMP(0, 8);
             return;
         }
@@ -629,7 +690,7 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
             load_FE_rc(d, sa, d.slot_cam[sa], pt, Fa, Ea, r0, r1);
             pairs_V<PREP>(Fa, Ea, hc, Va);
             pairs_diag<PREP>(Fa, Va, hc, d.gp + 3 * (size_t)pt, o28);
-            double* out = d.scat + 28 * (size_t)d.slot_campos_g[sa];
+            double* out = d.scat + 28 * (size_t)d.slot_campos_s[sa];
             for (int k = 0; k < 28; ++k) out[k] = o28[k];
         }
         if (pair_v) {

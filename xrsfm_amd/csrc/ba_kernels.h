@@ -65,6 +65,9 @@ struct Dev {
     const unsigned char* slot_gpos;   // [n_slots] position of the slot's lane in the camera-sorted order of its tile (63 = no observation)
     const int* tile_run;      // [n_tiles][kTileRunLd] per distinct camera: run start | length << 8 | first lane << 16
     const int* cam_ptr_g;     // [n_cams+1]
+    // (round 8) the S assembly's own camera-major numbering: slot_campos_g / cam_ptr_g without the entries of the tiles whose records
+    // are pre-reduced into the first tile of their group (k_sgroup_table below; the same arrays as the _g ones when nothing is grouped)
+    const int* slot_campos_s; const int* cam_ptr_s;
     // cameras
     CamRec* cam; CamRec* cam_cand; const int* cam_model; const unsigned char* cam_const; const int* cam_ptr;
     double* cam_act;    // [Nc] 1.0 if any rank observes the camera (cameras without observations are not in the program)
@@ -224,6 +227,80 @@ __global__ __launch_bounds__(256) void k_gram_runs(const int* __restrict__ slot_
     }
     slot_gpos[s] = (unsigned char)mypos;
     if (lane < kTileRunLd) tile_run[(size_t)t * kTileRunLd + lane] = mypk;
+}
+
+// ---- (round 8) tile groups of the S assembly: pre-reduction of same-tuple records on chip
+// The packer sorts tracks by camera tuple and starts a tuple that fills a tile on a tile boundary, so a banded map is runs of regular tiles
+// with one tuple each (config L: ~31 tiles per run).  Their diagonal-block / rhs records and Gram cells have the same destinations, cell for
+// cell; k_schur_pairs runs G consecutive tiles of its merged Gram launch as one workgroup (wave w: launch position G b + w) and adds the
+// records of the waves of one run in LDS, in wave order, before ONE write to the first tile's destinations (ba_chol.h: sgroup_finish).
+// A run is a maximal set of consecutive launch positions inside one window of G whose tiles are regular with L = C = 2..4 cameras (one
+// staging pass, the same accumulator layout whatever T: ba_pack.h gram_lds_need) and list the same cameras in the same cidx order.  Every
+// other tile is a group of one and writes as before.  Host (debug entry) and device evaluate the same functions.
+constexpr int kSGroupMax = 4;
+__host__ __device__ inline bool sgroup_same(const int* tile_stride, const int* tile_ncam, const int* slot_cam, const unsigned char* slot_cidx,
+                                            int a, int b) {
+    const int L = tile_stride[a];
+    if (L < 2 || L > 4 || tile_ncam[a] != L || tile_stride[b] != L || tile_ncam[b] != L) return false;
+    for (int r = 0; r < L; ++r)
+        if (slot_cam[64 * a + r] != slot_cam[64 * b + r] || slot_cidx[64 * a + r] != slot_cidx[64 * b + r]) return false;
+    return true;
+}
+// code of launch position p (the merged launch runs its list backwards: tile list[n - 1 - p]): index in its run | run length << 4
+__host__ __device__ inline int sgroup_code(const int* list, int n, int G, int p, const int* tile_stride, const int* tile_ncam,
+                                           const int* slot_cam, const unsigned char* slot_cidx) {
+    const int w0 = p - p % G, w1 = (w0 + G < n) ? w0 + G : n;
+    int s = p, e = p + 1;
+    while (s > w0 && sgroup_same(tile_stride, tile_ncam, slot_cam, slot_cidx, list[n - s], list[n - 1 - s])) --s;
+    while (e < w1 && sgroup_same(tile_stride, tile_ncam, slot_cam, slot_cidx, list[n - e], list[n - 1 - e])) ++e;
+    return (p - s) | ((e - s) << 4);
+}
+__global__ __launch_bounds__(256) void k_sgroup_table(const int* __restrict__ list, int n, int G, const int* __restrict__ tile_stride,
+                                                      const int* __restrict__ tile_ncam, const int* __restrict__ slot_cam,
+                                                      const unsigned char* __restrict__ slot_cidx, int* __restrict__ sgrp,
+                                                      unsigned char* __restrict__ tile_drop) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int code = sgroup_code(list, n, G, p, tile_stride, tile_ncam, slot_cam, slot_cidx);
+    sgrp[p] = code;
+    tile_drop[list[n - 1 - p]] = (code & 15) > 0 ? 1 : 0;
+}
+// keep flags of the entries: a camera entry's writer is a slot, a block entry's an observation pair (always kept) or a Gram cell
+__global__ __launch_bounds__(256) void k_sgroup_cam_flags(const int* __restrict__ slot_campos_g, const unsigned char* __restrict__ tile_drop,
+                                                          int n_slots, int* __restrict__ flag) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_slots) return;
+    const int e = slot_campos_g[s];
+    if (e >= 0) flag[e] = tile_drop[s >> 6] ? 0 : 1;
+}
+__global__ __launch_bounds__(256) void k_sgroup_pair_flags(const int* __restrict__ pair_dst, int n_obs_pairs, int* __restrict__ flag) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= n_obs_pairs) return;
+    const int e = pair_dst[w];
+    if (e >= 0) flag[e] = 1;
+}
+__global__ __launch_bounds__(256) void k_sgroup_cell_flags(const int* __restrict__ cells, const int* __restrict__ tile_ncam,
+                                                           const int* __restrict__ tile_gt_off, const unsigned char* __restrict__ tile_drop,
+                                                           int n_tiles, int* __restrict__ flag) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_tiles) return;
+    const int C = tile_ncam[t];
+    if (C <= 0) return;
+    const int* cell = cells + tile_gt_off[t];
+    const int keep = tile_drop[t] ? 0 : 1;
+    for (int q = 0; q < C * C; ++q) { const int e = cell[q]; if (e >= 0) flag[e] = keep; }
+}
+// renumbering by the exclusive scan pos of the flags: writer -> kept entry (or -1), list pointers -> compact list pointers
+__global__ __launch_bounds__(256) void k_sgroup_remap(const int* __restrict__ src, int n, const int* __restrict__ flag, const int* __restrict__ pos,
+                                                      int* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int e = src[i];
+    dst[i] = (e >= 0 && flag[e]) ? pos[e] : -1;
+}
+__global__ __launch_bounds__(256) void k_sgroup_remap_ptr(const int* __restrict__ src, int n, const int* __restrict__ pos, int* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = pos[src[i]];
 }
 
 struct SlotCtx {

@@ -110,6 +110,7 @@ struct CholHost {
     int* pairs_items = nullptr; int n_pairs_small = 0, n_pairs_big = 0, n_pairs_other = 0;
     int gram_n[8] = {0}; size_t gram_shm[8] = {0};   // Gram tiles / dynamic LDS per launch bucket (ba_plan.h)
     bool gram_merge = true;         // the buckets of operand heights 1..3 as ONE launch (XRSFM_BA_GRAM_MERGE=0: one launch per bucket)
+    int sgroup = 1; int* sgrp = nullptr;   // (round 8) tiles per workgroup of the merged Gram launch and its group table (k_sgroup_table)
     hipStream_t aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;     // the non-Gram items run concurrently
     // right-looking schedule (dense patterns): one panel after the other
     int* cols_flat = nullptr;                     // device list: per tile column its row tiles j < k (push-form backward substitution)
@@ -759,8 +760,13 @@ void set_kernel_attributes(int device) {
 #define XBA_PAIRS_ATTR(NI) \
     (void)hipFuncSetAttribute((const void*)k_schur_pairs<true, true, NI>, hipFuncAttributeMaxDynamicSharedMemorySize, pairs_max); \
     (void)hipFuncSetAttribute((const void*)k_schur_pairs<true, false, NI>, hipFuncAttributeMaxDynamicSharedMemorySize, pairs_max);
-    XBA_PAIRS_ATTR(0) XBA_PAIRS_ATTR(1) XBA_PAIRS_ATTR(2) XBA_PAIRS_ATTR(3) XBA_PAIRS_ATTR(4)
+    XBA_PAIRS_ATTR(1) XBA_PAIRS_ATTR(2) XBA_PAIRS_ATTR(3) XBA_PAIRS_ATTR(4)
 #undef XBA_PAIRS_ATTR
+    {   // the merged Gram launch: up to kSGroupMax tiles of the small LDS class per workgroup (round 8: sgroup_setup)
+        const int merged_max = std::max(pairs_max, kSGroupMax * (kGramSmallLds + 16));
+        (void)hipFuncSetAttribute((const void*)k_schur_pairs<true, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, merged_max);
+        (void)hipFuncSetAttribute((const void*)k_schur_pairs<true, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, merged_max);
+    }
     (void)hipFuncSetAttribute((const void*)k_schur_pairs<false, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, pairs_max);
     (void)hipFuncSetAttribute((const void*)k_schur_pairs<false, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, pairs_max);
     (void)hipFuncSetAttribute((const void*)k9_pairs_gram<1>, hipFuncAttributeMaxDynamicSharedMemorySize, pairs_max);
@@ -771,6 +777,74 @@ void set_kernel_attributes(int device) {
 }
 
 // ---------------------------------------------------------------- Cholesky path: structures
+// (round 8) Tile groups of the merged Gram launch (ba_kernels.h: k_sgroup_table) and the S assembly's compact entry lists: the camera
+// entries (slot_campos_s / cam_ptr_s) and the block entries (pair_dst / blk_ptr, renumbered in place) lose the entries of the tiles whose
+// records the first tile of their group writes.  Kept entries keep their order.  XRSFM_BA_SGROUP=0 (or 1): one entry per tile, as before;
+// =2..4: tiles per workgroup, always.  Unset: G = 4 when the groups drop at least a quarter of the camera entries.  n_writes: in the
+// block entry count, out the compact count.
+int sgroup_setup(xrsfm_ba_context* c, int& n_writes) {
+    CholHost& h = c->chol;
+    Dev& d = c->d;
+    const Packed& k = c->pk;
+    d.slot_campos_s = d.slot_campos_g; d.cam_ptr_s = d.cam_ptr_g;
+    h.sgroup = 1; h.sgrp = nullptr;
+    int G = 4;
+    const char* ge = std::getenv("XRSFM_BA_SGROUP");        // (read per set-up: the A/B test switches it)
+    if (ge) G = std::atoi(ge);
+    G = std::min(G, kSGroupMax);
+    int n_merged = 0; size_t shm_merged = 0;
+    for (int b = 0; b < 6; ++b) { n_merged += h.gram_n[b]; if (h.gram_n[b] > 0) shm_merged = std::max(shm_merged, h.gram_shm[b]); }
+    if (G < 2 || c->wide || !h.gram_merge || n_merged < 2 || shm_merged > (size_t)kGramSmallLds) return 0;
+    h.sgroup = G;
+    int e = 0;
+    const int nt = k.n_tiles, ns = k.n_slots, Nc = k.n_cams;
+    const int n_ent = std::max(0, n_writes), n_cent = k.n_cam_entries_g;
+    const int n_cells = k.n_gt_cells, n_obs_pairs = h.n_pairs - n_cells;
+    unsigned char* drop = nullptr;
+    int *flag = nullptr, *pos = nullptr, *cflag = nullptr, *cpos = nullptr, *campos_s = nullptr, *camptr_s = nullptr, *blk_tmp = nullptr;
+    if ((e = dev_alloc(c, &h.sgrp, (size_t)n_merged)) || (e = dev_alloc(c, &drop, (size_t)std::max(1, nt))) ||
+        (e = dev_alloc(c, &flag, (size_t)n_ent + 1)) || (e = dev_alloc(c, &pos, (size_t)n_ent + 1)) ||
+        (e = dev_alloc(c, &cflag, (size_t)n_cent + 1)) || (e = dev_alloc(c, &cpos, (size_t)n_cent + 1)) ||
+        (e = dev_alloc(c, &campos_s, (size_t)std::max(1, ns))) || (e = dev_alloc(c, &camptr_s, (size_t)Nc + 1)) ||
+        (e = dev_alloc(c, &blk_tmp, (size_t)h.n_blocks + 1))) return e;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemsetAsync(drop, 0, (size_t)std::max(1, nt), st));
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int) * ((size_t)n_ent + 1), st));
+    HIPCHK(hipMemsetAsync(cflag, 0, sizeof(int) * ((size_t)n_cent + 1), st));
+    hipLaunchKernelGGL(k_sgroup_table, dim3(cdiv(n_merged, 256)), dim3(256), 0, st, (const int*)h.pairs_items, n_merged, G, d.tile_stride, d.tile_ncam,
+                       d.slot_cam, d.slot_cidx, h.sgrp, drop);
+    if (ns > 0) hipLaunchKernelGGL(k_sgroup_cam_flags, dim3(cdiv(ns, 256)), dim3(256), 0, st, d.slot_campos_g, (const unsigned char*)drop, ns, cflag);
+    if (n_obs_pairs > 0) hipLaunchKernelGGL(k_sgroup_pair_flags, dim3(cdiv(n_obs_pairs, 256)), dim3(256), 0, st, (const int*)h.pair_dst, n_obs_pairs, flag);
+    if (nt > 0) hipLaunchKernelGGL(k_sgroup_cell_flags, dim3(cdiv(nt, 256)), dim3(256), 0, st, (const int*)(h.pair_dst + n_obs_pairs), d.tile_ncam, d.tile_gt_off,
+                                   (const unsigned char*)drop, nt, flag);
+    HIPCHK(hipGetLastError());
+    auto scan = [&](int* in, int* out, size_t n) -> int {
+        size_t q = 0;
+        if (rocprim::exclusive_scan(nullptr, q, in, out, 0, n, rocprim::plus<int>(), st) != hipSuccess) return XRSFM_BA_ENODEV;
+        unsigned char* tmp = nullptr;
+        if (int e2 = dev_alloc(c, &tmp, std::max<size_t>(q, 1))) return e2;
+        return rocprim::exclusive_scan(tmp, q, in, out, 0, n, rocprim::plus<int>(), st) == hipSuccess ? 0 : XRSFM_BA_ENODEV;
+    };
+    if ((e = scan(flag, pos, (size_t)n_ent + 1)) || (e = scan(cflag, cpos, (size_t)n_cent + 1))) return e;
+    int n_cent_s = n_cent;
+    HIPCHK(hipMemcpyAsync(&n_cent_s, cpos + n_cent, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // By default only where it pays: a map where few tiles share a workgroup with a tile of their tuple (ragged, config R: 1.7 % slower
+    // per solve with G = 4 — a workgroup holds the LDS of all its waves until the last one ends) keeps one wave per workgroup.
+    // XRSFM_BA_SGROUP set: grouped whatever the share.
+    if (!ge && 4LL * (n_cent - n_cent_s) < (long long)n_cent) { h.sgroup = 1; h.sgrp = nullptr; return 0; }
+    if (ns > 0) hipLaunchKernelGGL(k_sgroup_remap, dim3(cdiv(ns, 256)), dim3(256), 0, st, d.slot_campos_g, ns, (const int*)cflag, (const int*)cpos, campos_s);
+    hipLaunchKernelGGL(k_sgroup_remap_ptr, dim3(cdiv(Nc + 1, 256)), dim3(256), 0, st, d.cam_ptr_g, Nc + 1, (const int*)cpos, camptr_s);
+    if (h.n_pairs > 0) hipLaunchKernelGGL(k_sgroup_remap, dim3(cdiv(h.n_pairs, 256)), dim3(256), 0, st, (const int*)h.pair_dst, h.n_pairs, (const int*)flag, (const int*)pos, h.pair_dst);
+    hipLaunchKernelGGL(k_sgroup_remap_ptr, dim3(cdiv(h.n_blocks + 1, 256)), dim3(256), 0, st, (const int*)h.blk_ptr, h.n_blocks + 1, (const int*)pos, blk_tmp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h.blk_ptr, blk_tmp, sizeof(int) * ((size_t)h.n_blocks + 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(&n_writes, pos + n_ent, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    d.slot_campos_s = campos_s; d.cam_ptr_s = camptr_s;
+    return 0;
+}
+
 int chol_setup(xrsfm_ba_context* c) {
     CholHost& h = c->chol;
     if (h.ready) return 0;
@@ -871,6 +945,8 @@ int chol_setup(xrsfm_ba_context* c) {
     up.add(&d_cam_off, P.cam_off); up.add(&d_tile_rows, P.tile_rows); up.add(&d_tmap, P.tile_map);
     TRYC(up.flush());
     timer.mark("uploads");
+    int n_writes = P.n_writes;
+    TRYC(sgroup_setup(c, n_writes));
     const size_t blk_vals = c->wide ? kWB : 36, cam_vals = c->wide ? kWS : 28;
     {   // diagonal-block buffer and off-diagonal block values in one allocation: one all-reduce per LM step
         double* both = nullptr;
@@ -887,13 +963,13 @@ int chol_setup(xrsfm_ba_context* c) {
         const char* g4 = std::getenv("XRSFM_BA_GRAM4");          // (read per set-up: the A/B test switches it)
         h.gram4 = !(g4 && g4[0] == '0');
         const char* pe = std::getenv("XRSFM_BA_PAIR_V");        // (read per set-up: the A/B test switches it)
-        h.pair_from_v = !c->wide && h.n_pairs_other > 0 && (pe ? pe[0] != '0' : (P.n_pair_writes >= 262144 && 2LL * P.n_pair_writes >= P.n_writes));
+        h.pair_from_v = !c->wide && h.n_pairs_other > 0 && (pe ? pe[0] != '0' : (P.n_pair_writes >= 262144 && 2LL * P.n_pair_writes >= n_writes));
         // the scatter buffer of the block entries: one 36-value record per entry — with stored operands only the Gram tiles' cells are
         // ever written, so it holds those alone, numbered compactly (config T: 0.6 MB instead of 17.8 GB)
-        const size_t n_scat2 = h.pair_from_v ? (size_t)std::max(0, P.n_writes - P.n_pair_writes) : (size_t)std::max(0, P.n_writes);
+        const size_t n_scat2 = h.pair_from_v ? (size_t)std::max(0, n_writes - P.n_pair_writes) : (size_t)std::max(0, n_writes);
         TRYC(dev_alloc(c, &h.scat2, std::max<size_t>(1, n_scat2) * blk_vals));
         if (h.pair_from_v) {
-            const size_t ne = (size_t)std::max(1, P.n_writes);
+            const size_t ne = (size_t)std::max(1, n_writes);
             TRYC(dev_alloc(c, &h.ent_src, ne));
             TRYC(dev_alloc(c, &h.pair_v, (size_t)std::max(1, k.n_slots) * 18));
             HIPCHK(hipMemsetAsync(h.ent_src, 0xff, sizeof(int2) * ne, c->stream));
@@ -1026,8 +1102,15 @@ int chol_assemble(xrsfm_ba_context* c, bool materialize = false) {
         };
         auto launch_gram = [&](auto ni, int n, size_t shm, const int* items, hipStream_t st) {
             constexpr int NI = decltype(ni)::value;
-            if (c->step_prep) hipLaunchKernelGGL((k_schur_pairs<true, true, NI>), dim3(n), dim3(kWave), shm, st, d, items, h.slot_pair_ptr, h.pair_dst, n_obs_pairs, h.scat2, radius, (double*)nullptr, h.gram4);
-            else hipLaunchKernelGGL((k_schur_pairs<true, false, NI>), dim3(n), dim3(kWave), shm, st, d, items, h.slot_pair_ptr, h.pair_dst, n_obs_pairs, h.scat2, radius, (double*)nullptr, h.gram4);
+            // (round 8) the merged launch: G tiles per workgroup, each wave in an LDS region of its own (16-byte aligned)
+            const int G = NI == 0 ? h.sgroup : 1;
+            const size_t wbytes = (shm + 15) & ~(size_t)15;
+            const dim3 grid(cdiv(n, G)), block(kWave * G);
+            const size_t shm_wg = G > 1 ? wbytes * G : shm;
+            const int wld = G > 1 ? (int)(wbytes / sizeof(double)) : 0;
+            const int* sg = G > 1 ? (const int*)h.sgrp : nullptr;
+            if (c->step_prep) hipLaunchKernelGGL((k_schur_pairs<true, true, NI>), grid, block, shm_wg, st, d, items, h.slot_pair_ptr, h.pair_dst, n_obs_pairs, h.scat2, radius, (double*)nullptr, h.gram4, sg, n, wld);
+            else hipLaunchKernelGGL((k_schur_pairs<true, false, NI>), grid, block, shm_wg, st, d, items, h.slot_pair_ptr, h.pair_dst, n_obs_pairs, h.scat2, radius, (double*)nullptr, h.gram4, sg, n, wld);
         };
         // Gram tiles (round 6): ONE launch for the operand heights 1..3 — every tile fits the small LDS class in enough staging
         // passes (ba_pack.h: gram_lds_need), the height is read from the tile's camera count — on the main stream; only tiles of
@@ -1076,9 +1159,9 @@ int chol_assemble(xrsfm_ba_context* c, bool materialize = false) {
         }
     }
     if (d.n_cams + h.n_blocks > 0) {
-        if (h.pair_from_v) LAUNCH(c, K_BLOCK_SEGSUM, k_chol_segsum_v, dim3(d.n_cams + (h.n_blocks + 3) / 4), dim3(kBlock), 0, d.scat, d.cam_ptr_g, d.camS, d.n_cams, h.scat2, h.blk_ptr, h.Sblk,
+        if (h.pair_from_v) LAUNCH(c, K_BLOCK_SEGSUM, k_chol_segsum_v, dim3(d.n_cams + (h.n_blocks + 3) / 4), dim3(kBlock), 0, d.scat, d.cam_ptr_s, d.camS, d.n_cams, h.scat2, h.blk_ptr, h.Sblk,
                                   h.n_blocks, (const int2*)h.ent_src, (const double*)h.pair_v);
-        else LAUNCH(c, K_BLOCK_SEGSUM, k_chol_segsum, dim3(d.n_cams + h.n_blocks), dim3(kBlock), 0, d.scat, d.cam_ptr_g, d.camS, d.n_cams, h.scat2, h.blk_ptr, h.Sblk);
+        else LAUNCH(c, K_BLOCK_SEGSUM, k_chol_segsum, dim3(d.n_cams + h.n_blocks), dim3(kBlock), 0, d.scat, d.cam_ptr_s, d.camS, d.n_cams, h.scat2, h.blk_ptr, h.Sblk);
     }
     int e = allreduce(c, d.camS, (size_t)d.n_cams * 28 + (size_t)h.n_blocks * 36, kNcclSum);   // camS | Sblk are contiguous
     if (e) return e;
@@ -2657,6 +2740,48 @@ int xrsfm_ba_debug_gram_schedule(int n_cams, int32_t* n_inst, int32_t* n_inst_al
     *n_inst_all = S.n[n_cams];
     *n_inst = S.n[n_cams] <= kGram4MaxInst ? S.n[n_cams] : 0;
     for (int i = 0; i < 4 * S.n[n_cams] && i < 128; ++i) entries[i] = S.e[n_cams][i];
+    return 0;
+}
+
+// (round 8) the S assembly's tile groups on the host-packed tables (ba_kernels.h: sgroup_code, the functions the device table is built
+// with): per position of the merged Gram launch its tile and code (index in run | length << 4); per tile L and the first L slots' cameras
+// and cidx; stats = {positions, camera entries, camera entries kept}.  cam_ptr_s: the compact per-camera pointers [n_cams + 1].
+int xrsfm_ba_debug_sgroup(const xrsfm_ba_problem* p, int G, int32_t stats[3], int32_t* pos_tile, int32_t* pos_code, int32_t* tile_stride,
+                          int32_t* tile_cams, int32_t* tile_cidx, int32_t* cam_ptr_s) {
+    if (!p || !stats || G < 1 || G > kSGroupMax) return XRSFM_BA_EINVAL;
+    Packed k;
+    int e = pack_problem(*p, k, false);
+    if (e) return e;
+    std::vector<int> spp;
+    PairKeys keyed;
+    if ((e = chol_local_keys(k, spp, keyed))) return e == kErrDuplicateObs ? XRSFM_BA_EINVAL : e;
+    CholPlan P;
+    if ((e = chol_plan_build(k, spp, keyed, nullptr, P, kCholMaxN, kCholMaxBytes))) return e;
+    int n = 0;
+    for (int b = 0; b < 6; ++b) n += P.gram_n[b];
+    std::vector<unsigned char> drop(k.n_tiles, 0);
+    for (int q = 0; q < n; ++q) {
+        const int code = sgroup_code(P.pairs_items.data(), n, G, q, k.tile_stride.data(), k.tile_ncam.data(), k.slot_cam.data(), k.slot_cidx.data());
+        const int t = P.pairs_items[n - 1 - q];
+        drop[t] = (code & 15) > 0;
+        if (pos_tile) pos_tile[q] = t;
+        if (pos_code) pos_code[q] = code;
+    }
+    for (int t = 0; t < k.n_tiles; ++t) {
+        if (tile_stride) tile_stride[t] = k.tile_stride[t];
+        for (int r = 0; r < 4; ++r) {
+            const bool in = r < k.tile_stride[t];
+            if (tile_cams) tile_cams[4 * t + r] = in ? k.slot_cam[64 * t + r] : -1;
+            if (tile_cidx) tile_cidx[4 * t + r] = in ? (int)k.slot_cidx[64 * t + r] : -1;
+        }
+    }
+    std::vector<int> kept(k.n_cam_entries_g + 1, 0);
+    for (long long s2 = 0; s2 < k.n_slots; ++s2)
+        if (k.slot_campos_g[s2] >= 0) kept[k.slot_campos_g[s2]] = drop[s2 >> 6] ? 0 : 1;
+    std::vector<int> pos(kept.size(), 0);
+    for (size_t i = 1; i < kept.size(); ++i) pos[i] = pos[i - 1] + kept[i - 1];
+    stats[0] = n; stats[1] = k.n_cam_entries_g; stats[2] = pos.back();
+    if (cam_ptr_s) for (int c = 0; c <= k.n_cams; ++c) cam_ptr_s[c] = pos[k.cam_ptr_g[c]];
     return 0;
 }
 
