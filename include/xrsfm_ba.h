@@ -367,8 +367,9 @@ int xrsfm_ba_debug_gram_schedule(int n_cams, int32_t *n_inst, int32_t *n_inst_al
  * deep elimination trees: dense / unordered patterns), bit 1 (value 2) = look-ahead panel schedule (one launch per tile
  * column, k_panel_slot) — test the bits, not the value: a look-ahead plan reports 2, [7] structurally
  * non-zero tiles after fill.  cam_offset (may be NULL):
- * [n_cams] first row of each camera in the elimination order. */
-int xrsfm_ba_debug_chol_plan(const xrsfm_ba_problem *problem, int32_t stats[8], int32_t *cam_offset);
+ * [n_cams] first row of each camera in the elimination order.  facts (may be NULL): [16] the schedule facts of
+ * xrsfm_ba_debug_reduced_system, as far as the plan and the environment decide them. */
+int xrsfm_ba_debug_chol_plan(const xrsfm_ba_problem *problem, int32_t stats[8], int32_t *cam_offset, int32_t *facts);
 
 /* TEST ENTRY: device-side packing (large problems: xrsfm_ba_create sorts and lays out the observations on the GPU) against the host
  * packing it replaces: packs `problem` both ways and compares every array.  Returns 0 with *field = 0 when they are identical,
@@ -382,6 +383,22 @@ int xrsfm_ba_debug_set_block_pattern(xrsfm_ba_context *ctx, int n_pairs, const i
 /* After debug_linearize: solve S(radius) y = b with the Cholesky path; y [n_cams][6].  If S_dense != NULL it
  * receives the assembled reduced camera matrix before factorisation, [6 n_cams][6 n_cams] row-major, symmetric. */
 int xrsfm_ba_debug_cholesky_solve(xrsfm_ba_context *ctx, double radius, double *y, double *S_dense);
+
+/* TEST ENTRY.  After debug_linearize (bal9 contexts: after debug_wide): the damped reduced system S(radius) y = b exactly as the
+ * tile factorisation reads it, and optionally its solution by the same factorisation.  Runs the set-up, the step preparation and the
+ * assembly with a materialised tile storage (k_tile_fill), like debug_cholesky_solve with S_dense.  Outputs in camera order with
+ * cw = 6 (9 in bal9 mode) unknowns per camera: diag [n_cams][cw][cw] the diagonal blocks; blk_rc [n_blocks][2] the structurally
+ * non-zero off-diagonal blocks (row camera > column camera) and blk [n_blocks][cw][cw] their values, block (row, column) of S;
+ * b [n_cams][cw]; y [n_cams][cw] (may be NULL: no factorisation).  *n_blocks: capacity in, block count out; with blk_rc, blk, diag
+ * or b NULL only the set-up runs and the count and facts are returned.  Leaves no solved step behind (debug_backsub refuses).
+ * facts [16]: [0] tile columns T, [1] levels, [2] ordering (as debug_chol_plan), [3] schedule (0 level, 1 panel, 2 look-ahead
+ * panel), [4] levels with a macro-panel launch (k_panel2_part), [5] split levels (partials + fixed-order sum), [6] level
+ * look-ahead depth, [7] tiles composed outside the first level's columns, [8] 1 = those get a launch of their own (k_tile_fill:
+ * more than 4096 of them on a level schedule), [9] 1 = packed tile storage, [10] backward substitution (0 only inside the
+ * last factor launch, 1 one launch per level, 2 one launch for all levels, 3 per level in chunks, 4 push form), [11] bit m set =
+ * a tile column holds m cameras, [12] cw, [13] off-diagonal blocks, [14] unknowns, [15] structurally non-zero tiles. */
+int xrsfm_ba_debug_reduced_system(xrsfm_ba_context *ctx, double radius, int32_t facts[16], int32_t *n_blocks, int32_t *blk_rc,
+                                  double *blk, double *diag, double *b, double *y);
 
 /* bal9 contexts: linearise at the current state with Jacobi scaling (cost; per observation r [n_obs][2], Jc [n_obs][2][9],
  * Jp [n_obs][2][3]; per camera diag(Hcc), g_c [n_cams][9]) and, if y != NULL, solve the reduced system at `radius`

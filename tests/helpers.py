@@ -250,3 +250,86 @@ def make_bal9(n_cams=12, n_pts=600, k_obs=4, seed=5, **kw):
     model 5 {f, k1, k2} (no principal point) and keeps them VARIABLE (cam_const bit 2): 9-wide camera blocks.  Same geometry and
     observations as make() (the KITTI principal point is subtracted from the observations), intrinsics start 1 % / 0.01 off."""
     return synth.to_bal9(make(n_cams, n_pts, k_obs, seed=seed, **kw), seed)
+
+
+# ------------------------------------------------------------------------------------------------ reduced-system accuracy
+def _two_product(a, b):
+    """a * b = p + e exactly (Dekker / Veltkamp splitting; float64 arrays, no overflow)."""
+    p = a * b
+    def split(x):
+        t = 134217729.0 * x          # 2^27 + 1
+        hi = t - (t - x)
+        return hi, x - hi
+    ah, al = split(a); bh, bl = split(b)
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    return p, e
+
+
+def residual_ext(S, y, b, force_compensated=False):
+    """b - S y in extended precision (S scipy.sparse or dense): long double where it carries >= 63 mantissa bits, else exact
+    products (TwoProduct) summed with math.fsum.  Returned as float64."""
+    import math
+    import scipy.sparse as sp
+    S = sp.csr_matrix(S)
+    y = np.asarray(y, np.float64).reshape(-1); b = np.asarray(b, np.float64).reshape(-1)
+    if np.finfo(np.longdouble).nmant >= 63 and not force_compensated:
+        r = b.astype(np.longdouble) - S.astype(np.longdouble) @ y.astype(np.longdouble)
+        return r.astype(np.float64)
+    p, e = _two_product(S.data, y[S.indices])
+    out = np.empty(S.shape[0])
+    for i in range(S.shape[0]):
+        sl = slice(S.indptr[i], S.indptr[i + 1])
+        out[i] = math.fsum([b[i], *(-p[sl]), *(-e[sl])])
+    return out
+
+
+def backward_error(S, y, b):
+    """Normwise backward error of y as a solution of S y = b: ||b - S y||_inf / (||S||_inf ||y||_inf + ||b||_inf), the residual
+    in extended precision."""
+    import scipy.sparse as sp
+    y = np.asarray(y, np.float64).reshape(-1); b = np.asarray(b, np.float64).reshape(-1)
+    nS = float(abs(sp.csr_matrix(S)).sum(axis=1).max())
+    r = residual_ext(S, y, b)
+    return float(np.abs(r).max() / (nS * np.abs(y).max() + np.abs(b).max()))
+
+
+def reference_solve(S, b, max_steps=12):
+    """Reference solution of S y = b: LAPACK Cholesky (dense, n <= 6000; LU where Cholesky breaks down) or SuperLU, then
+    iterative refinement with the extended-precision residual.  Returns dict(y: refined solution, y0: the plain float64 solve,
+    eta0: its backward error, err0: its forward error against y, converged: whether the refinement reached the rounding
+    level of y — the forward-error comparison is meaningful only then)."""
+    import scipy.linalg as sla
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    b = np.asarray(b, np.float64).reshape(-1)
+    n = b.shape[0]
+    if n <= 6000:
+        A = sp.csr_matrix(S).toarray()
+        try:
+            f = sla.cho_factor(A, lower=True)
+            solve = lambda r: sla.cho_solve(f, r)
+        except np.linalg.LinAlgError:
+            f = sla.lu_factor(A)
+            solve = lambda r: sla.lu_solve(f, r)
+    else:
+        # symmetric mode, no row pivoting: S is symmetric and (up to rounding) positive definite, and partial pivoting would
+        # break the fill-reducing order of the nearly singular systems of large radii
+        lu = spla.splu(sp.csc_matrix(S), permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
+        solve = lu.solve
+    y0 = solve(b)
+    y = y0.copy()
+    converged, last = False, np.inf
+    for _ in range(max_steps):
+        if not np.isfinite(y).all():
+            break
+        dy = solve(residual_ext(S, y, b))
+        step = float(np.abs(dy).max() / max(np.abs(y).max(), 1e-300))
+        y = y + dy
+        if step <= 2.0 ** -51:        # (a correction of a few units in the last place of y: y is as exact as float64 holds it)
+            converged = True
+            break
+        if step > 0.5 * last:         # no contraction: kappa * eps is not small
+            break
+        last = step
+    err0 = float(np.abs(y0 - y).max() / max(np.abs(y).max(), 1e-300))
+    return dict(y=y, y0=y0, eta0=backward_error(S, y0, b), err0=err0, converged=converged)

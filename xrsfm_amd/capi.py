@@ -90,7 +90,24 @@ EXPORTS = [
     "xrsfm_ba_debug_cholesky_solve", "xrsfm_ba_debug_set_block_pattern", "xrsfm_ba_debug_pack", "xrsfm_ba_debug_chol_plan", "xrsfm_ba_refine_pose", "xrsfm_ba_refine_pose_options", "xrsfm_ba_debug_comm_hook", "xrsfm_pg_default_options", "xrsfm_pg_solve", "xrsfm_ba_debug_pack_gram", "xrsfm_ba_debug_gram_schedule",
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
+    "xrsfm_ba_debug_reduced_system",
 ]
+
+# xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
+CHOL_FACTS = ("T", "levels", "ordering", "schedule", "macro_levels", "split_levels", "la_depth", "fill_rest", "rest_apart", "packed",
+              "bwd", "height_mask", "cw", "blocks", "n", "tiles_nz")
+SCHEDULES = ("level", "panel", "lookahead")
+BWD_FORMS = ("fused", "per_level", "all", "chunk", "push")
+
+
+def _facts(v) -> dict:
+    f = dict(zip(CHOL_FACTS, (int(x) for x in v)))
+    f["schedule"] = SCHEDULES[f["schedule"]]
+    f["bwd"] = BWD_FORMS[f["bwd"]]
+    f["rest_apart"] = bool(f["rest_apart"]); f["packed"] = bool(f["packed"])
+    # pivot-tile heights in rows: a tile column of m cameras has m * cw rows
+    f["heights"] = sorted(m * f["cw"] for m in range(1, 31) if (f["height_mask"] >> m) & 1)
+    return f
 
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
 
@@ -161,8 +178,10 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_pack_gram.restype = C.c_int
     lib.xrsfm_ba_debug_sgroup.argtypes = [C.POINTER(CProblem), C.c_int] + [_c_int32_p] * 7
     lib.xrsfm_ba_debug_sgroup.restype = C.c_int
-    lib.xrsfm_ba_debug_chol_plan.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_debug_chol_plan.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p, _c_int32_p]
     lib.xrsfm_ba_debug_chol_plan.restype = C.c_int
+    lib.xrsfm_ba_debug_reduced_system.argtypes = [vp, C.c_double, _c_int32_p, C.POINTER(C.c_int32), _c_int32_p] + [_c_double_p] * 4
+    lib.xrsfm_ba_debug_reduced_system.restype = C.c_int
     lib.xrsfm_ba_debug_pack.argtypes = [C.POINTER(CProblem), _c_int32_p, _c_int32_p]
     lib.xrsfm_ba_debug_pack.restype = C.c_int
     lib.xrsfm_ba_profile_entry.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), _c_double_p, C.POINTER(C.c_int)]
@@ -346,6 +365,35 @@ class Context:
         check(self.lib.xrsfm_ba_debug_cholesky_solve(self._h, radius, _dp(y), _dp(S)), "debug_cholesky_solve")
         return y, S
 
+    def debug_reduced_system(self, radius: float, want_y: bool = True) -> dict:
+        """After debug_linearize (bal9: debug_wide): the damped reduced system as the tile factorisation reads it — S as a symmetric
+        scipy.sparse CSR matrix in camera order (cw unknowns per camera), b [n_cams][cw] — the solution y of the same
+        factorisation (want_y) and the schedule facts (CHOL_FACTS)."""
+        import scipy.sparse as sp
+        lib = self.lib
+        facts = np.zeros(16, np.int32)
+        nb = C.c_int32(0)
+        check(lib.xrsfm_ba_debug_reduced_system(self._h, radius, facts.ctypes.data_as(_c_int32_p), C.byref(nb), None, None, None, None, None),
+              "xrsfm_ba_debug_reduced_system")
+        f = _facts(facts)
+        nc, cw, m = self.problem.n_cams, f["cw"], nb.value
+        rc = np.zeros((max(m, 1), 2), np.int32); blk = np.zeros((max(m, 1), cw, cw)); diag = np.zeros((nc, cw, cw)); b = np.zeros((nc, cw))
+        y = np.zeros((nc, cw)) if want_y else None
+        check(lib.xrsfm_ba_debug_reduced_system(self._h, radius, facts.ctypes.data_as(_c_int32_p), C.byref(nb), rc.ctypes.data_as(_c_int32_p),
+                                                _dp(blk), _dp(diag), _dp(b), _dp(y)), "xrsfm_ba_debug_reduced_system")
+        rc, blk = rc[:m], blk[:m]
+        ar = np.arange(cw)
+        def coo(rows, cols, vals):      # [k] block rows / columns, [k][cw][cw] values -> scalar COO triplets
+            shape = (len(rows), cw, cw)
+            r = np.broadcast_to(cw * rows[:, None, None] + ar[None, :, None], shape)
+            c = np.broadcast_to(cw * cols[:, None, None] + ar[None, None, :], shape)
+            return r.ravel(), c.ravel(), vals.ravel()
+        cams = np.arange(nc)
+        parts = [coo(cams, cams, diag), coo(rc[:, 0], rc[:, 1], blk), coo(rc[:, 1], rc[:, 0], blk.transpose(0, 2, 1))]
+        r, c, v = (np.concatenate(x) for x in zip(*parts))
+        S = sp.csr_matrix((v, (r, c)), shape=(nc * cw, nc * cw))
+        return dict(S=S, b=b, y=y, facts=f, blk_rc=rc)
+
     def download_intrinsics(self) -> np.ndarray:
         """bal9 mode: intr_params with the refined {f, k1, k2} of the cameras that keep their intrinsics variable."""
         out = np.array(self.problem.intr_params, copy=True)
@@ -451,13 +499,16 @@ def debug_chol_plan(problem: ProblemArrays) -> dict:
     """Host-side plan of the Cholesky path: tiles, elimination-tree levels, ordering (works without a GPU)."""
     stats = np.zeros(8, np.int32)
     off = np.zeros(max(problem.n_cams, 1), np.int32)
+    facts = np.zeros(16, np.int32)
     cs = problem.c_struct()
-    check(load().xrsfm_ba_debug_chol_plan(C.byref(cs), stats.ctypes.data_as(_c_int32_p), off.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_chol_plan")
+    check(load().xrsfm_ba_debug_chol_plan(C.byref(cs), stats.ctypes.data_as(_c_int32_p), off.ctypes.data_as(_c_int32_p),
+                                          facts.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_chol_plan")
     keys = ("tiles", "levels", "ordering", "hubs", "band", "blocks", "level_schedule", "tiles_nz")
     out = dict(zip(keys, (int(v) for v in stats)))
     out["lookahead"] = (out["level_schedule"] >> 1) & 1      # panel schedule with partial products on a second stream (ba_plan.h)
     out["level_schedule"] &= 1
     out["cam_offset"] = off[:problem.n_cams].copy()
+    out["facts"] = _facts(facts)       # the schedule facts of debug_reduced_system (packed storage and the forms from the environment)
     return out
 
 

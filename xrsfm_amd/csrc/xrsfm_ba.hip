@@ -139,6 +139,8 @@ struct CholHost {
     int *md_tgt = nullptr, *md_q = nullptr, *md_cj = nullptr, *fz_late = nullptr;        // look-ahead schedule: late partials (ba_plan.h)
     std::vector<int> md_off; int md_max = 0; double* md_work = nullptr;
     int *fz_q = nullptr, *fill_rest = nullptr; int n_fill_rest = 0;    // tile fill inside the first level's launch
+    bool rest_apart = false;                                 // ... except on the level schedule with thousands of rest tiles: k_tile_fill (chol_rest_apart)
+    int32_t facts[16] = {0};                                 // schedule facts of the plan (chol_plan_facts)
     bool S_filled = false;                                   // chol_assemble ran k_tile_fill (else the first level composes its tiles)
     std::vector<int> fz_off;
     int *tf_ptr = nullptr, *tf_ent = nullptr;                // per non-zero tile: its 6x6 blocks (k_tile_fill)
@@ -845,6 +847,62 @@ int sgroup_setup(xrsfm_ba_context* c, int& n_writes) {
     return 0;
 }
 
+// tile storage of S: dense n_pad x n_pad while that is small (<= 4 GB: one address computation less per tile; measured at L / X / D:
+// 1-3 % faster than the packed form), else packed = only the structurally non-zero tiles + one zero tile (config T: 1.4 GB
+// instead of 16 GB, X: 0.1 instead of 8; the same speed at T — the factorisation is not bound by the stride of its operands).
+// XRSFM_BA_PACKED=0 / 1 forces one form.
+static bool chol_packed_storage(const CholPlan& P) {
+    const char* packed_e = std::getenv("XRSFM_BA_PACKED");        // (read per set-up: the tests switch it)
+    if (packed_e) return packed_e[0] != '0';
+    return (size_t)P.n_pad * P.n_pad * sizeof(double) > ((size_t)4 << 30);
+}
+
+// Form of the backward substitution: one launch for all levels but the last (level schedules with at least two levels;
+// XRSFM_BA_BWD_ALL=0: one launch per level), or on a deep level schedule with XRSFM_BA_BWD_ALL=0 one launch per level with the tiles
+// of a column shared out over workgroups (k_lv_bwd_chunk), or — XRSFM_BA_BWD_CHUNK=0 as well — the push form of the panel
+// schedules, two columns per launch.
+// (round 4 kept deep trees off the one-launch form: with the 174 levels of a dissected photo collection a solve took 20 ms against
+//  4 ms of per-level chunk launches — every workgroup walked its list parent first and ran its other rounds only after the parent
+//  was solved; with the lists walked from the root side (round 5, ba_chol.h) the same launch takes 0.68 ms: config T 1086 -> 970 ms)
+struct BwdChoice { bool all, chunk, push; };
+static BwdChoice chol_bwd_choice(const CholPlan& P) {
+    const char* be = std::getenv("XRSFM_BA_BWD_ALL");        // (read per context: the A/B test switches it inside one process)
+    const char* bce = std::getenv("XRSFM_BA_BWD_CHUNK");
+    BwdChoice b{};
+    b.all = !(be && be[0] == '0') && P.use_levels && !P.panel_ll && P.n_levels >= 2;
+    const bool deep = P.use_levels && !P.panel_ll && !b.all && P.n_levels > 32;
+    b.chunk = deep && !(bce && bce[0] == '0');
+    b.push = deep && !b.chunk;
+    return b;
+}
+
+constexpr int kFillRestApart = 4096;      // tiles outside the first level's columns from which a fill launch of their own pays (config T: 40 000)
+static bool chol_rest_apart(const CholPlan& P) {
+    return !P.lookahead && (int)P.fill_rest.size() > kFillRestApart;      // (the look-ahead schedule composes every tile in its first launch)
+}
+
+// The schedule facts of a plan, what chol_factor_solve launches for it (include/xrsfm_ba.h: xrsfm_ba_debug_reduced_system)
+static void chol_plan_facts(const CholPlan& P, int32_t f[16]) {
+    const BwdChoice bw = chol_bwd_choice(P);
+    int n_macro = 0, n_split = 0;
+    for (int lv = 0; lv < P.n_levels; ++lv) {
+        if ((int)P.mp_off.size() > lv + 1 && P.mp_off[lv + 1] - P.mp_off[lv] - 1 > 0) ++n_macro;
+        if ((int)P.sp_rt_off.size() > lv + 1 && P.sp_rt_off[lv + 1] > P.sp_rt_off[lv]) ++n_split;
+    }
+    int bwd;
+    if (P.lookahead || ((P.panel_ll || bw.push) && P.T > 1)) bwd = 4;       // push form (panel_backward)
+    else if (P.panel_ll || bw.push) bwd = 0;                                 // a single tile: solved inside the factor launch
+    else if (bw.chunk) bwd = 3;
+    else if (bw.all) bwd = 2;
+    else bwd = P.n_levels >= 2 ? 1 : 0;
+    int heights = 0;
+    for (int t = 0; t < P.T && t < (int)P.tile_rows.size(); ++t) heights |= 1 << (P.tile_rows[t] / P.cam_width);
+    const int32_t v[16] = {P.T, P.n_levels, P.ordering, P.lookahead ? 2 : (P.panel_ll ? 1 : 0), n_macro, n_split, P.la_depth,
+                           (int32_t)P.fill_rest.size(), chol_rest_apart(P) ? 1 : 0, chol_packed_storage(P) ? 1 : 0, bwd, heights,
+                           P.cam_width, P.n_blocks, P.n, P.n_tiles_nz};
+    for (int i = 0; i < 16; ++i) f[i] = v[i];
+}
+
 int chol_setup(xrsfm_ba_context* c) {
     CholHost& h = c->chol;
     if (h.ready) return 0;
@@ -991,13 +1049,9 @@ int chol_setup(xrsfm_ba_context* c) {
     }
     h.dev.n = P.n; h.dev.n_pad = P.n_pad; h.dev.T = P.T; h.dev.cam_off = d_cam_off; h.dev.tile_rows = d_tile_rows;
     h.dev.cw = P.cam_width; h.dev.cpt = P.cams_per_tile;
-    // tile storage of S: dense n_pad x n_pad while that is small (<= 4 GB: one address computation less per tile; measured at L / X / D:
-    // 1-3 % faster than the packed form), else packed = only the structurally non-zero tiles + one zero tile (config T: 1.4 GB
-    // instead of 16 GB, X: 0.1 instead of 8; the same speed at T — the factorisation is not bound by the stride of its operands).
-    // XRSFM_BA_PACKED=0 / 1 forces one form.
-    const char* packed_e = std::getenv("XRSFM_BA_PACKED");        // (read per set-up: the tests switch it)
-    const int packed_env = packed_e ? (packed_e[0] == '0' ? 0 : 1) : -1;
-    const bool packed = packed_env >= 0 ? packed_env == 1 : (size_t)P.n_pad * P.n_pad * sizeof(double) > ((size_t)4 << 30);
+    const bool packed = chol_packed_storage(P);
+    h.rest_apart = chol_rest_apart(P);
+    chol_plan_facts(P, h.facts);
     h.dev.tmap = packed ? d_tmap : nullptr;
     h.dev.ld = packed ? (size_t)kNB : (size_t)P.n_pad;
     h.dev.tstride = (size_t)kNB * kNB + kNB;
@@ -1007,20 +1061,10 @@ int chol_setup(xrsfm_ba_context* c) {
     TRYC(dev_alloc(c, &h.dev.S, h.S_doubles));
     TRYC(dev_alloc(c, &h.dev.Linv, (size_t)P.T * kNB * kNB));
     TRYC(dev_alloc(c, &h.dev.y, (size_t)P.n_pad)); TRYC(dev_alloc(c, &h.dev.rhs, (size_t)P.n_pad)); TRYC(dev_alloc(c, &h.dev.x, (size_t)P.n_pad));
-    {   // one-launch backward substitution (level schedules with at least two levels; XRSFM_BA_BWD_ALL=0: one launch per level)
-        const char* be = std::getenv("XRSFM_BA_BWD_ALL");        // (read per context: the A/B test switches it inside one process)
-        const bool on = !(be && be[0] == '0');
-        // (round 4 kept deep trees off it: with the 174 levels of a dissected photo collection a solve took 20 ms against 4 ms of per-level
-        //  chunk launches — every workgroup walked its list parent first and ran its other rounds only after the parent was solved;
-        //  with the lists walked from the root side (round 5, ba_chol.h) the same launch takes 0.68 ms: config T 1086 -> 970 ms)
-        h.bwd_all = on && P.use_levels && !P.panel_ll && P.n_levels >= 2;
+    {   // backward substitution (chol_bwd_choice)
+        const BwdChoice bw = chol_bwd_choice(P);
+        h.bwd_all = bw.all; h.bwd_chunk = bw.chunk; h.bwd_push = bw.push;
         { const char* te = std::getenv("XRSFM_BA_DEBUG_BWD_TIMEOUT"); h.bw_debug_timeout = te && te[0] == '1'; }      // (read per set-up: the test switches it)
-        // XRSFM_BA_BWD_ALL=0 on a deep level schedule: one launch per level with the tiles of a column shared out over workgroups
-        // (k_lv_bwd_chunk), or — XRSFM_BA_BWD_CHUNK=0 as well — the push form of the panel schedules, two columns per launch
-        const char* bce = std::getenv("XRSFM_BA_BWD_CHUNK");
-        const bool deep = P.use_levels && !P.panel_ll && !h.bwd_all && P.n_levels > 32;
-        h.bwd_chunk = deep && !(bce && bce[0] == '0');
-        h.bwd_push = deep && !h.bwd_chunk;
         if (h.bwd_chunk) {
             std::vector<int4> chunks;
             h.bc_off.assign(P.n_levels + 1, 0);
@@ -1188,8 +1232,6 @@ static void panel_backward(xrsfm_ba_context* c) {
     }
 }
 
-constexpr int kFillRestApart = 4096;      // tiles outside the first level's columns from which a fill launch of their own pays (config T: 40 000)
-
 int chol_factor_solve(xrsfm_ba_context* c) {
     Dev& d = c->d;
     CholHost& h = c->chol;
@@ -1269,7 +1311,7 @@ int chol_factor_solve(xrsfm_ba_context* c) {
                 lf.d = d; lf.f = FillLists{h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc, c->step_prep ? c->step_radius : 0.0};
                 lf.fz_q = h.fz_q; lf.rest = h.fill_rest; lf.n_factor = nf;
                 // thousands of tiles outside the first level: composed by a launch of their own (several workgroups per CU)
-                const bool rest_apart = h.n_fill_rest > kFillRestApart;
+                const bool rest_apart = h.rest_apart;
                 if (rest_apart)
                     LAUNCH(c, K_DENSE_FILL, k_tile_fill, dim3(h.n_fill_rest), dim3(256), 0, h.dev, d, h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc,
                            c->step_prep ? c->step_radius : 0.0, (const int*)h.fill_rest);
@@ -2805,7 +2847,7 @@ int xrsfm_ba_debug_pack_gram(const xrsfm_ba_problem* p, int32_t stats[8], int32_
     return 0;
 }
 
-int xrsfm_ba_debug_chol_plan(const xrsfm_ba_problem* p, int32_t stats[8], int32_t* cam_offset) {
+int xrsfm_ba_debug_chol_plan(const xrsfm_ba_problem* p, int32_t stats[8], int32_t* cam_offset, int32_t* facts) {
     if (!p || !stats) return XRSFM_BA_EINVAL;
     Packed k;
     const bool wide = problem_is_wide(p);
@@ -2819,6 +2861,7 @@ int xrsfm_ba_debug_chol_plan(const xrsfm_ba_problem* p, int32_t stats[8], int32_
     stats[0] = P.T; stats[1] = P.n_levels; stats[2] = P.ordering; stats[3] = P.n_hubs; stats[4] = P.band; stats[5] = P.n_blocks;
     stats[6] = (P.use_levels ? 1 : 0) | (P.lookahead ? 2 : 0); stats[7] = P.n_tiles_nz;
     if (cam_offset) for (int i = 0; i < k.n_cams; ++i) cam_offset[i] = P.cam_off[i];
+    if (facts) chol_plan_facts(P, facts);
     return 0;
 }
 
@@ -2872,6 +2915,84 @@ int xrsfm_ba_debug_cholesky_solve(xrsfm_ba_context* c, double radius, double* y,
     c->step_valid = true;
     HIPCHK(hipMemcpyAsync(y, d.px, sizeof(double) * (size_t)cd.n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The damped reduced system as the factorisation reads it from the tile storage (materialised by k_tile_fill / k9_tile_fill), in
+// camera order: only the tiles that hold a diagonal or a structural off-diagonal block are downloaded (the dense form of a photo
+// collection is gigabytes).
+int xrsfm_ba_debug_reduced_system(xrsfm_ba_context* c, double radius, int32_t facts[16], int32_t* n_blocks, int32_t* blk_rc,
+                                  double* blk, double* diag, double* b, double* y) {
+    if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
+    if (!c || !facts || !n_blocks) return XRSFM_BA_EINVAL;
+    if (!c->linearized) return XRSFM_BA_ESTATE;
+    HIPCHK(hipSetDevice(c->device));
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    int e;
+    if ((e = chol_setup(c))) return e == kErrDuplicateObs ? XRSFM_BA_EINVAL : e;
+    for (int i = 0; i < 16; ++i) facts[i] = h.facts[i];
+    const int cap = *n_blocks;
+    *n_blocks = h.n_blocks;
+    if (!blk_rc || !blk || !diag || !b) return 0;         // (the sizes and facts only)
+    if (cap < h.n_blocks) return XRSFM_BA_EINVAL;
+    c->step_valid = false;
+    if (c->wide) {
+        if ((e = assemble_wide(c, radius))) return e;
+    } else {
+        if ((e = prepare_step(c, radius, true))) return e;
+        if ((e = chol_assemble(c, true))) return e;
+    }
+    const CholDev& cd = h.dev;
+    const int Nc = d.n_cams, cw = cd.cw, T = cd.T;
+    const std::vector<int>& off = h.cam_off_host;
+    std::vector<int> rc(2 * (size_t)h.n_blocks);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.n_blocks > 0) HIPCHK(hipMemcpy(rc.data(), h.blk_rc, rc.size() * sizeof(int), hipMemcpyDeviceToHost));
+    // the tiles to download: every tile that holds (part of) a camera block, compact index per tile (i, k), i >= k
+    std::vector<int> slot((size_t)T * T, -1);
+    std::vector<int> tiles;
+    auto need = [&](int r0, int c0) {
+        for (int a = 0; a < cw; a += cw - 1) for (int b2 = 0; b2 < cw; b2 += cw - 1) {     // (a block may straddle a tile edge in neither
+            int r = r0 + a, col = c0 + b2;                                                   //  direction; the corners name its tiles)
+            if (r < col) std::swap(r, col);
+            const size_t q = (size_t)(r / kNB) * T + col / kNB;
+            if (slot[q] < 0) { slot[q] = (int)tiles.size(); tiles.push_back((int)q); }
+        }
+    };
+    for (int i = 0; i < Nc; ++i) need(off[i], off[i]);
+    for (int q = 0; q < h.n_blocks; ++q) need(off[rc[2 * q]], off[rc[2 * q + 1]]);
+    std::vector<double> st((size_t)tiles.size() * kNB * kNB);
+    const std::vector<int>& tm = h.tile_map_host;
+    for (size_t q = 0; q < tiles.size(); ++q) {
+        const int ti = tiles[q] / T, tk = tiles[q] % T;
+        double* dst = st.data() + q * kNB * kNB;
+        if (cd.tmap) HIPCHK(hipMemcpy(dst, cd.S + (size_t)tm[(size_t)ti * T + tk] * cd.tstride, sizeof(double) * kNB * kNB, hipMemcpyDeviceToHost));
+        else HIPCHK(hipMemcpy2D(dst, sizeof(double) * kNB, cd.S + (size_t)ti * kNB * cd.ld + (size_t)tk * kNB, sizeof(double) * cd.ld,
+                                sizeof(double) * kNB, kNB, hipMemcpyDeviceToHost));
+    }
+    auto at = [&](int r, int col) -> double {      // element (r, col) of the symmetric S in elimination order
+        if (r < col) std::swap(r, col);
+        return st[(size_t)slot[(size_t)(r / kNB) * T + col / kNB] * kNB * kNB + (size_t)(r % kNB) * kNB + col % kNB];
+    };
+    for (int i = 0; i < Nc; ++i)
+        for (int a = 0; a < cw; ++a)
+            for (int b2 = 0; b2 < cw; ++b2) diag[((size_t)i * cw + a) * cw + b2] = at(off[i] + a, off[i] + b2);
+    for (int q = 0; q < h.n_blocks; ++q) {
+        blk_rc[2 * q] = rc[2 * q]; blk_rc[2 * q + 1] = rc[2 * q + 1];
+        for (int a = 0; a < cw; ++a)
+            for (int b2 = 0; b2 < cw; ++b2) blk[((size_t)q * cw + a) * cw + b2] = at(off[rc[2 * q]] + a, off[rc[2 * q + 1]] + b2);
+    }
+    {
+        std::vector<double> rhs((size_t)cd.n_pad);
+        HIPCHK(hipMemcpy(rhs.data(), cd.rhs, rhs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < Nc; ++i) for (int a = 0; a < cw; ++a) b[(size_t)i * cw + a] = rhs[(size_t)off[i] + a];
+    }
+    if (y) {
+        if ((e = chol_factor_solve(c))) return e;
+        HIPCHK(hipMemcpyAsync(y, c->wide ? c->w.px : d.px, sizeof(double) * (size_t)Nc * cw, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return 0;
 }
 
