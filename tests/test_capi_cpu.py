@@ -87,3 +87,108 @@ def test_streaming_kernels_do_not_spill(tmp_path):
         scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
         assert spills == 0 and scratch == 0, (name, spills, scratch)
     assert seen >= 17          # 12 instantiations of k_schur_pairs + the others
+
+
+_TR_DRIVER = r"""
+#include <cstdio>
+#include <cstring>
+#include "ba_trust_region.h"
+// one command per line on stdin, one line "code radius decrease invalid" per command on stdout
+int main() {
+    xtr::TrustRegion tr{0.0};
+    char op[16];
+    while (std::scanf("%15s", op) == 1) {
+        int code = 0;
+        double a[6] = {0, 0, 0, 0, 0, 0};
+        if (!std::strcmp(op, "new")) { if (std::scanf("%lf", a) != 1) return 1; tr = xtr::TrustRegion{a[0]}; }
+        else if (!std::strcmp(op, "invalid")) code = tr.invalid_step();
+        else if (!std::strcmp(op, "valid")) tr.invalid = 0;
+        else if (!std::strcmp(op, "rho")) { if (std::scanf("%lf", a) != 1) return 1; code = xtr::TrustRegion::successful(a[0]); }
+        else if (!std::strcmp(op, "grow")) { if (std::scanf("%lf", a) != 1) return 1; tr.grow(a[0]); }
+        else if (!std::strcmp(op, "shrink")) code = tr.shrink();
+        else if (!std::strcmp(op, "tol")) {
+            for (int i = 0; i < 6; ++i) if (std::scanf("%lf", a + i) != 1) return 1;
+            code = xtr::TrustRegion::tolerance_exit(a[0], a[1], a[2], a[3], a[4], a[5]);
+        } else return 1;
+        std::printf("%d %.17g %.17g %d\n", code, tr.radius, tr.decrease, tr.invalid);
+    }
+    return 0;
+}
+"""
+
+
+def test_trust_region_rules(tmp_path):
+    """xrsfm_amd/csrc/ba_trust_region.h (the LM trust-region rules of the BA loop, the pose refinement kernel and the tag
+    refinement) compiled with the host C++ compiler, driven through scripted step sequences; every expected value comes from
+    the oracle's options and its radius update."""
+    import subprocess
+    from xrsfm_amd import _build
+    from oracle.ba_oracle import Options
+    o = Options()
+    src = tmp_path / "tr.cc"
+    exe = tmp_path / "tr"
+    src.write_text(_TR_DRIVER)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I", _build.CSRC, str(src), "-o", str(exe)], check=True)
+
+    def run(cmds):
+        out = subprocess.run([str(exe)], input="\n".join(cmds) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
+        rows = [ln.split() for ln in out if ln]
+        assert len(rows) == len(cmds)
+        return [(int(c), float(r), float(d), int(i)) for c, r, d, i in rows]
+
+    def grown(radius, rho):
+        return min(o.max_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
+
+    # rho test: strictly above min_relative_decrease
+    rhos = [o.min_relative_decrease, o.min_relative_decrease * 0.5, o.min_relative_decrease * 1.5, -1.0, 0.5]
+    assert [r[0] for r in run([f"rho {x!r}" for x in rhos])] == [int(x > o.min_relative_decrease) for x in rhos]
+
+    # accepts grow the radius up to the cap; rejects divide by 2, 4, 8, ...; an accept resets the factor
+    r0 = o.initial_radius
+    seq = ["grow 0.9", "grow 0.2", "shrink", "shrink", "shrink", "grow 0.6", "shrink", "shrink"]
+    exp, radius, decrease = [], r0, 2.0
+    for cmd in seq:
+        if cmd == "shrink":
+            radius /= decrease
+            decrease *= 2.0
+        else:
+            radius, decrease = grown(radius, float(cmd.split()[1])), 2.0
+        exp.append((0, radius, decrease, 0))
+    assert run([f"new {r0!r}"] + seq)[1:] == exp
+    assert [e[2] for e in exp] == [2.0, 2.0, 4.0, 8.0, 16.0, 2.0, 4.0, 8.0]
+    rows = run(["new 1e15"] + ["grow 1.0"] * 4)[1:]
+    assert [r[1] for r in rows] == [3e15, 9e15, o.max_radius, o.max_radius]
+
+    # invalid steps: each shrinks like a reject; the fifth in a row ends the solve (6) and leaves the radius as it was; a valid
+    # step in between restarts the count
+    n = o.max_consecutive_invalid_steps
+    rows = run([f"new {r0!r}"] + ["invalid"] * (n - 1) + ["valid"] + ["invalid"] * n)[1:]
+    radius, decrease, exp = r0, 2.0, []
+    for k in range(n - 1):
+        radius /= decrease
+        decrease *= 2.0
+        exp.append((0, radius, decrease, k + 1))
+    exp.append((0, radius, decrease, 0))
+    for k in range(n):
+        if k < n - 1:
+            radius /= decrease
+            decrease *= 2.0
+        exp.append((6 if k == n - 1 else 0, radius, decrease, k + 1))
+    assert rows == exp
+
+    # minimum radius: 4 on the first reject that takes the radius below it, not before
+    rows = run([f"new {1e4 * o.min_radius!r}"] + ["shrink"] * 6)[1:]
+    codes = [r[0] for r in rows]
+    first = next(i for i, r in enumerate(rows) if r[1] < o.min_radius)
+    assert codes[:first] == [0] * first and codes[first] == 4 and rows[first - 1][1] >= o.min_radius
+    assert run([f"new {2.0 * o.min_radius!r}", "shrink", "shrink"])[1:] == [(0, o.min_radius, 4.0, 0), (4, o.min_radius / 4.0, 8.0, 0)]
+
+    # tolerance exits: parameter tolerance (2) before function tolerance (3); both compare with <=
+    ptol, ftol = o.parameter_tolerance, o.function_tolerance
+    cases = [((ptol * (1.0 + ptol), 1.0, 0.0, 1.0), 2),              # both hold: 2
+             ((ptol * (1.0 + ptol), 1.0, 1.0, 1.0), 2),              # step only, on the boundary
+             ((1.0, 1.0, -ftol * 2.0, 2.0), 3),                      # cost change only, on the boundary (|change|)
+             ((1.0, 1.0, ftol * 2.0 * 1.5, 2.0), 0),
+             ((ptol * (1.0 + ptol) * 1.5, 1.0, ftol, 1.0), 3)]
+    rows = run([f"tol {s!r} {x!r} {ptol!r} {ch!r} {c!r} {ftol!r}" for (s, x, ch, c), _ in cases])
+    assert [r[0] for r in rows] == [want for _, want in cases]

@@ -5,10 +5,11 @@
 // 6x6 damped solve and the trust-region bookkeeping on one lane, and the candidate is linearised in the same pass that
 // yields its cost.  Same arithmetic as the engine (ba_math.h: project, huber, quat_plus; the camera block of linearize_item)
 // and the same restated Ceres loop as xrsfm_ba_run (Jacobi scaling from the first linearisation, D^2 = clamp(diag)/radius,
-// rho > 1e-3, radius update, tolerance exits that keep the current point).  grid.x = frames (batched candidates).
+// the trust-region rules of ba_trust_region.h).  grid.x = frames (batched candidates).
 #pragma once
 
 #include "ba_kernels.h"
+#include "ba_trust_region.h"
 
 namespace xba {
 
@@ -108,9 +109,10 @@ __global__ __launch_bounds__(kBlock) void k_refine_pose(const RefineJob* __restr
     // packing's radix sorts): 20-28 ms on the first pose refinement after every KGBA of a map of 140+ frames (mapper replay,
     // tools/runs/r06_call12.sh: device idle, kernel 0.1 ms, 24 ms between the launch and the end of hipStreamSynchronize).
     __shared__ double H[21], g[6], S[6], delta[6], A[36], b[6];
-    double q[4], t[3], cost = 0.0, gmax = 0.0, radius = opt.radius0, decrease = 2.0;
+    double q[4], t[3], cost = 0.0, gmax = 0.0;
     double qc[4], tc[3], model = 0.0;
-    int it = 0, invalid = 0, n_succ = 0, n_unsucc = 0, attempted = 0, term = 0, reason = 0;
+    xtr::TrustRegion tr{opt.radius0};
+    int it = 0, n_succ = 0, n_unsucc = 0, attempted = 0, term = 0, reason = 0;
     if (threadIdx.x == 0) {
         for (int k = 0; k < 4; ++k) { q[k] = job.q[k]; sq[k] = q[k]; }
         for (int k = 0; k < 3; ++k) { t[k] = job.t[k]; st[k] = t[k]; }
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_pose(const RefineJob* __restr
                     for (int c2 = a; c2 < 6; ++c2) { const double v = H[ref_idx(a, c2)] * S[a] * S[c2]; A[a * 6 + c2] = v; A[c2 * 6 + a] = v; }
                     b[a] = -S[a] * g[a];
                 }
-                for (int a = 0; a < 6; ++a) A[a * 6 + a] += fmin(fmax(A[a * 6 + a], 1e-6), 1e32) / radius;
+                for (int a = 0; a < 6; ++a) A[a * 6 + a] += fmin(fmax(A[a * 6 + a], 1e-6), 1e32) / tr.radius;
                 bool ok = true;
                 for (int j = 0; j < 6 && ok; ++j) {          // Cholesky, lower triangle in place
                     double d = A[j * 6 + j];
@@ -174,12 +176,11 @@ __global__ __launch_bounds__(kBlock) void k_refine_pose(const RefineJob* __restr
                     model = -(gd + 0.5 * dHd);
                 }
                 if (!(model > 0.0) || !isfinite(model)) {
-                    ++invalid; ++n_unsucc;
-                    if (invalid >= 5) { term = XRSFM_BA_FAILURE; reason = 6; break; }
-                    radius /= decrease; decrease *= 2.0;
+                    ++n_unsucc;
+                    if (const int r = tr.invalid_step()) { term = XRSFM_BA_FAILURE; reason = r; break; }
                     continue;
                 }
-                invalid = 0;
+                tr.invalid = 0;
                 quat_plus(q, delta, qc);
                 for (int k = 0; k < 3; ++k) tc[k] = t[k] + delta[3 + k];
                 have_step = true;
@@ -203,25 +204,23 @@ __global__ __launch_bounds__(kBlock) void k_refine_pose(const RefineJob* __restr
             for (int k = 0; k < 3; ++k) { xn2 += t[k] * t[k]; const double d = tc[k] - t[k]; st2 += d * d; }
             const double step_norm = sqrt(st2), xnorm = sqrt(xn2);
             const double change = cost - cost_c;
-            if (step_norm <= opt.ptol * (xnorm + opt.ptol)) { term = XRSFM_BA_CONVERGENCE; reason = 2; sh_go = 0; }
-            else if (fabs(change) <= opt.ftol * cost) { term = XRSFM_BA_CONVERGENCE; reason = 3; sh_go = 0; }
+            if (const int r = xtr::TrustRegion::tolerance_exit(step_norm, xnorm, opt.ptol, change, cost, opt.ftol)) { term = XRSFM_BA_CONVERGENCE; reason = r; sh_go = 0; }
             else {
                 const double rel = change / model;
-                if (rel > 1e-3) {
+                if (xtr::TrustRegion::successful(rel)) {
                     for (int k = 0; k < 4; ++k) q[k] = qc[k];
                     for (int k = 0; k < 3; ++k) t[k] = tc[k];
                     cost = cost_c;
                     for (int k = 0; k < 21; ++k) H[k] = tot[1 + k];
                     for (int k = 0; k < 6; ++k) g[k] = tot[22 + k];
                     gmax = refine_gradmax(q, g);
-                    radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3)));
-                    decrease = 2.0;
+                    tr.grow(rel);
                     ++n_succ;
                     if (gmax <= opt.gtol) { term = XRSFM_BA_CONVERGENCE; reason = 1; sh_go = 0; }
                 } else {
-                    radius /= decrease; decrease *= 2.0;
+                    const int r = tr.shrink();
                     ++n_unsucc;
-                    if (radius < 1e-32) { term = XRSFM_BA_CONVERGENCE; reason = 4; sh_go = 0; }
+                    if (r) { term = XRSFM_BA_CONVERGENCE; reason = r; sh_go = 0; }
                 }
             }
         }

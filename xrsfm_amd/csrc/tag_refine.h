@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "../../include/xrsfm_ba.h"
+#include "ba_trust_region.h"
 #include "line_search.h"
 
 namespace xtag {
@@ -373,11 +374,11 @@ struct Solver {
         for (int i = 0; i < n; ++i) S[i] = 1.0 / (1.0 + std::sqrt(diag(i)));
         double gmax = projected_gradient_max(x, tmp);
         double xnorm = std::sqrt(diff_norm2(x, nullptr, false));
-        double radius = o.initial_radius, decrease = 2.0;
-        if (o.verbose) printf("tag refine stage %d iter %3d  cost %.6e  |g| %.3e  radius %.3e\n", stage, 0, cost, gmax, radius);
+        xtr::TrustRegion tr{o.initial_radius};
+        if (o.verbose) printf("tag refine stage %d iter %3d  cost %.6e  |g| %.3e  radius %.3e\n", stage, 0, cost, gmax, tr.radius);
         if (gmax <= o.gradient_tolerance) return finish(1, cost);
         std::vector<double> d2(n), step, Hstep(n), keep_grad;
-        int it = 0, invalid = 0;
+        int it = 0;
         bool reuse_diagonal = false;
         std::vector<double> dg(n);
         while (true) {
@@ -392,7 +393,7 @@ struct Solver {
             // scale = bound (tests compare that mode with scipy's bounded least squares).
             scale_held = o.bounds_active_set && x.scale <= p.scale_lower && grad[0] > 0.0;
             if (!reuse_diagonal) for (int i = 0; i < n; ++i) dg[i] = std::min(std::max(diag(i) * S[i] * S[i], 1e-6), 1e32);
-            for (int i = 0; i < n; ++i) d2[i] = dg[i] / radius;
+            for (int i = 0; i < n; ++i) d2[i] = dg[i] / tr.radius;
             double model = -1.0;
             if (lm_step(S, d2, step)) {
                 multiply(step.data(), Hstep.data());
@@ -402,11 +403,11 @@ struct Solver {
             }
             if (!(model > 0.0) || !std::isfinite(model)) {
                 sum->n_unsuccessful++;
-                if (++invalid >= 5) return finish(6, cost);
-                radius /= decrease; decrease *= 2.0; reuse_diagonal = true;
+                if (const int r = tr.invalid_step()) return finish(r, cost);
+                reuse_diagonal = true;
                 continue;
             }
-            invalid = 0;
+            tr.invalid = 0;
             {   // the problem is bounds-constrained: projected line search on every step
                 keep_grad = grad;
                 const double Hs0 = Hs;
@@ -419,25 +420,23 @@ struct Solver {
             double cost_c = evaluate(cand, false);
             if (!std::isfinite(cost_c)) cost_c = DBL_MAX;
             const double step_norm = std::sqrt(diff_norm2(x, &cand, false));
-            if (step_norm <= o.parameter_tolerance * (xnorm + o.parameter_tolerance)) return finish(2, cost);
             const double change = cost - cost_c;
-            if (std::fabs(change) <= o.function_tolerance * cost) return finish(3, cost);
+            if (const int r = xtr::TrustRegion::tolerance_exit(step_norm, xnorm, o.parameter_tolerance, change, cost, o.function_tolerance)) return finish(r, cost);
             const double rho = change / model;
-            if (rho > 1e-3) {
+            if (xtr::TrustRegion::successful(rho)) {
                 std::swap(x, cand);
                 cost = evaluate(x, true);
                 xnorm = std::sqrt(diff_norm2(x, nullptr, false));
                 gmax = projected_gradient_max(x, tmp);
-                radius = std::fmin(1e16, radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
-                decrease = 2.0; reuse_diagonal = false;
+                tr.grow(rho); reuse_diagonal = false;
                 sum->n_successful++;
-                if (o.verbose) printf("tag refine stage %d iter %3d  cost %.6e  |g| %.3e  radius %.3e  rho %.3e\n", stage, it, cost, gmax, radius, rho);
+                if (o.verbose) printf("tag refine stage %d iter %3d  cost %.6e  |g| %.3e  radius %.3e  rho %.3e\n", stage, it, cost, gmax, tr.radius, rho);
                 if (gmax <= o.gradient_tolerance) return finish(1, cost);
             } else {
-                radius /= decrease; decrease *= 2.0; reuse_diagonal = true;
+                const int r = tr.shrink(); reuse_diagonal = true;
                 sum->n_unsuccessful++;
-                if (o.verbose) printf("tag refine stage %d iter %3d  rejected (rho %.3e)  radius %.3e\n", stage, it, rho, radius);
-                if (radius < 1e-32) return finish(4, cost);
+                if (o.verbose) printf("tag refine stage %d iter %3d  rejected (rho %.3e)  radius %.3e\n", stage, it, rho, tr.radius);
+                if (r) return finish(r, cost);
             }
         }
     }

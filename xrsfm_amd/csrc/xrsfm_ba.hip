@@ -31,6 +31,7 @@
 #include "ba_pack.h"
 #include "ba_plan.h"
 #include "ba_refine.h"
+#include "ba_trust_region.h"
 #include "ba_wide.h"
 #include "ba_pack_dev.h"
 #include "pose_graph.h"
@@ -188,7 +189,7 @@ struct xrsfm_ba_context {
     bool pcg_coarse = true; double* pcg_w = nullptr;      // PCG path: gauge coarse space of the preconditioner (ba_kernels.h: k_pcg_gauge) and its buffers
     bool prep_fused = true;         // Cholesky path: damped point blocks factored inside k_schur_pairs / k_backsub, LM diagonal of the
                                     // cameras inside the tile fill: no k_point_prep launch (XRSFM_BA_PREP_FUSED=0: round-2 schedule)
-    double step_radius = 0.0;       // radius of the step being assembled / solved (prepare_step)
+    double step_radius = 0.0;       // radius of the step being assembled / solved (prepare_step, assemble_wide)
     bool step_prep = false;         // ... and whether its kernels form the point factors themselves
     bool step_valid = false;        // a step of the current linearisation has been assembled and solved (xrsfm_ba_debug_backsub needs it)
     bool gradmax_done = false, published = false;    // the linearisation tail did these in its own launch
@@ -574,7 +575,7 @@ int use_stored_j(xrsfm_ba_context* c, bool on, bool materialize = false) {
 
 bool jfree_for_run(const xrsfm_ba_context* c, int solver) {
     const int set = jfree_setting();
-    return solver == XRSFM_BA_SOLVER_CHOLESKY && c->chol.n_pairs_other == 0 && (set == 1 || (set < 0 && c->d.n_slots >= kJfreeMinSlots));
+    return solver == XRSFM_BA_SOLVER_CHOLESKY && !c->wide && c->chol.n_pairs_other == 0 && (set == 1 || (set < 0 && c->d.n_slots >= kJfreeMinSlots));
 }
 
 enum { LIN_SKIP_CAMLIN = 1, LIN_FINAL = 2 };    // LIN_FINAL: gradient max-norm and the hand-over to the host follow this linearisation
@@ -629,9 +630,28 @@ int linearize(xrsfm_ba_context* c, double huber_a, const Dev& d, bool with_step,
     return 0;
 }
 
-// after linearize() of the same view, which leaves the point part in S_GRADMAX_PTS (one rank) or in the per-rank slots behind camlin
+// bal9 mode (9-wide camera blocks, ba_wide.h): linearise at the context's own state, through the launch-per-phase tail.  Leaves
+// S_COST, S_XNORM2_PTS and S_GRADMAX_PTS in the scalar block (the camera part of the gradient max-norm: gradient_max_enqueue).
+// bal9 contexts never linearise at the candidate (ba_run_impl: no speculation).
+int linearize_wide(xrsfm_ba_context* c, double huber_a) {
+    if (int e = use_stored_j(c, true)) return e;        // (bal9 keeps stored J)
+    Dev& d = c->d;
+    c->gradmax_done = false; c->published = false;
+    if (d.n_items > 0) LAUNCH(c, K_LINEARIZE, k9_linearize, dim3(cdiv(d.n_items, kWavesPerBlock)), dim3(kBlock), 0, d, c->w, huber_a);
+    if (d.n_cams > 0) LAUNCH(c, K_CAM_SEGSUM, k_cam_segsum<18>, dim3(d.n_cams), dim3(kBlock), 0, c->w.scat, d.cam_ptr_g, c->w.camlin, (const PcgStatus*)nullptr);
+    ReduceJobs j{};
+    const double* ins[3] = {d.part, d.part + d.n_items, d.part + 2 * (size_t)d.n_items};
+    double* outs[3] = {d.scal + S_COST, d.scal + S_XNORM2_PTS, d.scal + S_GRADMAX_PTS};
+    for (int q = 0; q < 3; ++q) { j.in[q] = ins[q]; j.n[q] = d.n_items; j.out[q] = outs[q]; j.op[q] = q == 2 ? 1 : 0; }
+    LAUNCH(c, K_SMALL, k_reduce_multi, dim3(3), dim3(kPcgThreads), 0, j);
+    return 0;
+}
+
+// after linearize() (linearize_wide()) of the same view, which leaves the point part in S_GRADMAX_PTS (one rank) or in the per-rank
+// slots behind camlin
 int gradient_max_enqueue(xrsfm_ba_context* c, const Dev& d) {
     if (c->gradmax_done) { c->gradmax_done = false; return 0; }        // k_lin_tail of the same view has done it
+    if (c->wide) { LAUNCH(c, K_SMALL, k9_gradmax_cams, dim3(1), dim3(kPcgThreads), 0, d, c->w, d.scal + S_GRADMAX_CAMS); return 0; }
     const double* rank_max = c->multi() ? d.camlin + (size_t)d.n_cams * 12 + 4 : nullptr;
     LAUNCH(c, K_SMALL, k_gradmax_cams, dim3(1), dim3(kPcgThreads), 0, d, d.scal + S_GRADMAX_CAMS, rank_max, c->n_ranks, d.scal + S_GRADMAX_PTS);
     return 0;
@@ -1393,22 +1413,25 @@ void accept_candidate(xrsfm_ba_context* c) {
 //   speculate: linearisation AT the candidate (its cost is the candidate cost; if the step is accepted the next iteration
 //              starts from it and nothing else has to run), or
 //   otherwise: a cost-only pass over the candidate (the linearisation follows only if the step is accepted).
-// The caller speculates while steps are being accepted: a rejected step wastes the difference between the two passes.
-// One hand-off of all scalars to the host either way.
+// The caller speculates while steps are being accepted: a rejected step wastes the difference between the two passes (bal9
+// contexts never speculate).  One hand-off of all scalars to the host either way.
 int finish_step(xrsfm_ba_context* c, double huber_a, bool speculate) {
     Dev& d = c->d;
     // back-substitution over the tracks; trailing workgroups turn the camera part of the solution into the candidate cameras
     // (and, when the candidate is linearised straight away, their CamLin records) next to it
     const bool cams_done = c->fused;
-    {
+    if (c->wide) {
+        const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cdiv(d.n_cams, kBlock);
+        if (nbi + nbc > 0) LAUNCH(c, K_BACKSUB, k9_backsub, dim3(nbi + nbc), dim3(kBlock), 0, d, c->w, nbi, c->step_radius);
+    } else {
         const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cams_done ? cdiv(d.n_cams, kBlock) : 0;
         CamLin* cr = (cams_done && speculate) ? c->alt.camrec : (CamLin*)nullptr;
         if (nbi + nbc > 0) {
             if (c->step_prep) LAUNCH(c, K_BACKSUB, k_backsub<true>, dim3(nbi + nbc), dim3(kBlock), 0, d, nbi, cr, c->step_radius);
             else LAUNCH(c, K_BACKSUB, k_backsub<false>, dim3(nbi + nbc), dim3(kBlock), 0, d, nbi, cr, c->step_radius);
         }
+        if (d.n_cams > 0 && !cams_done) LAUNCH(c, K_SMALL, k_cam_update, dim3(cdiv(d.n_cams, kBlock)), dim3(kBlock), 0, d);
     }
-    if (d.n_cams > 0 && !cams_done) LAUNCH(c, K_SMALL, k_cam_update, dim3(cdiv(d.n_cams, kBlock)), dim3(kBlock), 0, d);
     if (speculate) {
         const Dev cand = candidate_view(c);
         int e = linearize(c, huber_a, cand, true, LIN_FINAL | (cams_done ? LIN_SKIP_CAMLIN : 0));
@@ -1451,18 +1474,22 @@ void print_progress(const xrsfm_ba_options& o, int it, double cost, double chang
     printf("%4d  %.6e  %9.2e  %9.2e  %9.2e  %9.2e  %9.2e\n", it, cost, change, gmax, step, rho, radius);
 }
 
+// Jacobi scaling from the unscaled column norms, then the scaled linearisation (or the unscaled one alone: use_scaling = false)
 int init_scaling_and_linearize(xrsfm_ba_context* c, double huber_a, bool use_scaling) {
     Dev& d = c->d;
+    const int cw = c->wide ? kW : 6;
     int e;
-    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_cams * 6, kBlock) + 1), dim3(kBlock), 0, d.scale_c, 1.0, (size_t)d.n_cams * 6);
+    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_cams * cw, kBlock) + 1), dim3(kBlock), 0, c->wide ? c->w.scale_c : d.scale_c, 1.0, (size_t)d.n_cams * cw);
     LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_pts * 3, kBlock) + 1), dim3(kBlock), 0, d.scale_p, 1.0, (size_t)d.n_pts * 3);
     c->gradmax_done = false; c->published = false;
-    if ((e = linearize(c, huber_a, d, false, use_scaling ? 0 : LIN_FINAL))) return e;
+    auto lin = [&](int flags) { return c->wide ? linearize_wide(c, huber_a) : linearize(c, huber_a, d, false, flags); };
+    if ((e = lin(use_scaling ? 0 : LIN_FINAL))) return e;
     if (use_scaling) {
         // point norms are local to the rank that owns the track; camera norms were all-reduced in linearize()
-        const long long n = std::max((long long)d.n_cams * 6, (long long)d.n_pts * 3);
-        LAUNCH(c, K_SMALL, k_scale_from_norms, dim3(cdiv(n, kBlock) + 1), dim3(kBlock), 0, d);
-        if ((e = linearize(c, huber_a, d, false, LIN_FINAL))) return e;
+        const long long n = std::max((long long)d.n_cams * cw, (long long)d.n_pts * 3);
+        if (c->wide) LAUNCH(c, K_SMALL, k9_scale_from_norms, dim3(cdiv(n, kBlock) + 1), dim3(kBlock), 0, d, c->w);
+        else LAUNCH(c, K_SMALL, k_scale_from_norms, dim3(cdiv(n, kBlock) + 1), dim3(kBlock), 0, d);
+        if ((e = lin(LIN_FINAL))) return e;
     }
     c->linearized = true;
     return 0;
@@ -1896,29 +1923,13 @@ int xrsfm_ba_download(xrsfm_ba_context* c, double* cam_q, double* cam_t, double*
     return ok ? 0 : XRSFM_BA_ENODEV;
 }
 
-// bal9 mode: the same trust-region loop over the 9-wide kernels of ba_wide.h.  Plain schedule — linearise, assemble,
-// factor, back-substitute, cost of the candidate, linearise again after an accepted step — through the launch-per-phase tail.
-static int linearize_wide(xrsfm_ba_context* c, double huber_a, bool scaled_pass) {
-    if (int e = use_stored_j(c, true)) return e;        // (bal9 keeps stored J)
-    Dev& d = c->d;
-    (void)scaled_pass;
-    c->gradmax_done = false; c->published = false;
-    if (d.n_items > 0) LAUNCH(c, K_LINEARIZE, k9_linearize, dim3(cdiv(d.n_items, kWavesPerBlock)), dim3(kBlock), 0, d, c->w, huber_a);
-    if (d.n_cams > 0) LAUNCH(c, K_CAM_SEGSUM, k_cam_segsum<18>, dim3(d.n_cams), dim3(kBlock), 0, c->w.scat, d.cam_ptr_g, c->w.camlin, (const PcgStatus*)nullptr);
-    ReduceJobs j{};
-    const double* ins[3] = {d.part, d.part + d.n_items, d.part + 2 * (size_t)d.n_items};
-    double* outs[3] = {d.scal + S_COST, d.scal + S_XNORM2_PTS, d.scal + S_GRADMAX_PTS};
-    for (int q = 0; q < 3; ++q) { j.in[q] = ins[q]; j.n[q] = d.n_items; j.out[q] = outs[q]; j.op[q] = q == 2 ? 1 : 0; }
-    LAUNCH(c, K_SMALL, k_reduce_multi, dim3(3), dim3(kPcgThreads), 0, j);
-    return 0;
-}
-
 // S assembly in bal9 mode: Gram tiles per (operand height, LDS class) bucket (k9_pairs_gram), every other item through the
 // per-pair kernel, then the fixed-order sums over the S assembly's camera-major entries (cam_ptr_g) and the tile fill.
 static int assemble_wide(xrsfm_ba_context* c, double radius) {
     Dev& d = c->d;
     CholHost& h = c->chol;
     const int n_obs_pairs = h.n_pairs - c->pk.n_gt_cells;
+    c->step_radius = radius;        // (k9_backsub: finish_step)
     {
         Timed t_(c, K_SCHUR_PAIRS);
         const int* items = h.pairs_items;
@@ -1942,127 +1953,6 @@ static int assemble_wide(xrsfm_ba_context* c, double radius) {
     if (h.n_tiles_nz > 0) LAUNCH(c, K_DENSE_FILL, k9_tile_fill, dim3(h.n_tiles_nz), dim3(256), 0, h.dev, d, c->w, h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc, radius);
     h.S_filled = true;
     return 0;
-}
-
-static int run_wide(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_summary* sum) {
-    Dev& d = c->d;
-    CholHost& h = c->chol;
-    hipStream_t st = c->stream;
-    int e;
-    sum->linear_solver_used = XRSFM_BA_SOLVER_CHOLESKY;
-    c->profiling = opt.profile != 0;
-    for (int i = 0; i < K_COUNT; ++i) { c->prof_ms[i] = 0.0; c->prof_n[i] = 0; }
-    c->recs.clear(); c->ev_used = 0;
-    const auto t_begin = std::chrono::steady_clock::now();
-    sum->num_residuals = 2 * c->pk.n_obs;
-    {
-        int n_var_i = 0;
-        std::vector<unsigned char> cc(d.n_cams);
-        std::vector<double> act(d.n_cams);
-        if (d.n_cams) { HIPCHK(hipMemcpy(cc.data(), d.cam_const, d.n_cams, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(act.data(), d.cam_act, sizeof(double) * d.n_cams, hipMemcpyDeviceToHost)); }
-        for (int i = 0; i < d.n_cams; ++i) n_var_i += (act[i] > 0.0 && (cc[i] & kCamIntrVariable)) ? 1 : 0;
-        sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p + n_var_i);
-    }
-    auto finish = [&](int term, int reason, double cost) {
-        sum->termination = term; sum->termination_reason = reason; sum->final_cost = cost;
-        (void)hipStreamSynchronize(st);
-        sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        if (int be = bwd_all_status(c)) return be;
-        if (c->profiling) {
-            profile_collect(c);
-            int best = 0;
-            for (int i = 1; i < K_COUNT - 1; ++i) if (c->prof_ms[i] > c->prof_ms[best]) best = i;
-            sum->dom_kernel_id = best; sum->dom_kernel_ms = c->prof_ms[best]; sum->dom_kernel_launches = c->prof_n[best];
-        }
-        c->profiling = false;
-        return XRSFM_BA_OK;
-    };
-    auto gradmax_fetch = [&](double* gmax) {
-        LAUNCH(c, K_SMALL, k9_gradmax_cams, dim3(1), dim3(kPcgThreads), 0, d, c->w, d.scal + S_GRADMAX_CAMS);
-        int e2 = fetch_scalars(c);
-        if (e2) return e2;
-        *gmax = std::fmax(c->h_scal[S_GRADMAX_PTS], c->h_scal[S_GRADMAX_CAMS]);
-        return 0;
-    };
-    // iteration 0: Jacobi scaling from the unscaled column norms, then the scaled linearisation
-    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_cams * kW, kBlock) + 1), dim3(kBlock), 0, c->w.scale_c, 1.0, (size_t)d.n_cams * kW);
-    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_pts * 3, kBlock) + 1), dim3(kBlock), 0, d.scale_p, 1.0, (size_t)d.n_pts * 3);
-    if ((e = linearize_wide(c, opt.huber_a, false))) return e;
-    {
-        const long long n = std::max((long long)d.n_cams * kW, (long long)d.n_pts * 3);
-        LAUNCH(c, K_SMALL, k9_scale_from_norms, dim3(cdiv(n, kBlock) + 1), dim3(kBlock), 0, d, c->w);
-    }
-    if ((e = linearize_wide(c, opt.huber_a, true))) return e;
-    c->linearized = true;
-    double gmax = 0.0;
-    if ((e = gradmax_fetch(&gmax))) return e;
-    double cost = 0.5 * c->h_scal[S_COST];
-    double xnorm2_pts = c->h_scal[S_XNORM2_PTS];
-    sum->initial_cost = cost;
-    double radius = opt.initial_radius, decrease = 2.0;
-    print_progress(opt, 0, cost, 0.0, gmax, 0.0, 0.0, radius);
-    if (gmax <= opt.gradient_tolerance) return finish(XRSFM_BA_CONVERGENCE, 1, cost);
-    int it = 0, invalid = 0;
-    const double max_radius = 1e16, min_radius = 1e-32, min_rel_decrease = 1e-3;
-    const int n_obs_pairs = h.n_pairs - c->pk.n_gt_cells;
-    while (true) {
-        if (it >= opt.max_iterations) return finish(XRSFM_BA_NO_CONVERGENCE, 5, cost);
-        ++it;
-        sum->lm_steps_attempted++;
-        // reduced camera system: per-observation diagonal terms + per-pair blocks, fixed-order sums, tile fill, tile Cholesky
-        (void)n_obs_pairs;
-        if ((e = assemble_wide(c, radius))) return e;
-        if ((e = chol_factor_solve(c))) return e;
-        {   // back-substitution + candidate state, cost of the candidate, the scalars of the step
-            const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cdiv(d.n_cams, kBlock);
-            if (nbi + nbc > 0) LAUNCH(c, K_BACKSUB, k9_backsub, dim3(nbi + nbc), dim3(kBlock), 0, d, c->w, nbi, radius);
-            if (d.n_items > 0) LAUNCH(c, K_COST, k_cost, dim3(cdiv(d.n_items, kWavesPerBlock)), dim3(kBlock), 0, d, opt.huber_a);
-            ReduceJobs j{};
-            const double* ins[5] = {d.part, d.part + 2 * (size_t)d.n_items, d.part + 3 * (size_t)d.n_items, d.campart, d.campart + d.n_cams};
-            const int ns[5] = {d.n_items, d.n_items, d.n_items, d.n_cams, d.n_cams};
-            double* outs[5] = {d.scal + S_COST_CAND, d.scal + S_MODEL, d.scal + S_STEP2_PTS, d.scal + S_STEP2_CAMS, d.scal + S_XNORM2_CAMS};
-            for (int q = 0; q < 5; ++q) { j.in[q] = ins[q]; j.n[q] = ns[q]; j.out[q] = outs[q]; j.op[q] = 0; }
-            LAUNCH(c, K_SMALL, k_reduce_multi, dim3(5), dim3(kPcgThreads), 0, j);
-            if ((e = fetch_scalars(c))) return e;
-        }
-        const double* s = c->h_scal;
-        const double model_change = s[S_MODEL];
-        const double xnorm = std::sqrt(xnorm2_pts + s[S_XNORM2_CAMS]);
-        if (!(model_change > 0.0) || !std::isfinite(model_change)) {
-            ++invalid;
-            sum->n_unsuccessful++;
-            print_progress(opt, it, cost, 0.0, gmax, 0.0, 0.0, radius);
-            if (invalid >= 5) return finish(XRSFM_BA_FAILURE, 6, cost);
-            radius /= decrease; decrease *= 2.0;
-            if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
-            continue;
-        }
-        invalid = 0;
-        const double cost_cand = 0.5 * s[S_COST_CAND];
-        const double step_norm = std::sqrt(s[S_STEP2_PTS] + s[S_STEP2_CAMS]);
-        if (step_norm <= opt.parameter_tolerance * (xnorm + opt.parameter_tolerance)) return finish(XRSFM_BA_CONVERGENCE, 2, cost);
-        const double cost_change = cost - cost_cand;
-        if (std::fabs(cost_change) <= opt.function_tolerance * cost) return finish(XRSFM_BA_CONVERGENCE, 3, cost);
-        const double rel = cost_change / model_change;
-        if (rel > min_rel_decrease) {
-            std::swap(d.cam, d.cam_cand);
-            std::swap(d.P, d.P_cand);
-            if ((e = linearize_wide(c, opt.huber_a, true))) return e;
-            if ((e = gradmax_fetch(&gmax))) return e;
-            cost = 0.5 * c->h_scal[S_COST];
-            xnorm2_pts = c->h_scal[S_XNORM2_PTS];
-            radius = std::fmin(max_radius, radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
-            decrease = 2.0;
-            sum->n_successful++;
-            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, radius);
-            if (gmax <= opt.gradient_tolerance) return finish(XRSFM_BA_CONVERGENCE, 1, cost);
-        } else {
-            radius /= decrease; decrease *= 2.0;
-            sum->n_unsuccessful++;
-            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, radius);
-            if (radius < min_radius) return finish(XRSFM_BA_CONVERGENCE, 4, cost);
-        }
-    }
 }
 
 static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) {
@@ -2100,7 +1990,6 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
         }
         return e;
     }
-    if (c->wide) return run_wide(c, opt, sum);
     if ((e = use_stored_j(c, !jfree_for_run(c, solver)))) return e;
     sum->linear_solver_used = solver;
     c->profiling = opt.profile != 0;
@@ -2108,7 +1997,16 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
     c->recs.clear(); c->ev_used = 0;
     const auto t_begin = std::chrono::steady_clock::now();
     sum->num_residuals = 2 * c->pk.n_obs;
-    sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p);
+    {
+        int n_var_i = 0;        // bal9: cameras whose intrinsics {f, k1, k2} are variable
+        if (c->wide && d.n_cams) {
+            std::vector<unsigned char> cc(d.n_cams);
+            std::vector<double> act(d.n_cams);
+            HIPCHK(hipMemcpy(cc.data(), d.cam_const, d.n_cams, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(act.data(), d.cam_act, sizeof(double) * d.n_cams, hipMemcpyDeviceToHost));
+            for (int i = 0; i < d.n_cams; ++i) n_var_i += (act[i] > 0.0 && (cc[i] & kCamIntrVariable)) ? 1 : 0;
+        }
+        sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p + n_var_i);
+    }
     auto finish = [&](int term, int reason, double cost) {
         sum->termination = term; sum->termination_reason = reason; sum->final_cost = cost;
         (void)hipStreamSynchronize(st);
@@ -2130,52 +2028,53 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
     double cost = 0.5 * c->h_scal[S_COST];
     double xnorm2_pts = c->h_scal[S_XNORM2_PTS];
     sum->initial_cost = cost;
-    double radius = opt.initial_radius, decrease = 2.0;
-    print_progress(opt, 0, cost, 0.0, gmax, 0.0, 0.0, radius);
+    xtr::TrustRegion tr{opt.initial_radius};
+    print_progress(opt, 0, cost, 0.0, gmax, 0.0, 0.0, tr.radius);
     if (gmax <= opt.gradient_tolerance) return finish(XRSFM_BA_CONVERGENCE, 1, cost);
-    int it = 0, invalid = 0;
-    const double max_radius = 1e16, min_radius = 1e-32, min_rel_decrease = 1e-3;
+    int it = 0;
     // While steps are being accepted, finish_step() linearises at the candidate straight away: one host round trip per LM
     // iteration hands over the model decrease and step norms of the step AND the cost, |x|^2 and gradient max-norm at the
     // candidate.  After a rejected step (they come in runs while the radius collapses) only the cost of the candidate is
     // evaluated, and the linearisation follows once a step is accepted again; once a solve has seen a rejection, two accepted
     // steps in a row are needed before the next one is linearised ahead again (near convergence accepted and rejected steps
-    // alternate, and a wasted linearisation costs more than a saved cost pass).
-    bool speculate = true;
+    // alternate, and a wasted linearisation costs more than a saved cost pass).  bal9 contexts never speculate.
+    bool speculate = !c->wide;
     int accepted_run = 0;
     while (true) {
         if (it >= opt.max_iterations) return finish(XRSFM_BA_NO_CONVERGENCE, 5, cost);
         ++it;
         sum->lm_steps_attempted++;
-        if ((e = prepare_step(c, radius, solver == XRSFM_BA_SOLVER_CHOLESKY))) return e;
-        if (solver == XRSFM_BA_SOLVER_PCG) {
-            if ((e = pcg_solve(c, opt, sum))) return e;
-        } else {
-            if ((e = chol_assemble(c))) return e;
+        if (c->wide) {
+            if ((e = assemble_wide(c, tr.radius))) return e;
             if ((e = chol_factor_solve(c))) return e;
+        } else {
+            if ((e = prepare_step(c, tr.radius, solver == XRSFM_BA_SOLVER_CHOLESKY))) return e;
+            if (solver == XRSFM_BA_SOLVER_PCG) {
+                if ((e = pcg_solve(c, opt, sum))) return e;
+            } else {
+                if ((e = chol_assemble(c))) return e;
+                if ((e = chol_factor_solve(c))) return e;
+            }
         }
         if ((e = finish_step(c, opt.huber_a, speculate))) return e;
         const double* s = c->h_scal;
         const double model_change = s[S_MODEL];
         const double xnorm = std::sqrt(xnorm2_pts + s[S_XNORM2_CAMS]);
         if (!(model_change > 0.0) || !std::isfinite(model_change)) {
-            ++invalid;
             sum->n_unsuccessful++;
-            print_progress(opt, it, cost, 0.0, gmax, 0.0, 0.0, radius);
-            if (invalid >= 5) return finish(XRSFM_BA_FAILURE, 6, cost);
-            radius /= decrease; decrease *= 2.0;
+            print_progress(opt, it, cost, 0.0, gmax, 0.0, 0.0, tr.radius);
+            if (const int r = tr.invalid_step()) return finish(XRSFM_BA_FAILURE, r, cost);
             if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
             continue;
         }
-        invalid = 0;
+        tr.invalid = 0;
         const double cost_cand = 0.5 * (speculate ? s[S_COST] : s[S_COST_CAND]);    // (S_COST: of the linearisation at the candidate)
         const double step_norm = std::sqrt(s[S_STEP2_PTS] + s[S_STEP2_CAMS]);
-        if (step_norm <= opt.parameter_tolerance * (xnorm + opt.parameter_tolerance))
-            return finish(XRSFM_BA_CONVERGENCE, 2, cost);
         const double cost_change = cost - cost_cand;
-        if (std::fabs(cost_change) <= opt.function_tolerance * cost) return finish(XRSFM_BA_CONVERGENCE, 3, cost);
+        if (const int r = xtr::TrustRegion::tolerance_exit(step_norm, xnorm, opt.parameter_tolerance, cost_change, cost, opt.function_tolerance))
+            return finish(XRSFM_BA_CONVERGENCE, r, cost);
         const double rel = cost_change / model_change;
-        if (rel > min_rel_decrease) {
+        if (xtr::TrustRegion::successful(rel)) {
             if (speculate) {
                 accept_candidate(c);
                 cost = cost_cand;
@@ -2184,25 +2083,24 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
             } else {
                 std::swap(d.cam, d.cam_cand);
                 std::swap(d.P, d.P_cand);
-                if ((e = linearize(c, opt.huber_a, d, false, LIN_FINAL))) return e;
+                if ((e = c->wide ? linearize_wide(c, opt.huber_a) : linearize(c, opt.huber_a, d, false, LIN_FINAL))) return e;
                 if ((e = gradient_max(c, &gmax))) return e;
                 cost = 0.5 * c->h_scal[S_COST];
                 xnorm2_pts = c->h_scal[S_XNORM2_PTS];
             }
             ++accepted_run;
-            speculate = sum->n_unsuccessful == 0 || accepted_run >= 2;
-            radius = std::fmin(max_radius, radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
-            decrease = 2.0;
+            speculate = !c->wide && (sum->n_unsuccessful == 0 || accepted_run >= 2);
+            tr.grow(rel);
             sum->n_successful++;
-            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, radius);
+            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, tr.radius);
             if (gmax <= opt.gradient_tolerance) return finish(XRSFM_BA_CONVERGENCE, 1, cost);
         } else {
             speculate = false; accepted_run = 0;
-            radius /= decrease; decrease *= 2.0;
+            const int r = tr.shrink();
             if (!d.Jp && (e = use_stored_j(c, true, true))) return e;     // (a retry of this linearisation: stored J from here on, jfree_for_run)
             sum->n_unsuccessful++;
-            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, radius);
-            if (radius < min_radius) return finish(XRSFM_BA_CONVERGENCE, 4, cost);
+            print_progress(opt, it, cost, cost_change, gmax, step_norm, rel, tr.radius);
+            if (r) return finish(XRSFM_BA_CONVERGENCE, r, cost);
         }
     }
 }
@@ -2661,18 +2559,9 @@ int xrsfm_ba_debug_wide(xrsfm_ba_context* c, double huber_a, double radius, doub
     if (!c || !c->wide) return XRSFM_BA_EINVAL;
     HIPCHK(hipSetDevice(c->device));
     Dev& d = c->d;
-    CholHost& h = c->chol;
     int e;
-    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_cams * kW, kBlock) + 1), dim3(kBlock), 0, c->w.scale_c, 1.0, (size_t)d.n_cams * kW);
-    LAUNCH(c, K_SMALL, k_fill, dim3(cdiv((long long)d.n_pts * 3, kBlock) + 1), dim3(kBlock), 0, d.scale_p, 1.0, (size_t)d.n_pts * 3);
-    if ((e = linearize_wide(c, huber_a, false))) return e;
-    {
-        const long long n = std::max((long long)d.n_cams * kW, (long long)d.n_pts * 3);
-        LAUNCH(c, K_SMALL, k9_scale_from_norms, dim3(cdiv(n, kBlock) + 1), dim3(kBlock), 0, d, c->w);
-    }
-    if ((e = linearize_wide(c, huber_a, true))) return e;
+    if ((e = init_scaling_and_linearize(c, huber_a, true))) return e;
     if ((e = fetch_scalars(c))) return e;
-    c->linearized = true;
     if (cost) *cost = 0.5 * c->h_scal[S_COST];
     const Packed& k = c->pk;
     const size_t ns = (size_t)k.n_slots;
