@@ -38,6 +38,7 @@ extern "C" {
 #define XRSFM_BA_ESTATE (-5)   /* call order violated                            */
 #define XRSFM_BA_ETOOBIG (-6)  /* explicit reduced camera matrix requested (CHOLESKY) but it does not fit: use AUTO or PCG */
 #define XRSFM_BA_EINTERNAL (-7) /* an unexpected C++ exception was stopped at the boundary (never the termination code +2) */
+#define XRSFM_BA_ESINGULAR (-8) /* S(0) is not positive definite: gauge not fixed, a selected camera is unobserved, or a free point's undamped block is singular */
 
 /* camera models: ids of /root/reference/src/base/camera_model.hpp:93-209 */
 #define XRSFM_BA_SIMPLE_PINHOLE 0 /* {f,cx,cy}             uv = 2f*xn + c (reference quirk, :102-105) */
@@ -181,6 +182,35 @@ int xrsfm_ba_download(xrsfm_ba_context *ctx, double *cam_q, double *cam_t, doubl
 /* bal9 mode: intrinsics {f, k1, k2} of the cameras with XRSFM_BA_INTR_VARIABLE into intr_params [n_intr][8] (other rows and
  * columns untouched); a no-op for ordinary problems. */
 int xrsfm_ba_download_intrinsics(xrsfm_ba_context *ctx, double *intr_params);
+
+/* Marginal covariance of selected cameras at the CURRENT device state (after create, run or reset):
+ * block (c,c) of (J^T J)^-1 with J the robustified Jacobian (Huber huber_a) in the tangent space of the
+ * library's Plus (rotation 3, translation 3: the order of debug_linearize's Jc columns), UNSCALED
+ * coordinates, no damping, no sigma^2 factor: what ceres::Covariance::GetCovarianceBlockInTangentSpace
+ * returns for (q,t) of one frame.  cov [n_sel][6][6] row-major, symmetric.  Rows/columns of a constant
+ * block (XRSFM_BA_CONST_Q / _T) are zero.  Does not change the state or the trust region of a later run.
+ *
+ * How: the state is linearised like the first iteration of a run (Jacobi scaling), the reduced camera matrix S is assembled
+ * with the damping an explicit ZERO (the point blocks are inverted undamped, all-zero rows of constant blocks get a unit
+ * diagonal) and factored by the tile Cholesky of XRSFM_BA_SOLVER_CHOLESKY.  With Z_c = L^-1 E_c (E_c: the 6 unit columns of
+ * camera c) the block is D_c Z_c^T Z_c D_c, D_c the Jacobi scale: a forward substitution with a 64-column panel (10 cameras)
+ * through the level-scheduled factor, dense or packed tile storage (xrsfm_amd/csrc/ba_cov.h), restricted to the tile columns the
+ * selected cameras reach in the elimination tree.  Plans on a panel / look-ahead panel schedule (xrsfm_ba_debug_chol_plan
+ * stats[6] bit 0 clear, more than one tile column) take a slow exact fallback instead: S x = e_j for the 6 unit vectors of each
+ * camera with the run path's factor-and-solve, 6 factorisations per camera; XRSFM_BA_COV_FALLBACK=1 (environment, read per call)
+ * forces it everywhere (A/B check of the panel kernel).  The result does not depend on the order of cam_sel, and on the kernel
+ * path a camera's block is bit-identical whatever else is selected with it.
+ *
+ * Errors: XRSFM_BA_EINVAL — index out of range, duplicate in cam_sel, n_sel < 0, NULL cam_sel / cov with n_sel > 0, bal9 context,
+ * multi-rank context (communicator or test hook), a track observed twice by one camera; XRSFM_BA_ETOOBIG exactly where
+ * XRSFM_BA_SOLVER_CHOLESKY returns it (there is no PCG variant); XRSFM_BA_ESINGULAR — a selected camera has no observation, a
+ * free point's undamped 3x3 block is singular (a track of one observation), or the factorisation met a non-positive pivot
+ * (recognised like an invalid step of a run: the solution of the factored system is not finite), or a block would hold a NaN / Inf
+ * (a nearly singular S whose Z^T Z overflows).  The result is staged and checked before it is copied: on every error code cov is
+ * left UNTOUCHED, it never receives a NaN or an Inf.  A singular point block is named on stderr (how many, and the first one's
+ * index).  n_sel == 0 is success and touches nothing.
+ * Not built: point covariances, camera-camera cross blocks, bal9, several ranks, a PCG variant. */
+int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *cam_sel, double *cov);
 
 void xrsfm_ba_destroy(xrsfm_ba_context *ctx);
 

@@ -1,0 +1,73 @@
+"""Time of one xrsfm_ba_covariance call on bench config L's problem (1000 cameras / 500 000 points / 2M observations) for 1, 10,
+100 and all 1000 cameras, next to the time of one LM iteration of the same context; one table.  Host clock around blocking
+calls (every call ends in a device synchronise); the first call of each size is a warm-up and is not counted.
+
+    python tools/cov_timing.py [--config L] [--repeat 5] [--fallback-cams 10]
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch  # noqa: F401  (first, so that both share one HIP runtime)
+
+from xrsfm_amd import capi, synth
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="L")
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--fallback-cams", type=int, default=10, help="also time the fallback path for this many cameras (0: skip)")
+    args = ap.parse_args()
+    if capi.device_count() < 1:
+        raise SystemExit("cov_timing: no HIP device")
+    d = synth.make_problem(**synth.CONFIGS[args.config])
+    arr = {k: np.array(d[k], copy=True) for k in capi.ProblemArrays.FIELDS}
+    cc = arr["cam_const"].copy(); cc[0] |= 3; cc[1] |= 2; arr["cam_const"] = cc      # the gauge of the reference's GBA
+    n = arr["cam_q"].shape[0]
+    plan = capi.debug_chol_plan(capi.ProblemArrays(**arr))
+    ctx = capi.Context(capi.ProblemArrays(**arr))
+    opt = capi.default_options(linear_solver=capi.SOLVER_CHOLESKY)
+    ctx.run(opt)                                   # warm-up (set-up of the factorisation, code objects)
+    lm = []
+    for _ in range(args.repeat):
+        ctx.reset()
+        t0 = time.perf_counter(); s = ctx.run(opt); dt = time.perf_counter() - t0
+        lm.append(dt / max(1, s.n_successful + s.n_unsuccessful))
+    ctx.reset()                                    # the covariance is timed at the uploaded state
+    rng = np.random.default_rng(0)
+    rows = []
+    for m in (1, 10, 100, n):
+        sel = np.sort(rng.choice(n, m, replace=False)) if m < n else np.arange(n)
+        ctx.covariance(sel)
+        ts = []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter(); ctx.covariance(sel); ts.append(time.perf_counter() - t0)
+        rows.append((f"{m} cameras", min(ts), float(np.median(ts))))
+    if args.fallback_cams > 0:
+        sel = np.sort(rng.choice(n, args.fallback_cams, replace=False))
+        os.environ["XRSFM_BA_COV_FALLBACK"] = "1"
+        try:
+            ctx.covariance(sel)
+            ts = []
+            for _ in range(max(1, args.repeat // 2)):
+                t0 = time.perf_counter(); ctx.covariance(sel); ts.append(time.perf_counter() - t0)
+        finally:
+            del os.environ["XRSFM_BA_COV_FALLBACK"]
+        rows.append((f"{args.fallback_cams} cameras, fallback", min(ts), float(np.median(ts))))
+    ctx.close()
+    print(f"config {args.config}: {n} cameras, {arr['points'].shape[0]} points, {arr['obs_cam'].shape[0]} observations; "
+          f"{plan['tiles']} tile columns on {plan['levels']} levels, schedule {plan['facts']['schedule']}, packed {plan['facts']['packed']}")
+    print(f"| call | min ms | median ms | x one LM iteration |")
+    print(f"|---|---|---|---|")
+    lm_ms = 1e3 * float(np.median(lm))
+    print(f"| one LM iteration (whole run / iterations) | {1e3 * min(lm):.3f} | {lm_ms:.3f} | 1.0 |")
+    for name, tmin, tmed in rows:
+        print(f"| covariance, {name} | {1e3 * tmin:.3f} | {1e3 * tmed:.3f} | {1e3 * tmed / lm_ms:.1f} |")
+
+
+if __name__ == "__main__":
+    main()

@@ -26,6 +26,7 @@
 
 #include "../../include/xrsfm_ba.h"
 #include "ba_chol.h"
+#include "ba_cov.h"
 #include "ba_filter.h"
 #include "ba_kernels.h"
 #include "ba_pack.h"
@@ -147,6 +148,7 @@ struct CholHost {
     int *tf_ptr = nullptr, *tf_ent = nullptr;                // per non-zero tile: its 6x6 blocks (k_tile_fill)
     std::vector<int> cam_off_host;
     std::vector<int> tile_map_host; size_t S_doubles = 0;    // packed tile storage of S (CholDev::tmap), its size in doubles
+    std::vector<int> lv_k_host, lv_bptr_host, lv_bi_host;    // host copies of the level lists (xrsfm_ba_covariance: which tile columns a selection reaches)
     int ordering = 0;                                        // 0 natural, 1 nested dissection of a band/ring, 2 reverse Cuthill-McKee, 3 nested dissection of an unordered graph
 };
 
@@ -995,6 +997,7 @@ int chol_setup(xrsfm_ba_context* c) {
     { const char* me = std::getenv("XRSFM_BA_GRAM_MERGE"); h.gram_merge = !(me && me[0] == '0'); }      // (read per set-up: the A/B test switches it)
     h.cols_off = P.cols_off; h.bw2_off = P.bw2_off; h.bw2_link = P.bw2_link;
     h.lv_k_off = P.lv_k_off; h.lv_tgt_off = P.lv_tgt_off;
+    h.lv_k_host = P.lv_k; h.lv_bptr_host = P.lv_bptr; h.lv_bi_host = P.lv_bi;
     h.sp_chunk_off = P.sp_chunk_off; h.sp_rt_off = P.sp_rt_off; h.mp_off = P.mp_off; h.fz_off = P.fz_off;
     int *d_cam_off = nullptr, *d_tile_rows = nullptr, *d_tmap = nullptr;
 #define TRYC(x) do { e = (x); if (e) return e; } while (0)
@@ -1493,6 +1496,199 @@ int init_scaling_and_linearize(xrsfm_ba_context* c, double huber_a, bool use_sca
     }
     c->linearized = true;
     return 0;
+}
+
+// ---------------------------------------------------------------- marginal covariance of selected cameras (ba_cov.h)
+struct DevScratch {          // device memory of one call
+    std::vector<void*> p;
+    ~DevScratch() { for (void* q : p) (void)hipFree(q); }
+    template <typename T>
+    int get(T** out, size_t n) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return XRSFM_BA_ENOMEM;
+        p.push_back(q); *out = static_cast<T*>(q);
+        return 0;
+    }
+    template <typename T>
+    int put(T** out, const std::vector<T>& v) {
+        if (int e = get(out, v.size())) return e;
+        if (!v.empty() && hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return XRSFM_BA_ENODEV;
+        return 0;
+    }
+};
+
+// The run path's test of a solved step (ba_run_impl: a model decrease that is not finite is an invalid step): a non-positive
+// pivot leaves NaN in Linv of its tile column and from there in the solution.
+static int cov_solution_status(xrsfm_ba_context* c, std::vector<double>& x) {
+    x.resize((size_t)c->d.n_cams * 6);
+    HIPCHK(hipMemcpyAsync(x.data(), c->d.px, x.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (int e = bwd_all_status(c)) return e;
+    for (double v : x) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    return 0;
+}
+
+// Work lists of k_lv_fwd_multi for every chunk of the selection (cameras sorted by elimination position, 10 per chunk)
+struct CovLists {
+    std::vector<int4> ent; std::vector<int2> lj; std::vector<int> sel_row, sel_cam;
+    struct Launch { int chunk, ent0, n; };      // one per (chunk, level with reached columns)
+    std::vector<Launch> launches;
+    std::vector<int> chunk_slots;               // panel slots (reached tile columns) per chunk
+    int max_slots = 0;
+};
+static void cov_build_lists(const CholHost& h, const std::vector<int>& cams_sorted, CovLists& L) {
+    const int T = h.T, n_lv = h.n_levels;
+    // rows[i]: the columns j < i with a structurally non-zero tile (i, j), ascending (the transpose of the backward lists)
+    std::vector<std::vector<int>> rows(T);
+    for (size_t e = 0; e < h.lv_k_host.size(); ++e)
+        for (int q = h.lv_bptr_host[e]; q < h.lv_bptr_host[e + 1]; ++q) rows[h.lv_bi_host[q]].push_back(h.lv_k_host[e]);
+    for (auto& r : rows) std::sort(r.begin(), r.end());
+    std::vector<char> reached(T);
+    std::vector<int> slot(T);
+    const int n = (int)cams_sorted.size();
+    for (int c0 = 0, ch = 0; c0 < n; c0 += kCovCamsPerChunk, ++ch) {
+        const int nc = std::min(kCovCamsPerChunk, n - c0);
+        std::fill(reached.begin(), reached.end(), 0);
+        for (int i = 0; i < nc; ++i) {
+            const int cam = cams_sorted[c0 + i];
+            L.sel_cam.push_back(cam); L.sel_row.push_back(h.cam_off_host[cam]);
+            reached[h.cam_off_host[cam] / kNB] = 1;
+        }
+        for (int i = nc; i < kCovCamsPerChunk; ++i) { L.sel_cam.push_back(-1); L.sel_row.push_back(0); }      // (fixed stride per chunk)
+        // a reached column reaches every row tile of its column of L (levels ascend along lv_k)
+        for (size_t e = 0; e < h.lv_k_host.size(); ++e)
+            if (reached[h.lv_k_host[e]])
+                for (int q = h.lv_bptr_host[e]; q < h.lv_bptr_host[e + 1]; ++q) reached[h.lv_bi_host[q]] = 1;
+        int ns = 0;
+        for (int k = 0; k < T; ++k) slot[k] = reached[k] ? ns++ : -1;
+        L.chunk_slots.push_back(ns); L.max_slots = std::max(L.max_slots, ns);
+        for (int lv = 0; lv < n_lv; ++lv) {
+            const int ent0 = (int)L.ent.size();
+            for (int e = h.lv_k_off[lv]; e < h.lv_k_off[lv + 1]; ++e) {
+                const int k = h.lv_k_host[e];
+                if (!reached[k]) continue;
+                const int q0 = (int)L.lj.size();
+                for (int j : rows[k]) if (reached[j]) L.lj.push_back(make_int2(j, slot[j]));
+                L.ent.push_back(make_int4(k, slot[k], q0, (int)L.lj.size()));
+            }
+            if ((int)L.ent.size() > ent0) L.launches.push_back({ch, ent0, (int)L.ent.size() - ent0});
+        }
+    }
+}
+
+int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
+    if (n_sel == 0) return XRSFM_BA_OK;
+    if (!cam_sel || !cov) return XRSFM_BA_EINVAL;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Nc = d.n_cams;
+    {
+        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
+        for (int i = 0; i < n_sel; ++i) {
+            const int s = cam_sel[i];
+            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
+            seen[s] = 1;
+        }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    int e;
+    if ((e = chol_setup(c))) return e == kErrDuplicateObs ? XRSFM_BA_EINVAL : e;
+    std::vector<unsigned char> cc((size_t)Nc);
+    std::vector<double> act((size_t)Nc), sc((size_t)Nc * 6);
+    HIPCHK(hipMemcpy(cc.data(), d.cam_const, (size_t)Nc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(act.data(), d.cam_act, sizeof(double) * (size_t)Nc, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_sel; ++i) if (!(act[cam_sel[i]] > 0.0)) return XRSFM_BA_ESINGULAR;      // no observation: no information
+    // linearise at the current state like the first iteration of a run (Jacobi scaling from the unscaled column norms)
+    if ((e = use_stored_j(c, !jfree_for_run(c, XRSFM_BA_SOLVER_CHOLESKY)))) return e;
+    if ((e = init_scaling_and_linearize(c, huber_a, true))) return e;
+    if ((e = fetch_scalars(c))) return e;
+    HIPCHK(hipMemcpy(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost));
+    DevScratch ds;
+    // zero damping, stated as such: the undamped point factors and D_c^2 = 0 in the buffers the S assembly reads when it does not
+    // form the damping itself (the XRSFM_BA_PREP_FUSED=0 form of chol_assemble)
+    int* d_flag = nullptr;
+    if ((e = ds.get(&d_flag, 2))) return e;      // [0] singular free point blocks, [1] the first of them (packed point index)
+    {
+        const int init[2] = {0, 0x7fffffff};
+        HIPCHK(hipMemcpyAsync(d_flag, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    }
+    {
+        const int nbp = cdiv(d.n_pts, kBlock), nbc = cdiv((long long)Nc * 6, kBlock);
+        LAUNCH(c, K_SMALL, k_cov_prep, dim3(nbp + nbc), dim3(kBlock), 0, d, nbp, d_flag);
+    }
+    int flag[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flag[0]) {
+        // which track: the caller's point index (Packed::pt_orig stays on the host with either packing)
+        const bool have = (size_t)flag[1] < c->pk.pt_orig.size();
+        fprintf(stderr, "[xrsfm_ba] covariance: the undamped 3x3 block of %d free point(s) is not positive definite (a Cholesky pivot <= 64 eps x its "
+                        "diagonal entry); first: %s point %d.  Filter such tracks (xrsfm_ba_filter_tracks) or hold them constant.\n",
+                flag[0], have ? "caller" : "packed", have ? (int)c->pk.pt_orig[flag[1]] : flag[1]);
+        return XRSFM_BA_ESINGULAR;
+    }
+    c->step_radius = 0.0; c->step_prep = false; c->step_valid = false;
+    auto dof_const = [&](int cam, int a) { return (a < 3 ? (cc[cam] & 1u) : (cc[cam] & 2u)) != 0; };
+    std::vector<double> x;
+    std::vector<double> out((size_t)n_sel * 36);      // staged: cov is written only when every value is finite
+    const char* fe = std::getenv("XRSFM_BA_COV_FALLBACK");       // (read per call: the A/B oracle of the panel kernel)
+    // the panel kernel serves the level schedule (a single tile column is its own level); every other plan: the fallback
+    const bool fallback = (fe && fe[0] != '0') || !(h.use_levels || h.T == 1);
+    if (fallback) {
+        // S x = e_j for the 6 unit vectors of each selected camera with the run path's factor-and-solve; the factorisation
+        // overwrites S, so every solve assembles it again.  Rows c of x are column j of block (c, c).
+        for (int i = 0; i < n_sel; ++i) {
+            const int cam = cam_sel[i];
+            double M[6][6] = {{0.0}};
+            for (int a = 0; a < 6; ++a) {
+                if (dof_const(cam, a)) continue;
+                if ((e = chol_assemble(c, true))) return e;
+                HIPCHK(hipMemsetAsync(h.dev.rhs, 0, sizeof(double) * (size_t)h.dev.n_pad, c->stream));
+                LAUNCH(c, K_SMALL, k_fill, dim3(1), dim3(kBlock), 0, h.dev.rhs + h.cam_off_host[cam] + a, 1.0, (size_t)1);
+                if ((e = chol_factor_solve(c))) return e;
+                if ((e = cov_solution_status(c, x))) return e;
+                for (int b = 0; b < 6; ++b) M[b][a] = x[6 * (size_t)cam + b];
+            }
+            for (int a = 0; a < 6; ++a)
+                for (int b = 0; b < 6; ++b) {
+                    const bool fixed = dof_const(cam, a) || dof_const(cam, b);
+                    out[36 * (size_t)i + 6 * a + b] = fixed ? 0.0 : 0.5 * (M[a][b] + M[b][a]) * (sc[6 * (size_t)cam + a] * sc[6 * (size_t)cam + b]);
+                }
+        }
+    } else {
+        if ((e = chol_assemble(c, true))) return e;
+        if ((e = chol_factor_solve(c))) return e;
+        if ((e = cov_solution_status(c, x))) return e;
+        std::vector<int> order((size_t)n_sel), cams_sorted((size_t)n_sel);
+        for (int i = 0; i < n_sel; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return h.cam_off_host[cam_sel[a]] < h.cam_off_host[cam_sel[b]]; });
+        for (int i = 0; i < n_sel; ++i) cams_sorted[i] = cam_sel[order[i]];
+        CovLists L;
+        cov_build_lists(h, cams_sorted, L);
+        int4* d_ent = nullptr; int2* d_lj = nullptr; int *d_row = nullptr, *d_cam = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_cam, L.sel_cam)) ||
+            (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n_sel * 36))) return e;
+        size_t li = 0;
+        for (int ch = 0, c0 = 0; c0 < n_sel; ++ch, c0 += kCovCamsPerChunk) {
+            const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
+            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li)
+                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
+                       (const int*)(d_row + (size_t)ch * kCovCamsPerChunk), nc);
+            LAUNCH(c, K_SMALL, k_cov_gram, dim3(nc), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_cam + (size_t)ch * kCovCamsPerChunk), d_cov + 36 * (size_t)c0);
+        }
+        HIPCHK(hipGetLastError());
+        std::vector<double> hc((size_t)n_sel * 36);
+        HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < n_sel; ++i) memcpy(out.data() + 36 * (size_t)order[i], hc.data() + 36 * (size_t)i, 36 * sizeof(double));
+    }
+    // (a nearly singular S can pass the factorisation and still overflow in Z^T Z: the caller never sees a NaN or an Inf)
+    for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    memcpy(cov, out.data(), out.size() * sizeof(double));
+    return XRSFM_BA_OK;
 }
 
 }  // namespace
@@ -2981,5 +3177,6 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 
 // ---------------------------------------------------------------- exception barrier of the entry points that allocate on the host
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
+int xrsfm_ba_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) { return no_throw([&] { return covariance_impl(c, huber_a, n_sel, cam_sel, cov); }); }
 int xrsfm_pg_solve(const xrsfm_pg_options* opt, xrsfm_pg_problem* p, xrsfm_pg_summary* summary) { return no_throw([&] { return pg_solve_impl(opt, p, summary); }); }
 int xrsfm_tag_refine(const xrsfm_pg_options* opt, xrsfm_tag_problem* p, int32_t stages, xrsfm_pg_summary* summaries) { return no_throw([&] { return tag_refine_impl(opt, p, stages, summaries); }); }
