@@ -209,8 +209,37 @@ int xrsfm_ba_download_intrinsics(xrsfm_ba_context *ctx, double *intr_params);
  * (a nearly singular S whose Z^T Z overflows).  The result is staged and checked before it is copied: on every error code cov is
  * left UNTOUCHED, it never receives a NaN or an Inf.  A singular point block is named on stderr (how many, and the first one's
  * index).  n_sel == 0 is success and touches nothing.
- * Not built: point covariances, camera-camera cross blocks, bal9, several ranks, a PCG variant. */
+ * Not built: camera-camera cross blocks, bal9, several ranks, a PCG variant. */
 int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *cam_sel, double *cov);
+
+/* Marginal covariance of selected 3-D points at the CURRENT device state: block (p,p) of (J^T J)^-1 with the conventions of
+ * xrsfm_ba_covariance (robustified J, UNSCALED coordinates, no damping, no sigma^2 factor): what
+ * ceres::Covariance::GetCovarianceBlock returns for one track's point3d_.  pt_sel holds the caller's point indices,
+ * cov [n_sel][3][3] row-major, exactly symmetric.  A constant point (point_const) gets an all-zero block; a point whose observing
+ * cameras are all constant gets exactly D_p Hinv_p D_p.  Does not change the state or the trust region of a later run.
+ *
+ * How: the front half of xrsfm_ba_covariance (linearisation with Jacobi scaling, undamped point inverses Hinv_p, undamped S = L L^T
+ * by the tile Cholesky).  With W_p = sum_obs F_c^T E_p the 6 n_cams x 3 block column of the point (non-zero on the rows of the
+ * cameras that observe it, zero on constant blocks) the block is
+ *     D_p (Hinv_p + Y_p^T Y_p) D_p,   Y_p = L^-1 (W_p Hinv_p),   D_p the Jacobi scale of the point:
+ * one streaming pass over the observations forms the 6x3 blocks F_c^T E_p Hinv_p of the selected points, they are scattered into
+ * a 64-column right-hand-side panel (3 columns per point, 21 points per chunk) and go through the level-scheduled forward
+ * substitution of the camera call with a general right-hand side (xrsfm_amd/csrc/ba_cov.h), restricted to the tile columns of the
+ * cameras that observe a point of the chunk and their ancestors in the elimination tree; no backward pass.  Panel / look-ahead
+ * panel plans and XRSFM_BA_COV_FALLBACK=1 take the slow exact fallback: per point and column b one factor-and-solve S x_b = w_b
+ * (w_b: column b of W_p Hinv_p), Sigma_ab = Hinv_ab + w_a^T x_b, symmetrised: 3 factorisations per point.  The result does not
+ * depend on the order of pt_sel, on the kernel path a point's block is bit-identical whatever else is selected with it, and two
+ * calls agree bit for bit.
+ *
+ * Errors: XRSFM_BA_EINVAL — index out of range, duplicate in pt_sel, n_sel < 0, NULL pt_sel / cov with n_sel > 0, bal9 context,
+ * multi-rank context (communicator or test hook), a track observed twice by one camera; XRSFM_BA_ETOOBIG exactly where
+ * XRSFM_BA_SOLVER_CHOLESKY returns it; XRSFM_BA_ESINGULAR — a selected point has no observation in the program (constant or not:
+ * it is not part of it), ANY free point's undamped 3x3 block is singular (named on stderr like the camera call does), the solution
+ * of the factored system is not finite, or a block would hold a NaN / Inf.  The result is staged: on every error code cov is left
+ * UNTOUCHED.  n_sel == 0 is success and touches nothing.
+ * Not built: the covariance of ALL points by selected inversion, camera-camera and camera-point cross blocks, bal9, several ranks,
+ * a PCG variant. */
+int xrsfm_ba_point_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *pt_sel, double *cov);
 
 void xrsfm_ba_destroy(xrsfm_ba_context *ctx);
 

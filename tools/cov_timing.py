@@ -1,8 +1,11 @@
 """Time of one xrsfm_ba_covariance call on bench config L's problem (1000 cameras / 500 000 points / 2M observations) for 1, 10,
-100 and all 1000 cameras, next to the time of one LM iteration of the same context; one table.  Host clock around blocking
-calls (every call ends in a device synchronise); the first call of each size is a warm-up and is not counted.
+100 and all 1000 cameras, next to the time of one LM iteration of the same context; one table.  Then the same for
+xrsfm_ba_point_covariance: 1, 21, 210 and 2100 points (1, 1, 10 and 100 chunks of 21) spread over the ring, the 21-point fallback,
+and the ratio of every point row to the camera row with the same number of chunks (1, 10, 100, 1000 cameras are 1, 1, 10, 100
+chunks of 10).  Host clock around blocking calls (every call ends in a device synchronise); the first call of each size is a
+warm-up and is not counted.
 
-    python tools/cov_timing.py [--config L] [--repeat 5] [--fallback-cams 10]
+    python tools/cov_timing.py [--config L] [--repeat 5] [--fallback-cams 10] [--fallback-points 21]
 """
 import argparse
 import os
@@ -21,6 +24,7 @@ def main():
     ap.add_argument("--config", default="L")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--fallback-cams", type=int, default=10, help="also time the fallback path for this many cameras (0: skip)")
+    ap.add_argument("--fallback-points", type=int, default=21, help="also time the point fallback for this many points (0: skip)")
     args = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("cov_timing: no HIP device")
@@ -58,6 +62,35 @@ def main():
         finally:
             del os.environ["XRSFM_BA_COV_FALLBACK"]
         rows.append((f"{args.fallback_cams} cameras, fallback", min(ts), float(np.median(ts))))
+    # points: observed points ordered by their first observing camera, taken evenly over that order (spread over the ring)
+    n_pts = arr["points"].shape[0]
+    first = np.full(n_pts, n, np.int64)
+    np.minimum.at(first, arr["obs_pt"], arr["obs_cam"])
+    by_cam = np.argsort(first, kind="stable")
+    by_cam = by_cam[first[by_cam] < n]
+
+    def spread(m):
+        return by_cam[np.linspace(0, by_cam.shape[0] - 1, m).astype(int)].astype(np.int32)
+
+    prow = []
+    for m in (1, 21, 210, 2100):
+        sel = spread(m)
+        ctx.point_covariance(sel)
+        ts = []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter(); ctx.point_covariance(sel); ts.append(time.perf_counter() - t0)
+        prow.append((f"{m} points", min(ts), float(np.median(ts)), -(-m // 21)))
+    if args.fallback_points > 0:
+        sel = spread(args.fallback_points)
+        os.environ["XRSFM_BA_COV_FALLBACK"] = "1"
+        try:
+            ctx.point_covariance(sel)
+            ts = []
+            for _ in range(max(1, args.repeat // 2)):
+                t0 = time.perf_counter(); ctx.point_covariance(sel); ts.append(time.perf_counter() - t0)
+        finally:
+            del os.environ["XRSFM_BA_COV_FALLBACK"]
+        prow.append((f"{args.fallback_points} points, fallback", min(ts), float(np.median(ts)), None))
     ctx.close()
     print(f"config {args.config}: {n} cameras, {arr['points'].shape[0]} points, {arr['obs_cam'].shape[0]} observations; "
           f"{plan['tiles']} tile columns on {plan['levels']} levels, schedule {plan['facts']['schedule']}, packed {plan['facts']['packed']}")
@@ -67,6 +100,13 @@ def main():
     print(f"| one LM iteration (whole run / iterations) | {1e3 * min(lm):.3f} | {lm_ms:.3f} | 1.0 |")
     for name, tmin, tmed in rows:
         print(f"| covariance, {name} | {1e3 * tmin:.3f} | {1e3 * tmed:.3f} | {1e3 * tmed / lm_ms:.1f} |")
+    cam_by_chunks = {-(-m // 10): tmed for (name, _, tmed), m in zip(rows, (1, 10, 100, n))}      # (1 camera and 10 cameras: one chunk; the later row stays)
+    print()
+    print(f"| call | min ms | median ms | x one LM iteration | x camera call with as many chunks |")
+    print(f"|---|---|---|---|---|")
+    for name, tmin, tmed, chunks in prow:
+        ratio = f"{tmed / cam_by_chunks[chunks]:.2f} ({chunks} chunk{'s' if chunks > 1 else ''})" if chunks in cam_by_chunks else "-"
+        print(f"| point covariance, {name} | {1e3 * tmin:.3f} | {1e3 * tmed:.3f} | {1e3 * tmed / lm_ms:.1f} | {ratio} |")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 // Marginal covariance of selected cameras from the tile-Cholesky factor of the UNDAMPED reduced camera matrix
-// (include/xrsfm_ba.h: xrsfm_ba_covariance).
+// (include/xrsfm_ba.h: xrsfm_ba_covariance), and of selected points through the same forward substitution with a general
+// right-hand side (xrsfm_ba_point_covariance: the second half of this file).
 //
 // With S = L L^T and E_c the 6 unit columns of camera c in elimination order, Z_c = L^-1 E_c and block (c,c) of S^-1 is
 // Z_c^T Z_c: a forward substitution with a right-hand-side PANEL, no backward pass.  The panel holds 6 columns per camera,
@@ -86,6 +87,10 @@ __global__ void k_cov_prep(Dev d, int n_pt_blocks, int* __restrict__ singular) {
 //   sel_row [ci] = first elimination row of the chunk's camera ci (panel columns 6 ci .. 6 ci + 5), n_chunk <= 10 of them
 // LDS: two 64 x 66 operand tiles (67 584 B = 66 KiB: two workgroups per compute unit); the next operands are in registers while the
 // matrix cores work on the current ones, as in lv_factor_body.
+// RHS = false: the unit columns of the selected cameras (sel_row, n_chunk).  RHS = true (point covariance): a general right-hand
+// side, Xt_k = Bt_k - sum: the panel slot of k holds Bt_k on entry (k_cov_pt_scatter into zero-filled slots) and Zt_k on exit; only
+// this workgroup touches the slot during its level.  sel_row / n_chunk are not read.
+template <bool RHS>
 __global__ __launch_bounds__(256) void k_lv_fwd_multi(CholDev c, const int4* __restrict__ ent, const int2* __restrict__ lj,
                                                       double* __restrict__ Zt, const int* __restrict__ sel_row, int n_chunk) {
     __shared__ __attribute__((aligned(16))) double As[kNB * kLdT];
@@ -119,7 +124,20 @@ __global__ __launch_bounds__(256) void k_lv_fwd_multi(CholDev c, const int4* __r
         tile_abt_mfma(As, Bs, acc);            // += Zt_j L_kj^T
     }
     load_tile_regs(rb, c.Linv + (size_t)k * kNB * kNB, kNB);
+    if constexpr (RHS) load_tile_regs(ra, Zt + (size_t)en.y * kCovPanel, kNB);      // Bt_k
     __syncthreads();
+    if constexpr (RHS) {
+        store_tile_lds(As, ra);
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) As[(r0 + 16 * m + lk + 4 * g) * kLdT + c0 + 16 * n2 + li] -= acc[m][n2][g];
+        store_tile_lds(Bs, rb);
+        __syncthreads();
+    } else {
     // Xt_k = Et_k - sum (row = panel column, column = row of tile column k)
 #pragma unroll
     for (int m = 0; m < 2; ++m)
@@ -134,6 +152,7 @@ __global__ __launch_bounds__(256) void k_lv_fwd_multi(CholDev c, const int4* __r
         if ((row >> 6) == k) As[t * kLdT + (row & 63)] += 1.0;
     }
     __syncthreads();
+    }
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -177,6 +196,89 @@ __global__ __launch_bounds__(256) void k_cov_gram(Dev d, const double* __restric
         const double db = (b < 3 ? (cc & 1u) : (cc & 2u)) ? 0.0 : sc[b];
         cov[36 * (size_t)ci + e] = (da == 0.0 || db == 0.0) ? 0.0 : s * (da * db);      // (da * db: the same factor for (a, b) and (b, a))
     }
+}
+
+// ---------------------------------------------------------------- marginal covariance of selected points (xrsfm_ba_point_covariance)
+// Sigma_pp = Hinv_p + Y_p^T Y_p,  Y_p = L^-1 (W_p Hinv_p),  W_p = sum_obs F_c^T E_p (6 N_c x 3, rows of the observing cameras):
+// three right-hand-side columns per point, 21 points (63 of the 64 panel columns) per chunk, forward substitution only.
+constexpr int kCovPtsPerChunk = 21;
+
+// One streaming pass over the packed slots: every observation of a selected point (pt_col[packed point] >= 0: its index in the
+// selection) yields one record {selection index, camera} + the scaled 6x3 block F_c^T E_p Hinv_p (row-major, [a][b]), F / E as every
+// other consumer rebuilds them (load_FE_rc: stored or recomputed J).  blk == nullptr: count only (the host sizes the record arrays).
+// The record ORDER follows an integer ticket and is arbitrary; the values are not, and every (point, camera) cell of the panel has
+// exactly one record (a track observed twice by one camera is refused before), so nothing downstream depends on the order.
+__global__ __launch_bounds__(kBlock) void k_cov_pt_rhs(Dev d, const int* __restrict__ pt_col, int cap, int* __restrict__ counter,
+                                                       int2* __restrict__ rec_id, double* __restrict__ blk) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= d.n_slots) return;
+    const int cam = d.slot_cam[slot];
+    if (cam < 0) return;
+    const int pt = d.slot_pt[slot];
+    const int si = pt_col[pt];
+    if (si < 0) return;
+    const int r = atomicAdd(counter, 1);
+    if (!blk || r >= cap) return;
+    double F[12], E[6], r0, r1;
+    load_FE_rc(d, slot, cam, pt, F, E, r0, r1);
+    const double* Hi = d.Hinv + 6 * (size_t)pt;
+    const double h[6] = {Hi[0], Hi[1], Hi[2], Hi[3], Hi[4], Hi[5]};
+    rec_id[r] = make_int2(si, cam);
+    double* o = blk + 18 * (size_t)r;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const double w0 = F[a] * E[0] + F[6 + a] * E[3], w1 = F[a] * E[1] + F[6 + a] * E[4], w2 = F[a] * E[2] + F[6 + a] * E[5];
+        o[3 * a + 0] = w0 * h[0] + w1 * h[1] + w2 * h[2];
+        o[3 * a + 1] = w0 * h[1] + w1 * h[3] + w2 * h[4];
+        o[3 * a + 2] = w0 * h[2] + w1 * h[4] + w2 * h[5];
+    }
+}
+
+// Records of one chunk into its zero-filled panel slots: ent = {record, panel slot, row of the camera in its tile column, 3 x index
+// of the point in the chunk}; thread = (entry, element of the 6x3 block).  Bt[slot][3 i + b][row + a].
+__global__ __launch_bounds__(256) void k_cov_pt_scatter(const int4* __restrict__ ent, int n_ent, const double* __restrict__ blk, double* __restrict__ Bt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 18 * n_ent) return;
+    const int4 e = ent[i / 18];
+    const int q = i % 18, a = q / 3, b = q % 3;
+    Bt[(size_t)e.y * kCovPanel + (size_t)(e.w + b) * kNB + e.z + a] = blk[18 * (size_t)e.x + q];
+}
+
+// cov_p = D_p (Hinv_p + Y_p^T Y_p) D_p: one wave per point of the chunk (4 points per workgroup), the reached panel slots in
+// elimination order, 64 rows each.  Thread = (entry (a, b), quarter of the 64 rows), the quarters added by two shuffles as in
+// k_cov_gram: one fixed order, (a, b) and (b, a) add the same products in the same order.  D_p = the Jacobi scale of the point.
+__global__ __launch_bounds__(256) void k_cov_pt_gram(Dev d, const double* __restrict__ Zt, int n_slots, const int* __restrict__ sel_pt, int n_chunk,
+                                                     double* __restrict__ cov) {
+    const int pi = blockIdx.x * 4 + (threadIdx.x >> 6), t = threadIdx.x & 63;
+    if (pi >= n_chunk || t >= 36) return;
+    const int e = t >> 2, part = t & 3, a = e / 3, b = e % 3;
+    const double* za = Zt + (size_t)(3 * pi + a) * kNB + part * 16;
+    const double* zb = Zt + (size_t)(3 * pi + b) * kNB + part * 16;
+    double s = 0.0;
+    for (int sl = 0; sl < n_slots; ++sl) {
+        const double* pa = za + (size_t)sl * kCovPanel;
+        const double* pb = zb + (size_t)sl * kCovPanel;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) s = fma(pa[m], pb[m], s);
+    }
+    s += __shfl_xor(s, 1, kWave);
+    s += __shfl_xor(s, 2, kWave);
+    if (part == 0) {
+        const int pt = sel_pt[pi];
+        const int lo = a < b ? a : b, hi = a < b ? b : a;
+        const double hv = d.Hinv[6 * (size_t)pt + (lo == 0 ? hi : lo + hi + 1)];      // upper storage: 00 01 02 11 12 22
+        const double* sp = d.scale_p + 3 * (size_t)pt;
+        cov[9 * (size_t)pi + e] = (hv + s) * (sp[a] * sp[b]);
+    }
+}
+
+// Hinv (6) and the Jacobi scale (3) of selected points, for the fallback's host arithmetic
+__global__ void k_cov_pt_gather(Dev d, const int* __restrict__ sel_pt, int n, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int pt = sel_pt[i];
+    for (int k = 0; k < 6; ++k) out[9 * (size_t)i + k] = d.Hinv[6 * (size_t)pt + k];
+    for (int k = 0; k < 3; ++k) out[9 * (size_t)i + 6 + k] = d.scale_p[3 * (size_t)pt + k];
 }
 
 }  // namespace xba

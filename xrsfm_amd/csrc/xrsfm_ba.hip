@@ -1498,7 +1498,7 @@ int init_scaling_and_linearize(xrsfm_ba_context* c, double huber_a, bool use_sca
     return 0;
 }
 
-// ---------------------------------------------------------------- marginal covariance of selected cameras (ba_cov.h)
+// ---------------------------------------------------------------- marginal covariance of selected cameras and points (ba_cov.h)
 struct DevScratch {          // device memory of one call
     std::vector<void*> p;
     ~DevScratch() { for (void* q : p) (void)hipFree(q); }
@@ -1528,15 +1528,17 @@ static int cov_solution_status(xrsfm_ba_context* c, std::vector<double>& x) {
     return 0;
 }
 
-// Work lists of k_lv_fwd_multi for every chunk of the selection (cameras sorted by elimination position, 10 per chunk)
+// Work lists of k_lv_fwd_multi for every chunk of a selection: the tile columns a chunk reaches are its seed columns (cameras: the
+// tile columns of its cameras; points: those of every camera that observes one of its points) and their ancestors in the elimination tree
 struct CovLists {
     std::vector<int4> ent; std::vector<int2> lj; std::vector<int> sel_row, sel_cam;
     struct Launch { int chunk, ent0, n; };      // one per (chunk, level with reached columns)
     std::vector<Launch> launches;
     std::vector<int> chunk_slots;               // panel slots (reached tile columns) per chunk
+    std::vector<int> slot_of;                   // [chunk][T] panel slot of a tile column, -1 = not reached (keep_slots only)
     int max_slots = 0;
 };
-static void cov_build_lists(const CholHost& h, const std::vector<int>& cams_sorted, CovLists& L) {
+static void cov_build_lists(const CholHost& h, const std::vector<std::vector<int>>& seeds, CovLists& L, bool keep_slots) {
     const int T = h.T, n_lv = h.n_levels;
     // rows[i]: the columns j < i with a structurally non-zero tile (i, j), ascending (the transpose of the backward lists)
     std::vector<std::vector<int>> rows(T);
@@ -1545,16 +1547,9 @@ static void cov_build_lists(const CholHost& h, const std::vector<int>& cams_sort
     for (auto& r : rows) std::sort(r.begin(), r.end());
     std::vector<char> reached(T);
     std::vector<int> slot(T);
-    const int n = (int)cams_sorted.size();
-    for (int c0 = 0, ch = 0; c0 < n; c0 += kCovCamsPerChunk, ++ch) {
-        const int nc = std::min(kCovCamsPerChunk, n - c0);
+    for (int ch = 0; ch < (int)seeds.size(); ++ch) {
         std::fill(reached.begin(), reached.end(), 0);
-        for (int i = 0; i < nc; ++i) {
-            const int cam = cams_sorted[c0 + i];
-            L.sel_cam.push_back(cam); L.sel_row.push_back(h.cam_off_host[cam]);
-            reached[h.cam_off_host[cam] / kNB] = 1;
-        }
-        for (int i = nc; i < kCovCamsPerChunk; ++i) { L.sel_cam.push_back(-1); L.sel_row.push_back(0); }      // (fixed stride per chunk)
+        for (int k : seeds[ch]) reached[k] = 1;
         // a reached column reaches every row tile of its column of L (levels ascend along lv_k)
         for (size_t e = 0; e < h.lv_k_host.size(); ++e)
             if (reached[h.lv_k_host[e]])
@@ -1562,6 +1557,7 @@ static void cov_build_lists(const CholHost& h, const std::vector<int>& cams_sort
         int ns = 0;
         for (int k = 0; k < T; ++k) slot[k] = reached[k] ? ns++ : -1;
         L.chunk_slots.push_back(ns); L.max_slots = std::max(L.max_slots, ns);
+        if (keep_slots) L.slot_of.insert(L.slot_of.end(), slot.begin(), slot.end());
         for (int lv = 0; lv < n_lv; ++lv) {
             const int ent0 = (int)L.ent.size();
             for (int e = h.lv_k_off[lv]; e < h.lv_k_off[lv + 1]; ++e) {
@@ -1576,36 +1572,29 @@ static void cov_build_lists(const CholHost& h, const std::vector<int>& cams_sort
     }
 }
 
-int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) {
-    if (!c) return XRSFM_BA_EINVAL;
-    if (c->poisoned) return XRSFM_BA_ESTATE;
-    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
-    if (n_sel == 0) return XRSFM_BA_OK;
-    if (!cam_sel || !cov) return XRSFM_BA_EINVAL;
+// What the camera and the point call share.  cov_front: set-up of the factorisation, the selection's own test (sel_check, with the
+// constant bits and the activity of the cameras on the host), the linearisation at the current state like the first iteration of a
+// run (Jacobi scaling from the unscaled column norms), the undamped point blocks and the zero damping.
+struct CovFront {
+    std::vector<unsigned char> cc; std::vector<double> act;
+    bool fallback = false;
+    bool dof_const(int cam, int a) const { return (a < 3 ? (cc[cam] & 1u) : (cc[cam] & 2u)) != 0; }
+};
+template <typename Check>
+static int cov_front(xrsfm_ba_context* c, double huber_a, CovFront& f, Check&& sel_check) {
     Dev& d = c->d;
     CholHost& h = c->chol;
     const int Nc = d.n_cams;
-    {
-        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
-        for (int i = 0; i < n_sel; ++i) {
-            const int s = cam_sel[i];
-            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
-            seen[s] = 1;
-        }
-    }
     HIPCHK(hipSetDevice(c->device));
     int e;
     if ((e = chol_setup(c))) return e == kErrDuplicateObs ? XRSFM_BA_EINVAL : e;
-    std::vector<unsigned char> cc((size_t)Nc);
-    std::vector<double> act((size_t)Nc), sc((size_t)Nc * 6);
-    HIPCHK(hipMemcpy(cc.data(), d.cam_const, (size_t)Nc, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(act.data(), d.cam_act, sizeof(double) * (size_t)Nc, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_sel; ++i) if (!(act[cam_sel[i]] > 0.0)) return XRSFM_BA_ESINGULAR;      // no observation: no information
-    // linearise at the current state like the first iteration of a run (Jacobi scaling from the unscaled column norms)
+    f.cc.resize((size_t)Nc); f.act.resize((size_t)Nc);
+    HIPCHK(hipMemcpy(f.cc.data(), d.cam_const, (size_t)Nc, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.act.data(), d.cam_act, sizeof(double) * (size_t)Nc, hipMemcpyDeviceToHost));
+    if ((e = sel_check())) return e;
     if ((e = use_stored_j(c, !jfree_for_run(c, XRSFM_BA_SOLVER_CHOLESKY)))) return e;
     if ((e = init_scaling_and_linearize(c, huber_a, true))) return e;
     if ((e = fetch_scalars(c))) return e;
-    HIPCHK(hipMemcpy(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost));
     DevScratch ds;
     // zero damping, stated as such: the undamped point factors and D_c^2 = 0 in the buffers the S assembly reads when it does not
     // form the damping itself (the XRSFM_BA_PREP_FUSED=0 form of chol_assemble)
@@ -1631,13 +1620,51 @@ int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const in
         return XRSFM_BA_ESINGULAR;
     }
     c->step_radius = 0.0; c->step_prep = false; c->step_valid = false;
-    auto dof_const = [&](int cam, int a) { return (a < 3 ? (cc[cam] & 1u) : (cc[cam] & 2u)) != 0; };
-    std::vector<double> x;
-    std::vector<double> out((size_t)n_sel * 36);      // staged: cov is written only when every value is finite
     const char* fe = std::getenv("XRSFM_BA_COV_FALLBACK");       // (read per call: the A/B oracle of the panel kernel)
     // the panel kernel serves the level schedule (a single tile column is its own level); every other plan: the fallback
-    const bool fallback = (fe && fe[0] != '0') || !(h.use_levels || h.T == 1);
-    if (fallback) {
+    f.fallback = (fe && fe[0] != '0') || !(h.use_levels || h.T == 1);
+    return 0;
+}
+// ... and the undamped S assembled, factored and checked with the run path's factor-and-solve (its right-hand side: whatever
+// h.dev.rhs holds after the assembly, or `rhs` [n_pad] when given).  The factorisation overwrites S: every solve assembles it again.
+static int cov_factor(xrsfm_ba_context* c, std::vector<double>& x, const std::vector<double>* rhs = nullptr) {
+    int e;
+    if ((e = chol_assemble(c, true))) return e;
+    if (rhs) HIPCHK(hipMemcpyAsync(c->chol.dev.rhs, rhs->data(), sizeof(double) * (size_t)c->chol.dev.n_pad, hipMemcpyHostToDevice, c->stream));
+    if ((e = chol_factor_solve(c))) return e;
+    return cov_solution_status(c, x);
+}
+
+int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
+    if (n_sel == 0) return XRSFM_BA_OK;
+    if (!cam_sel || !cov) return XRSFM_BA_EINVAL;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Nc = d.n_cams;
+    {
+        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
+        for (int i = 0; i < n_sel; ++i) {
+            const int s = cam_sel[i];
+            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
+            seen[s] = 1;
+        }
+    }
+    int e;
+    CovFront f;
+    if ((e = cov_front(c, huber_a, f, [&] {
+            for (int i = 0; i < n_sel; ++i) if (!(f.act[cam_sel[i]] > 0.0)) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
+            return 0;
+        }))) return e;
+    std::vector<double> sc((size_t)Nc * 6);
+    HIPCHK(hipMemcpy(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost));
+    DevScratch ds;
+    auto dof_const = [&](int cam, int a) { return f.dof_const(cam, a); };
+    std::vector<double> x;
+    std::vector<double> out((size_t)n_sel * 36);      // staged: cov is written only when every value is finite
+    if (f.fallback) {
         // S x = e_j for the 6 unit vectors of each selected camera with the run path's factor-and-solve; the factorisation
         // overwrites S, so every solve assembles it again.  Rows c of x are column j of block (c, c).
         for (int i = 0; i < n_sel; ++i) {
@@ -1659,15 +1686,24 @@ int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const in
                 }
         }
     } else {
-        if ((e = chol_assemble(c, true))) return e;
-        if ((e = chol_factor_solve(c))) return e;
-        if ((e = cov_solution_status(c, x))) return e;
+        if ((e = cov_factor(c, x))) return e;
         std::vector<int> order((size_t)n_sel), cams_sorted((size_t)n_sel);
         for (int i = 0; i < n_sel; ++i) order[i] = i;
         std::sort(order.begin(), order.end(), [&](int a, int b) { return h.cam_off_host[cam_sel[a]] < h.cam_off_host[cam_sel[b]]; });
         for (int i = 0; i < n_sel; ++i) cams_sorted[i] = cam_sel[order[i]];
         CovLists L;
-        cov_build_lists(h, cams_sorted, L);
+        std::vector<std::vector<int>> seeds;
+        for (int c0 = 0; c0 < n_sel; c0 += kCovCamsPerChunk) {
+            const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
+            seeds.emplace_back();
+            for (int i = 0; i < nc; ++i) {
+                const int cam = cams_sorted[c0 + i];
+                L.sel_cam.push_back(cam); L.sel_row.push_back(h.cam_off_host[cam]);
+                seeds.back().push_back(h.cam_off_host[cam] / kNB);
+            }
+            for (int i = nc; i < kCovCamsPerChunk; ++i) { L.sel_cam.push_back(-1); L.sel_row.push_back(0); }      // (fixed stride per chunk)
+        }
+        cov_build_lists(h, seeds, L, false);
         int4* d_ent = nullptr; int2* d_lj = nullptr; int *d_row = nullptr, *d_cam = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
         if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_cam, L.sel_cam)) ||
             (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n_sel * 36))) return e;
@@ -1675,7 +1711,7 @@ int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const in
         for (int ch = 0, c0 = 0; c0 < n_sel; ++ch, c0 += kCovCamsPerChunk) {
             const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
             for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li)
-                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
+                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<false>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
                        (const int*)(d_row + (size_t)ch * kCovCamsPerChunk), nc);
             LAUNCH(c, K_SMALL, k_cov_gram, dim3(nc), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_cam + (size_t)ch * kCovCamsPerChunk), d_cov + 36 * (size_t)c0);
         }
@@ -1686,6 +1722,155 @@ int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const in
         for (int i = 0; i < n_sel; ++i) memcpy(out.data() + 36 * (size_t)order[i], hc.data() + 36 * (size_t)i, 36 * sizeof(double));
     }
     // (a nearly singular S can pass the factorisation and still overflow in Z^T Z: the caller never sees a NaN or an Inf)
+    for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    memcpy(cov, out.data(), out.size() * sizeof(double));
+    return XRSFM_BA_OK;
+}
+
+// ---------------------------------------------------------------- marginal covariance of selected points (ba_cov.h)
+int point_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
+    if (n_sel == 0) return XRSFM_BA_OK;
+    if (!pt_sel || !cov) return XRSFM_BA_EINVAL;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Np = c->n_points_caller;
+    // caller's point -> packed point (only points with an observation are packed), then -> index in the selection
+    std::vector<int> packed_of((size_t)std::max(Np, 1), -1);
+    {
+        std::vector<char> seen((size_t)std::max(Np, 1), 0);
+        for (int i = 0; i < n_sel; ++i) {
+            const int s = pt_sel[i];
+            if (s < 0 || s >= Np || seen[s]) return XRSFM_BA_EINVAL;
+            seen[s] = 1;
+        }
+        for (size_t j = 0; j < c->pk.pt_orig.size(); ++j) packed_of[c->pk.pt_orig[j]] = (int)j;
+    }
+    int e;
+    CovFront f;
+    if ((e = cov_front(c, huber_a, f, [&] {
+            for (int i = 0; i < n_sel; ++i) if (packed_of[pt_sel[i]] < 0) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
+            return 0;
+        }))) return e;
+    DevScratch ds;
+    std::vector<double> out((size_t)n_sel * 9, 0.0);      // staged: cov is written only when every value is finite
+    // the free points of the selection (a constant point keeps its all-zero block): sel[] = index in pt_sel, by ascending packed index
+    std::vector<int> sel;
+    for (int i = 0; i < n_sel; ++i) if (!c->pk.pt_const[packed_of[pt_sel[i]]]) sel.push_back(i);
+    std::sort(sel.begin(), sel.end(), [&](int a, int b) { return packed_of[pt_sel[a]] < packed_of[pt_sel[b]]; });
+    const int n = (int)sel.size();
+    if (n == 0) { memcpy(cov, out.data(), out.size() * sizeof(double)); return XRSFM_BA_OK; }
+    // records {index in sel[], camera} + F_c^T E_p Hinv_p of every observation of a selected point: count, size, build
+    std::vector<int> pt_col((size_t)d.n_pts, -1), sel_pt((size_t)n);
+    for (int i = 0; i < n; ++i) { sel_pt[i] = packed_of[pt_sel[sel[i]]]; pt_col[sel_pt[i]] = i; }
+    int *d_col = nullptr, *d_cnt = nullptr; int2* d_rec = nullptr; double* d_blk = nullptr;
+    if ((e = ds.put(&d_col, pt_col)) || (e = ds.get(&d_cnt, 1))) return e;
+    int n_rec = 0;
+    const int nbs = cdiv(d.n_slots, kBlock);
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
+    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, 0, d_cnt, (int2*)nullptr, (double*)nullptr);
+    HIPCHK(hipMemcpyAsync(&n_rec, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((e = ds.get(&d_rec, (size_t)n_rec)) || (e = ds.get(&d_blk, (size_t)n_rec * 18))) return e;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
+    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, n_rec, d_cnt, d_rec, d_blk);
+    std::vector<int2> rec((size_t)n_rec);
+    if (n_rec > 0) HIPCHK(hipMemcpyAsync(rec.data(), d_rec, sizeof(int2) * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // records by point (and camera: a fixed order, whatever tickets the lanes drew)
+    std::vector<int> ro((size_t)n_rec);
+    for (int r = 0; r < n_rec; ++r) ro[r] = r;
+    std::sort(ro.begin(), ro.end(), [&](int a, int b) { return rec[a].x != rec[b].x ? rec[a].x < rec[b].x : rec[a].y < rec[b].y; });
+    std::vector<int> rptr((size_t)n + 1, 0);
+    for (int r = 0; r < n_rec; ++r) rptr[rec[r].x + 1]++;
+    for (int i = 0; i < n; ++i) rptr[i + 1] += rptr[i];
+    int* d_selpt = nullptr;
+    std::vector<double> x;
+    if (f.fallback) {
+        // per point and column b: S x_b = w_b (column b of W_p Hinv_p) with the run path's factor-and-solve, Sigma_ab = Hinv_ab + w_a^T x_b
+        std::vector<double> blk((size_t)n_rec * 18), hs((size_t)n * 9), rhs((size_t)h.dev.n_pad);
+        double* d_hs = nullptr;
+        if ((e = ds.put(&d_selpt, sel_pt)) || (e = ds.get(&d_hs, (size_t)n * 9))) return e;
+        LAUNCH(c, K_SMALL, k_cov_pt_gather, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, d, (const int*)d_selpt, n, d_hs);
+        if (n_rec > 0) HIPCHK(hipMemcpyAsync(blk.data(), d_blk, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        static const int up[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+        for (int i = 0; i < n; ++i) {
+            double M[3][3];
+            bool any = false;       // a point seen by constant cameras only: W_p = 0, nothing to solve
+            for (int q = rptr[i]; q < rptr[i + 1]; ++q) any = any || !(f.dof_const(rec[ro[q]].y, 0) && f.dof_const(rec[ro[q]].y, 3));
+            for (int b = 0; b < 3; ++b) {
+                if (any) {
+                    std::fill(rhs.begin(), rhs.end(), 0.0);
+                    for (int q = rptr[i]; q < rptr[i + 1]; ++q)
+                        for (int a = 0; a < 6; ++a) rhs[h.cam_off_host[rec[ro[q]].y] + a] = blk[18 * (size_t)ro[q] + 3 * a + b];
+                    if ((e = cov_factor(c, x, &rhs))) return e;
+                }
+                for (int a = 0; a < 3; ++a) {
+                    double s = 0.0;
+                    if (any)
+                        for (int q = rptr[i]; q < rptr[i + 1]; ++q)
+                            for (int r = 0; r < 6; ++r) s += blk[18 * (size_t)ro[q] + 3 * r + a] * x[6 * (size_t)rec[ro[q]].y + r];
+                    M[a][b] = hs[9 * (size_t)i + up[a][b]] + s;
+                }
+            }
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) out[9 * (size_t)sel[i] + 3 * a + b] = 0.5 * (M[a][b] + M[b][a]) * (hs[9 * (size_t)i + 6 + a] * hs[9 * (size_t)i + 6 + b]);
+        }
+    } else {
+        if ((e = cov_factor(c, x))) return e;
+        // chunks of 21 points whose cameras are close in elimination order: by the smallest tile column of a point's observers
+        // (then by packed index: the order of pt_sel has no say; chunking affects no value — ba_cov.h)
+        auto col_of = [&](int cam) { return h.cam_off_host[cam] / kNB; };
+        std::vector<int> kmin((size_t)n, h.T), po((size_t)n);
+        for (int r = 0; r < n_rec; ++r) kmin[rec[r].x] = std::min(kmin[rec[r].x], col_of(rec[r].y));
+        for (int i = 0; i < n; ++i) po[i] = i;
+        std::sort(po.begin(), po.end(), [&](int a, int b) { return kmin[a] != kmin[b] ? kmin[a] < kmin[b] : a < b; });
+        const int n_ch = cdiv(n, kCovPtsPerChunk);
+        std::vector<std::vector<int>> seeds((size_t)n_ch);
+        std::vector<int> chunk_pt((size_t)n_ch * kCovPtsPerChunk, 0);
+        for (int j = 0; j < n; ++j) {
+            const int i = po[j], ch = j / kCovPtsPerChunk;
+            chunk_pt[j] = sel_pt[i];
+            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
+                const int cam = rec[ro[q]].y;
+                if (!(f.dof_const(cam, 0) && f.dof_const(cam, 3))) seeds[ch].push_back(col_of(cam));      // (an all-constant camera: zero rows of W_p)
+            }
+        }
+        CovLists L;
+        cov_build_lists(h, seeds, L, true);
+        std::vector<int4> sc_ent; std::vector<int> sc_off((size_t)n_ch + 1, 0);
+        for (int j = 0; j < n; ++j) {
+            const int i = po[j], ch = j / kCovPtsPerChunk;
+            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
+                const int cam = rec[ro[q]].y, row = h.cam_off_host[cam];
+                const int sl = L.slot_of[(size_t)ch * h.T + row / kNB];
+                if (sl >= 0) sc_ent.push_back(make_int4(ro[q], sl, row % kNB, 3 * (j % kCovPtsPerChunk)));
+            }
+            sc_off[ch + 1] = (int)sc_ent.size();
+        }
+        int4 *d_ent = nullptr, *d_sc = nullptr; int2* d_lj = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, sc_ent)) || (e = ds.put(&d_selpt, chunk_pt)) ||
+            (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n * 9))) return e;
+        size_t li = 0;
+        for (int ch = 0, p0 = 0; ch < n_ch; ++ch, p0 += kCovPtsPerChunk) {
+            const int np = std::min(kCovPtsPerChunk, n - p0), ne = sc_off[ch + 1] - sc_off[ch];
+            if (L.chunk_slots[ch] > 0) HIPCHK(hipMemsetAsync(d_Z, 0, sizeof(double) * (size_t)L.chunk_slots[ch] * kCovPanel, c->stream));
+            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + sc_off[ch]), ne, (const double*)d_blk, d_Z);
+            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li)
+                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<true>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
+                       (const int*)nullptr, 0);
+            LAUNCH(c, K_SMALL, k_cov_pt_gram, dim3(cdiv(np, 4)), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_selpt + p0), np, d_cov + 9 * (size_t)p0);
+        }
+        HIPCHK(hipGetLastError());
+        std::vector<double> hc((size_t)n * 9);
+        HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int j = 0; j < n; ++j) memcpy(out.data() + 9 * (size_t)sel[po[j]], hc.data() + 9 * (size_t)j, 9 * sizeof(double));
+    }
     for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
     memcpy(cov, out.data(), out.size() * sizeof(double));
     return XRSFM_BA_OK;
@@ -3178,5 +3363,6 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 // ---------------------------------------------------------------- exception barrier of the entry points that allocate on the host
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
 int xrsfm_ba_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) { return no_throw([&] { return covariance_impl(c, huber_a, n_sel, cam_sel, cov); }); }
+int xrsfm_ba_point_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) { return no_throw([&] { return point_covariance_impl(c, huber_a, n_sel, pt_sel, cov); }); }
 int xrsfm_pg_solve(const xrsfm_pg_options* opt, xrsfm_pg_problem* p, xrsfm_pg_summary* summary) { return no_throw([&] { return pg_solve_impl(opt, p, summary); }); }
 int xrsfm_tag_refine(const xrsfm_pg_options* opt, xrsfm_tag_problem* p, int32_t stages, xrsfm_pg_summary* summaries) { return no_throw([&] { return tag_refine_impl(opt, p, stages, summaries); }); }
