@@ -209,7 +209,8 @@ int xrsfm_ba_download_intrinsics(xrsfm_ba_context *ctx, double *intr_params);
  * (a nearly singular S whose Z^T Z overflows).  The result is staged and checked before it is copied: on every error code cov is
  * left UNTOUCHED, it never receives a NaN or an Inf.  A singular point block is named on stderr (how many, and the first one's
  * index).  n_sel == 0 is success and touches nothing.
- * Not built: camera-camera cross blocks, bal9, several ranks, a PCG variant. */
+ * Cross blocks between cameras (and between cameras and points): xrsfm_ba_joint_covariance.  Not built: bal9, several ranks, a PCG
+ * variant. */
 int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *cam_sel, double *cov);
 
 /* Marginal covariance of selected 3-D points at the CURRENT device state: block (p,p) of (J^T J)^-1 with the conventions of
@@ -237,9 +238,47 @@ int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, co
  * it is not part of it), ANY free point's undamped 3x3 block is singular (named on stderr like the camera call does), the solution
  * of the factored system is not finite, or a block would hold a NaN / Inf.  The result is staged: on every error code cov is left
  * UNTOUCHED.  n_sel == 0 is success and touches nothing.
- * Not built: the covariance of ALL points by selected inversion, camera-camera and camera-point cross blocks, bal9, several ranks,
- * a PCG variant. */
+ * Cross blocks between points (and between cameras and points): xrsfm_ba_joint_covariance.  Not built: the covariance of ALL points
+ * by selected inversion, bal9, several ranks, a PCG variant. */
 int xrsfm_ba_point_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *pt_sel, double *cov);
+
+/* Joint covariance of selected cameras AND points with every cross block: the sub-matrix of (J^T J)^-1 on the selected parameter
+ * blocks, in the conventions of the two calls above (robustified J with Huber huber_a, tangent space of the cameras, UNSCALED
+ * coordinates, no damping, no sigma^2 factor, current device state): what ceres::Covariance::Compute with every pair of the selected
+ * blocks followed by GetCovarianceBlock[InTangentSpace] returns.  cov is [N][N] row-major, N = 6 n_cam_sel + 3 n_pt_sel: the
+ * cameras first, in the order of cam_sel (rotation 3, translation 3), then the points in the order of pt_sel (the caller's point
+ * indices).  Rows and columns of constant degrees of freedom (XRSFM_BA_CONST_Q / _T, point_const) are exact zeros; a point whose
+ * observing cameras are all constant has exact zero cross blocks and the diagonal block D_p Hinv_p D_p.  The result is exactly
+ * symmetric (cov[i][j] == cov[j][i] bit for bit).  Does not change the state or the trust region of a later run.
+ *
+ * How: the front half of the two calls above, once.  In its Jacobi-scaled coordinates, with S = L L^T undamped,
+ *     X_c = L^-1 E_c (the 6 unit columns of a camera),   X_p = L^-1 (W_p Hinv_p) (the 3 columns of the point call),
+ *     Sigma_cc' = X_c^T X_c',   Sigma_cp = -X_c^T X_p,   Sigma_pp' = delta_pp' Hinv_p + X_p^T X_p',
+ * each entry times the Jacobi scales of its row and of its column: forward substitutions only.  The selection is cut into 64-column
+ * chunks (10 cameras, or 21 free points), every chunk runs the level-scheduled forward substitution of the calls above into panel
+ * storage of its own, and one workgroup per chunk pair forms the Gram between the two panels on the FP64 matrix cores, one 64x64x64
+ * product per tile column both chunks reach, in ascending elimination order (xrsfm_amd/csrc/ba_cov.h: k_cov_joint_gram); an
+ * epilogue applies signs, Hinv_p and scales, writes the upper triangle in the caller's order and copies it into the lower.  An
+ * entry depends on its two columns only: on the kernel path it is bit-identical whatever else is selected and in whatever order,
+ * and two calls agree bit for bit.  Panel / look-ahead panel plans and XRSFM_BA_COV_FALLBACK=1 (read per call) take the slow exact
+ * fallback: one factor-and-solve S x = rhs per free selected column (N factorisations), the entries assembled from the rows of x
+ * with the same signs and scales, symmetrised.
+ *
+ * Size: N <= XRSFM_BA_JOINT_COV_MAX_COLS.  Device scratch of one call: 32 KiB per chunk and reached tile column for the panels plus
+ * 32 KiB per chunk pair and 8 N^2 bytes for the result.  At the cap (18 chunks at most, 171 pairs) on bench config L (112 tile
+ * columns) that is at most 63 MiB + 5.4 MiB + 8 MiB whatever the selection reaches; XRSFM_BA_ENOMEM if the device cannot give it.
+ *
+ * Errors: XRSFM_BA_EINVAL — NULL context, an index out of range, a duplicate within cam_sel or within pt_sel, a negative count, a
+ * NULL selection with a positive count, NULL cov with N > 0, N above the cap, bal9 context, multi-rank context (communicator or
+ * test hook), a track observed twice by one camera; XRSFM_BA_ETOOBIG exactly where XRSFM_BA_SOLVER_CHOLESKY returns it;
+ * XRSFM_BA_ESINGULAR — a selected camera has no observation, a selected point has no observation in the program, ANY free point's
+ * undamped 3x3 block is singular (named on stderr like the calls above), the solution of the factored system is not finite, or the
+ * result would hold a NaN / Inf.  The result is staged and checked: on every error code cov is left UNTOUCHED.  N == 0 is success
+ * and touches nothing; either count may be zero on its own.
+ * Not built: the covariance of ALL points by selected inversion, bal9, several ranks, a PCG variant, a kernel path on panel plans. */
+#define XRSFM_BA_JOINT_COV_MAX_COLS 1024
+int xrsfm_ba_joint_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_cam_sel, const int32_t *cam_sel, int32_t n_pt_sel,
+                              const int32_t *pt_sel, double *cov);
 
 void xrsfm_ba_destroy(xrsfm_ba_context *ctx);
 

@@ -2,10 +2,15 @@
 100 and all 1000 cameras, next to the time of one LM iteration of the same context; one table.  Then the same for
 xrsfm_ba_point_covariance: 1, 21, 210 and 2100 points (1, 1, 10 and 100 chunks of 21) spread over the ring, the 21-point fallback,
 and the ratio of every point row to the camera row with the same number of chunks (1, 10, 100, 1000 cameras are 1, 1, 10, 100
-chunks of 10).  Host clock around blocking calls (every call ends in a device synchronise); the first call of each size is a
+chunks of 10).  Then xrsfm_ba_joint_covariance: 2 cameras; 10 cameras + 21 points; 64 cameras + 85 points (spread over the ring),
+the fallback at the smallest size, each next to the sum of the two marginal calls on the same selections.  --joint-only times
+nothing but the joint rows (--joint-size picks one) and prints the number of joint calls made on the kernel path: under
+`rocprofv3 --kernel-trace --stats` that gives the device time of k_cov_joint_gram per call, and --gram-us (one value per joint
+size) puts it into the table as a share of the call.  Host clock around blocking calls (every call ends in a device synchronise); the first call of each size is a
 warm-up and is not counted.
 
     python tools/cov_timing.py [--config L] [--repeat 5] [--fallback-cams 10] [--fallback-points 21]
+    python tools/cov_timing.py --joint-only [--joint-size 0|1|2] [--gram-us A,B,C]
 """
 import argparse
 import os
@@ -25,6 +30,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--fallback-cams", type=int, default=10, help="also time the fallback path for this many cameras (0: skip)")
     ap.add_argument("--fallback-points", type=int, default=21, help="also time the point fallback for this many points (0: skip)")
+    ap.add_argument("--joint-only", action="store_true", help="time the joint rows only")
+    ap.add_argument("--joint-size", type=int, default=-1, help="with --joint-only: only this one of the three joint sizes (and no fallback)")
+    ap.add_argument("--gram-us", default="", help="device time of k_cov_joint_gram per call (us, from rocprofv3), one per joint size, comma separated")
     args = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("cov_timing: no HIP device")
@@ -44,14 +52,14 @@ def main():
     ctx.reset()                                    # the covariance is timed at the uploaded state
     rng = np.random.default_rng(0)
     rows = []
-    for m in (1, 10, 100, n):
+    for m in (() if args.joint_only else (1, 10, 100, n)):
         sel = np.sort(rng.choice(n, m, replace=False)) if m < n else np.arange(n)
         ctx.covariance(sel)
         ts = []
         for _ in range(args.repeat):
             t0 = time.perf_counter(); ctx.covariance(sel); ts.append(time.perf_counter() - t0)
         rows.append((f"{m} cameras", min(ts), float(np.median(ts))))
-    if args.fallback_cams > 0:
+    if args.fallback_cams > 0 and not args.joint_only:
         sel = np.sort(rng.choice(n, args.fallback_cams, replace=False))
         os.environ["XRSFM_BA_COV_FALLBACK"] = "1"
         try:
@@ -73,14 +81,14 @@ def main():
         return by_cam[np.linspace(0, by_cam.shape[0] - 1, m).astype(int)].astype(np.int32)
 
     prow = []
-    for m in (1, 21, 210, 2100):
+    for m in (() if args.joint_only else (1, 21, 210, 2100)):
         sel = spread(m)
         ctx.point_covariance(sel)
         ts = []
         for _ in range(args.repeat):
             t0 = time.perf_counter(); ctx.point_covariance(sel); ts.append(time.perf_counter() - t0)
         prow.append((f"{m} points", min(ts), float(np.median(ts)), -(-m // 21)))
-    if args.fallback_points > 0:
+    if args.fallback_points > 0 and not args.joint_only:
         sel = spread(args.fallback_points)
         os.environ["XRSFM_BA_COV_FALLBACK"] = "1"
         try:
@@ -91,6 +99,32 @@ def main():
         finally:
             del os.environ["XRSFM_BA_COV_FALLBACK"]
         prow.append((f"{args.fallback_points} points, fallback", min(ts), float(np.median(ts)), None))
+    # joint call: cameras spread over the ring past the two frames of the gauge, points spread as above
+    def timed(f):
+        f()
+        ts = []
+        for _ in range(args.repeat):
+            t0 = time.perf_counter(); f(); ts.append(time.perf_counter() - t0)
+        return min(ts), float(np.median(ts))
+
+    sizes = [(2, 0), (10, 21), (64, 85)]
+    gram_us = [float(v) for v in args.gram_us.split(",")] if args.gram_us else []
+    jrow, n_joint_calls = [], 0
+    for i, (mc, mp) in enumerate(sizes):
+        if args.joint_only and args.joint_size >= 0 and i != args.joint_size:
+            continue
+        cs, ps = np.linspace(2, n - 1, mc).astype(np.int32), spread(mp) if mp else np.zeros(0, np.int32)
+        tj = timed(lambda: ctx.joint_covariance(cs, ps))
+        n_joint_calls += args.repeat + 1
+        tm = timed(lambda: (ctx.covariance(cs), ctx.point_covariance(ps)))
+        jrow.append((f"{mc} cameras + {mp} points (N = {6 * mc + 3 * mp})", tj, tm, gram_us[i] if i < len(gram_us) else None))
+        if i == 0 and args.joint_size < 0:
+            os.environ["XRSFM_BA_COV_FALLBACK"] = "1"
+            try:
+                tf = timed(lambda: ctx.joint_covariance(cs, ps))
+            finally:
+                del os.environ["XRSFM_BA_COV_FALLBACK"]
+            jrow.append((f"{mc} cameras + {mp} points, fallback", tf, None, None))
     ctx.close()
     print(f"config {args.config}: {n} cameras, {arr['points'].shape[0]} points, {arr['obs_cam'].shape[0]} observations; "
           f"{plan['tiles']} tile columns on {plan['levels']} levels, schedule {plan['facts']['schedule']}, packed {plan['facts']['packed']}")
@@ -107,6 +141,15 @@ def main():
     for name, tmin, tmed, chunks in prow:
         ratio = f"{tmed / cam_by_chunks[chunks]:.2f} ({chunks} chunk{'s' if chunks > 1 else ''})" if chunks in cam_by_chunks else "-"
         print(f"| point covariance, {name} | {1e3 * tmin:.3f} | {1e3 * tmed:.3f} | {1e3 * tmed / lm_ms:.1f} | {ratio} |")
+    print()
+    if args.joint_only:
+        print(f"joint calls on the kernel path: {n_joint_calls}")
+    print(f"| call | min ms | median ms | x one LM iteration | covariance + point_covariance, same selections: median ms | k_cov_joint_gram per call: us (share) |")
+    print(f"|---|---|---|---|---|---|")
+    for name, (tmin, tmed), tm, g in jrow:
+        both = f"{1e3 * tm[1]:.3f}" if tm else "-"
+        share = f"{g:.1f} ({100.0 * g * 1e-6 / tmed:.1f} %)" if g is not None else "-"
+        print(f"| joint covariance, {name} | {1e3 * tmin:.3f} | {1e3 * tmed:.3f} | {1e3 * tmed / lm_ms:.1f} | {both} | {share} |")
 
 
 if __name__ == "__main__":

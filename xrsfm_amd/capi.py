@@ -90,7 +90,7 @@ EXPORTS = [
     "xrsfm_ba_debug_cholesky_solve", "xrsfm_ba_debug_set_block_pattern", "xrsfm_ba_debug_pack", "xrsfm_ba_debug_chol_plan", "xrsfm_ba_refine_pose", "xrsfm_ba_refine_pose_options", "xrsfm_ba_debug_comm_hook", "xrsfm_pg_default_options", "xrsfm_pg_solve", "xrsfm_ba_debug_pack_gram", "xrsfm_ba_debug_gram_schedule",
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
-    "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance",
+    "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -192,6 +192,8 @@ def load(path: str | None = None):
     lib.xrsfm_ba_covariance.restype = C.c_int
     lib.xrsfm_ba_point_covariance.argtypes = [vp, C.c_double, C.c_int32, _c_int32_p, _c_double_p]
     lib.xrsfm_ba_point_covariance.restype = C.c_int
+    lib.xrsfm_ba_joint_covariance.argtypes = [vp, C.c_double, C.c_int32, _c_int32_p, C.c_int32, _c_int32_p, _c_double_p]
+    lib.xrsfm_ba_joint_covariance.restype = C.c_int
     _lib = lib
     return lib
 
@@ -353,6 +355,18 @@ class Context:
         sel = np.ascontiguousarray(points, np.int32).reshape(-1)
         cov = np.zeros((sel.shape[0], 3, 3))
         check(self.lib.xrsfm_ba_point_covariance(self._h, huber_a, sel.shape[0], sel.ctypes.data_as(_c_int32_p), _dp(cov)), "xrsfm_ba_point_covariance")
+        return cov
+
+    def joint_covariance(self, cams, points, huber_a: float = 5.99) -> np.ndarray:
+        """Joint covariance [N][N], N = 6 len(cams) + 3 len(points), of the cameras `cams` (first, 6 tangent rows each) and the 3-D
+        points `points` (the caller's indices) with every cross block, at the current device state: xrsfm_ba_joint_covariance.
+        Raises RuntimeError naming the code (EINVAL, ETOOBIG, ESINGULAR, ENOMEM) on failure."""
+        cs = np.ascontiguousarray(cams, np.int32).reshape(-1)
+        ps = np.ascontiguousarray(points, np.int32).reshape(-1)
+        n = 6 * cs.shape[0] + 3 * ps.shape[0]
+        cov = np.zeros((n, n))
+        check(self.lib.xrsfm_ba_joint_covariance(self._h, huber_a, cs.shape[0], cs.ctypes.data_as(_c_int32_p), ps.shape[0], ps.ctypes.data_as(_c_int32_p), _dp(cov)),
+              "xrsfm_ba_joint_covariance")
         return cov
 
     def debug_linearize(self, huber_a: float = 5.99, use_scaling: bool = False):

@@ -281,4 +281,97 @@ __global__ void k_cov_pt_gather(Dev d, const int* __restrict__ sel_pt, int n, do
     for (int k = 0; k < 3; ++k) out[9 * (size_t)i + 6 + k] = d.scale_p[3 * (size_t)pt + k];
 }
 
+// ---------------------------------------------------------------- joint covariance with cross blocks (xrsfm_ba_joint_covariance)
+// Every chunk of the selection (10 cameras with unit injection, 21 free points with the scattered right-hand side) keeps panel
+// slots of its own, so that after the forward substitutions the panels X = L^-1 [E_c .. | W_p Hinv_p ..] of ALL chunks are resident.
+// In the scaled coordinates of the front half
+//     Sigma_cc' = X_c^T X_c',    Sigma_cp = -X_c^T X_p,    Sigma_pp' = delta_pp' Hinv_p + X_p^T X_p':
+// the Gram between the panels of two chunks, one 64x64x64 FP64 A B^T product per tile column both chunks reach.
+constexpr int kCovJointMaxCols = XRSFM_BA_JOINT_COV_MAX_COLS;      // columns of one joint call (include/xrsfm_ba.h states the memory this bounds)
+
+// One workgroup per chunk pair (A <= B): G_AB = sum_k Zt_A[k] Zt_B[k]^T over the tile columns k both chunks reach.
+//   ent  [pair] = {q0, q1}: its list slots[q0 .. q1)
+//   slots [q]   = {panel slot of k in A, panel slot of k in B}, k ascending (elimination order)
+// A panel column is a row of the A or of the B operand, an element of an MFMA result depends on its own row of A and of B only, and
+// a slot holds exact zeros in the panel columns that do not reach its tile column: a product with such a slot adds exact zeros.  So
+// an entry depends on its two columns only, not on what shares their chunks, and the sum over k is not split: one workgroup adds
+// the tile columns in ascending order whatever the chunks reach.  Staging as in k_lv_fwd_multi: two 64 x 66 operand tiles in LDS
+// (66 KiB: two workgroups per compute unit), the next operands in registers while the matrix cores work on the current ones.
+__global__ __launch_bounds__(256) void k_cov_joint_gram(const int2* __restrict__ ent, const int2* __restrict__ slots, const double* __restrict__ Zt,
+                                                        double* __restrict__ G) {
+    __shared__ __attribute__((aligned(16))) double As[kNB * kLdT];
+    __shared__ __attribute__((aligned(16))) double Bs[kNB * kLdT];
+    const int2 en = ent[blockIdx.x];
+    const int q0 = en.x, q1 = en.y;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = (wave >> 1) * 32, c0 = (wave & 1) * 32;
+    v4d acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) acc[m][n2] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double2 ra[8], rb[8];
+    if (q0 < q1) {
+        const int2 e = slots[q0];
+        load_tile_regs(ra, Zt + (size_t)e.x * kCovPanel, kNB);
+        load_tile_regs(rb, Zt + (size_t)e.y * kCovPanel, kNB);
+    }
+    for (int q = q0; q < q1; ++q) {
+        __syncthreads();                       // the previous product no longer reads LDS
+        store_tile_lds(As, ra);
+        store_tile_lds(Bs, rb);
+        __syncthreads();
+        if (q + 1 < q1) {
+            const int2 e = slots[q + 1];
+            load_tile_regs(ra, Zt + (size_t)e.x * kCovPanel, kNB);
+            load_tile_regs(rb, Zt + (size_t)e.y * kCovPanel, kNB);
+        }
+        tile_abt_mfma(As, Bs, acc);            // += Zt_A[k] Zt_B[k]^T
+    }
+    double* out = G + (size_t)blockIdx.x * kCovPanel;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) out[(r0 + 16 * m + lk + 4 * g) * kNB + c0 + 16 * n2 + li] = acc[m][n2][g];
+}
+
+// The N x N result in the caller's order from the chunk-pair Grams.  col [i] = {panel column of row / column i (64 x chunk + column
+// in the chunk, chunks in the order of the pairs; -1: a constant point), camera or packed point, degree of freedom in its block,
+// 0 camera / 1 point}.  Thread = one entry (i <= j) of the upper triangle: it reads the entry of the pair (the earlier panel column
+// is the row: one location whatever the caller's order), negates camera-point entries, adds Hinv_p on a point's own block,
+// applies the two Jacobi scales (0 on constant degrees of freedom: exact zeros) and writes (i, j) and its mirror image (j, i).
+__global__ __launch_bounds__(256) void k_cov_joint_finish(Dev d, const int4* __restrict__ col, int N, int n_chunks, const double* __restrict__ G,
+                                                          double* __restrict__ cov) {
+    const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (long long)N * N) return;
+    const int i = (int)(id / N), j = (int)(id % N);
+    if (i > j) return;
+    const int4 ci = col[i], cj = col[j];
+    auto scale = [&](const int4& cl) {
+        if (cl.x < 0) return 0.0;
+        if (cl.w) return d.scale_p[3 * (size_t)cl.y + cl.z];
+        const unsigned cc = d.cam_const[cl.y];
+        return (cl.z < 3 ? (cc & 1u) : (cc & 2u)) ? 0.0 : d.scale_c[6 * (size_t)cl.y + cl.z];
+    };
+    const double di = scale(ci), dj = scale(cj);
+    double v = 0.0;
+    if (di != 0.0 && dj != 0.0) {
+        const int lo = ci.x < cj.x ? ci.x : cj.x, hi = ci.x < cj.x ? cj.x : ci.x;
+        const int A = lo >> 6, B = hi >> 6;
+        const size_t pair = (size_t)A * n_chunks - (size_t)A * (A - 1) / 2 + (B - A);      // pairs (A, B >= A) row by row
+        double s = G[pair * kCovPanel + (size_t)(lo & 63) * kNB + (hi & 63)];
+        if (ci.w != cj.w) s = -s;
+        else if (ci.w && ci.y == cj.y) {
+            const int a = ci.z < cj.z ? ci.z : cj.z, b = ci.z < cj.z ? cj.z : ci.z;
+            s = d.Hinv[6 * (size_t)ci.y + (a == 0 ? b : a + b + 1)] + s;      // upper storage: 00 01 02 11 12 22
+        }
+        v = s * (di * dj);
+    }
+    cov[(size_t)i * N + j] = v;
+    cov[(size_t)j * N + i] = v;
+}
+
 }  // namespace xba

@@ -1727,6 +1727,45 @@ int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const in
     return XRSFM_BA_OK;
 }
 
+// Records {index in sel_pt[], camera} + F_c^T E_p Hinv_p of every observation of the selected free points (sel_pt: packed indices;
+// k_cov_pt_rhs: count, size, build), and their order by point and camera: ro[rptr[i] .. rptr[i + 1]) are the records of point i.
+struct CovPtRecords {
+    int n_rec = 0; double* d_blk = nullptr;
+    std::vector<int2> rec; std::vector<int> ro, rptr;
+};
+static int cov_point_records(xrsfm_ba_context* c, DevScratch& ds, const std::vector<int>& sel_pt, CovPtRecords& R) {
+    Dev& d = c->d;
+    const int n = (int)sel_pt.size();
+    int e;
+    std::vector<int> pt_col((size_t)d.n_pts, -1);
+    for (int i = 0; i < n; ++i) pt_col[sel_pt[i]] = i;
+    int *d_col = nullptr, *d_cnt = nullptr; int2* d_rec = nullptr; double* d_blk = nullptr;
+    if ((e = ds.put(&d_col, pt_col)) || (e = ds.get(&d_cnt, 1))) return e;
+    int n_rec = 0;
+    const int nbs = cdiv(d.n_slots, kBlock);
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
+    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, 0, d_cnt, (int2*)nullptr, (double*)nullptr);
+    HIPCHK(hipMemcpyAsync(&n_rec, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((e = ds.get(&d_rec, (size_t)n_rec)) || (e = ds.get(&d_blk, (size_t)n_rec * 18))) return e;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
+    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, n_rec, d_cnt, d_rec, d_blk);
+    std::vector<int2>& rec = R.rec;
+    rec.resize((size_t)n_rec);
+    if (n_rec > 0) HIPCHK(hipMemcpyAsync(rec.data(), d_rec, sizeof(int2) * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // records by point (and camera: a fixed order, whatever tickets the lanes drew)
+    std::vector<int>& ro = R.ro;
+    ro.resize((size_t)n_rec);
+    for (int r = 0; r < n_rec; ++r) ro[r] = r;
+    std::sort(ro.begin(), ro.end(), [&](int a, int b) { return rec[a].x != rec[b].x ? rec[a].x < rec[b].x : rec[a].y < rec[b].y; });
+    R.rptr.assign((size_t)n + 1, 0);
+    for (int r = 0; r < n_rec; ++r) R.rptr[rec[r].x + 1]++;
+    for (int i = 0; i < n; ++i) R.rptr[i + 1] += R.rptr[i];
+    R.n_rec = n_rec; R.d_blk = d_blk;
+    return 0;
+}
+
 // ---------------------------------------------------------------- marginal covariance of selected points (ba_cov.h)
 int point_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) {
     if (!c) return XRSFM_BA_EINVAL;
@@ -1762,30 +1801,15 @@ int point_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, co
     std::sort(sel.begin(), sel.end(), [&](int a, int b) { return packed_of[pt_sel[a]] < packed_of[pt_sel[b]]; });
     const int n = (int)sel.size();
     if (n == 0) { memcpy(cov, out.data(), out.size() * sizeof(double)); return XRSFM_BA_OK; }
-    // records {index in sel[], camera} + F_c^T E_p Hinv_p of every observation of a selected point: count, size, build
-    std::vector<int> pt_col((size_t)d.n_pts, -1), sel_pt((size_t)n);
-    for (int i = 0; i < n; ++i) { sel_pt[i] = packed_of[pt_sel[sel[i]]]; pt_col[sel_pt[i]] = i; }
-    int *d_col = nullptr, *d_cnt = nullptr; int2* d_rec = nullptr; double* d_blk = nullptr;
-    if ((e = ds.put(&d_col, pt_col)) || (e = ds.get(&d_cnt, 1))) return e;
-    int n_rec = 0;
-    const int nbs = cdiv(d.n_slots, kBlock);
-    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
-    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, 0, d_cnt, (int2*)nullptr, (double*)nullptr);
-    HIPCHK(hipMemcpyAsync(&n_rec, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if ((e = ds.get(&d_rec, (size_t)n_rec)) || (e = ds.get(&d_blk, (size_t)n_rec * 18))) return e;
-    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int), c->stream));
-    LAUNCH(c, K_SMALL, k_cov_pt_rhs, dim3(nbs), dim3(kBlock), 0, d, (const int*)d_col, n_rec, d_cnt, d_rec, d_blk);
-    std::vector<int2> rec((size_t)n_rec);
-    if (n_rec > 0) HIPCHK(hipMemcpyAsync(rec.data(), d_rec, sizeof(int2) * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    // records by point (and camera: a fixed order, whatever tickets the lanes drew)
-    std::vector<int> ro((size_t)n_rec);
-    for (int r = 0; r < n_rec; ++r) ro[r] = r;
-    std::sort(ro.begin(), ro.end(), [&](int a, int b) { return rec[a].x != rec[b].x ? rec[a].x < rec[b].x : rec[a].y < rec[b].y; });
-    std::vector<int> rptr((size_t)n + 1, 0);
-    for (int r = 0; r < n_rec; ++r) rptr[rec[r].x + 1]++;
-    for (int i = 0; i < n; ++i) rptr[i + 1] += rptr[i];
+    std::vector<int> sel_pt((size_t)n);
+    for (int i = 0; i < n; ++i) sel_pt[i] = packed_of[pt_sel[sel[i]]];
+    CovPtRecords R;
+    if ((e = cov_point_records(c, ds, sel_pt, R))) return e;
+    const int n_rec = R.n_rec;
+    double* const d_blk = R.d_blk;
+    const std::vector<int2>& rec = R.rec;
+    const std::vector<int>& ro = R.ro;
+    const std::vector<int>& rptr = R.rptr;
     int* d_selpt = nullptr;
     std::vector<double> x;
     if (f.fallback) {
@@ -1870,6 +1894,207 @@ int point_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, co
         HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int j = 0; j < n; ++j) memcpy(out.data() + 9 * (size_t)sel[po[j]], hc.data() + 9 * (size_t)j, 9 * sizeof(double));
+    }
+    for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    memcpy(cov, out.data(), out.size() * sizeof(double));
+    return XRSFM_BA_OK;
+}
+
+// ---------------------------------------------------------------- joint covariance of selected cameras and points (ba_cov.h)
+int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel, const int32_t* cam_sel, int32_t n_pt_sel, const int32_t* pt_sel,
+                          double* cov) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    if (c->wide || c->multi() || n_cam_sel < 0 || n_pt_sel < 0) return XRSFM_BA_EINVAL;
+    const long long N_ll = 6LL * n_cam_sel + 3LL * n_pt_sel;
+    if (N_ll == 0) return XRSFM_BA_OK;
+    if (N_ll > kCovJointMaxCols || (n_cam_sel > 0 && !cam_sel) || (n_pt_sel > 0 && !pt_sel) || !cov) return XRSFM_BA_EINVAL;
+    const int N = (int)N_ll, n_cs = n_cam_sel, n_ps = n_pt_sel;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Nc = d.n_cams, Np = c->n_points_caller;
+    std::vector<int> packed_of((size_t)std::max(Np, 1), -1);
+    {
+        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
+        for (int i = 0; i < n_cs; ++i) {
+            const int s = cam_sel[i];
+            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
+            seen[s] = 1;
+        }
+        seen.assign((size_t)std::max(Np, 1), 0);
+        for (int i = 0; i < n_ps; ++i) {
+            const int s = pt_sel[i];
+            if (s < 0 || s >= Np || seen[s]) return XRSFM_BA_EINVAL;
+            seen[s] = 1;
+        }
+        for (size_t j = 0; j < c->pk.pt_orig.size(); ++j) packed_of[c->pk.pt_orig[j]] = (int)j;
+    }
+    int e;
+    CovFront f;
+    if ((e = cov_front(c, huber_a, f, [&] {
+            for (int i = 0; i < n_cs; ++i) if (!(f.act[cam_sel[i]] > 0.0)) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
+            for (int i = 0; i < n_ps; ++i) if (packed_of[pt_sel[i]] < 0) return (int)XRSFM_BA_ESINGULAR;
+            return 0;
+        }))) return e;
+    DevScratch ds;
+    std::vector<double> out((size_t)N * N, 0.0);      // staged: cov is written only when every value is finite
+    // the free points of the selection (a constant point keeps its all-zero rows and columns): sel[] = index in pt_sel, by ascending packed index
+    std::vector<int> sel;
+    for (int i = 0; i < n_ps; ++i) if (!c->pk.pt_const[packed_of[pt_sel[i]]]) sel.push_back(i);
+    std::sort(sel.begin(), sel.end(), [&](int a, int b) { return packed_of[pt_sel[a]] < packed_of[pt_sel[b]]; });
+    const int n = (int)sel.size();
+    if (n_cs == 0 && n == 0) { memcpy(cov, out.data(), out.size() * sizeof(double)); return XRSFM_BA_OK; }      // nothing but constant points
+    std::vector<int> sel_pt((size_t)n);
+    for (int i = 0; i < n; ++i) sel_pt[i] = packed_of[pt_sel[sel[i]]];
+    CovPtRecords R;
+    if (n > 0 && (e = cov_point_records(c, ds, sel_pt, R))) return e;
+    R.rptr.resize((size_t)n + 1, 0);
+    const std::vector<int2>& rec = R.rec;
+    const std::vector<int>& ro = R.ro;
+    const std::vector<int>& rptr = R.rptr;
+    auto cam_fixed = [&](int cam) { return f.dof_const(cam, 0) && f.dof_const(cam, 3); };      // (an all-constant camera: zero rows of W_p)
+    std::vector<double> x;
+    if (f.fallback) {
+        // One factor-and-solve S x = rhs per free selected column (a unit vector; column b of W_p Hinv_p) with the run path's
+        // factor-and-solve: M = the selected rows of [E | -W Hinv]^T S^-1 [E | -W Hinv] (+ Hinv_p), symmetrised and unscaled.
+        std::vector<double> blk((size_t)R.n_rec * 18), hs((size_t)n * 9), sc((size_t)Nc * 6), rhs((size_t)h.dev.n_pad), M((size_t)N * N, 0.0), scl((size_t)N, 0.0);
+        int* d_selpt = nullptr; double* d_hs = nullptr;
+        if ((e = ds.put(&d_selpt, sel_pt)) || (e = ds.get(&d_hs, (size_t)n * 9))) return e;
+        if (n > 0) {
+            LAUNCH(c, K_SMALL, k_cov_pt_gather, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, d, (const int*)d_selpt, n, d_hs);
+            HIPCHK(hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (R.n_rec > 0) HIPCHK(hipMemcpyAsync(blk.data(), R.d_blk, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        static const int up[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+        struct Col { int pt, blk, a; };      // pt: -1 camera, else index in sel[]; blk: camera / unused; a: degree of freedom
+        std::vector<Col> cols((size_t)N, Col{-1, 0, 0});
+        for (int i = 0; i < n_cs; ++i)
+            for (int a = 0; a < 6; ++a) {
+                cols[6 * (size_t)i + a] = Col{-1, cam_sel[i], a};
+                scl[6 * (size_t)i + a] = f.dof_const(cam_sel[i], a) ? 0.0 : sc[6 * (size_t)cam_sel[i] + a];
+            }
+        for (int i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) {
+                const size_t j = 6 * (size_t)n_cs + 3 * (size_t)sel[i] + a;
+                cols[j] = Col{i, 0, a};
+                scl[j] = hs[9 * (size_t)i + 6 + a];
+            }
+        for (int j = 0; j < N; ++j) {
+            if (scl[j] == 0.0) continue;
+            const Col cj = cols[j];
+            bool any = cj.pt < 0;       // a point seen by constant cameras only: W_p = 0, nothing to solve
+            std::fill(rhs.begin(), rhs.end(), 0.0);
+            if (cj.pt < 0) rhs[h.cam_off_host[cj.blk] + cj.a] = 1.0;
+            else
+                for (int q = rptr[cj.pt]; q < rptr[cj.pt + 1]; ++q) {
+                    any = any || !cam_fixed(rec[ro[q]].y);
+                    for (int r = 0; r < 6; ++r) rhs[h.cam_off_host[rec[ro[q]].y] + r] = blk[18 * (size_t)ro[q] + 3 * r + cj.a];
+                }
+            if (any) { if ((e = cov_factor(c, x, &rhs))) return e; }
+            else x.assign((size_t)Nc * 6, 0.0);
+            for (int i = 0; i < N; ++i) {
+                if (scl[i] == 0.0) continue;
+                const Col ci = cols[i];
+                double u = 0.0;
+                if (ci.pt < 0) u = x[6 * (size_t)ci.blk + ci.a];
+                else
+                    for (int q = rptr[ci.pt]; q < rptr[ci.pt + 1]; ++q)
+                        for (int r = 0; r < 6; ++r) u += blk[18 * (size_t)ro[q] + 3 * r + ci.a] * x[6 * (size_t)rec[ro[q]].y + r];
+                if ((ci.pt < 0) != (cj.pt < 0)) u = -u;
+                else if (ci.pt >= 0 && ci.pt == cj.pt) u += hs[9 * (size_t)ci.pt + up[ci.a][cj.a]];
+                M[(size_t)i * N + j] = u;
+            }
+        }
+        for (int i = 0; i < N; ++i)
+            for (int j = i; j < N; ++j) {
+                const double sij = scl[i] * scl[j];
+                const double v = sij == 0.0 ? 0.0 : 0.5 * (M[(size_t)i * N + j] + M[(size_t)j * N + i]) * sij;
+                out[(size_t)i * N + j] = v; out[(size_t)j * N + i] = v;
+            }
+    } else {
+        if ((e = cov_factor(c, x))) return e;
+        auto col_of = [&](int cam) { return h.cam_off_host[cam] / kNB; };
+        // chunks: the cameras by elimination row, 10 per chunk, then the free points by the smallest tile column of their observers
+        // (then by packed index), 21 per chunk: the order of cam_sel / pt_sel has no say, and chunking affects no value (ba_cov.h)
+        std::vector<int> co((size_t)n_cs);
+        for (int i = 0; i < n_cs; ++i) co[i] = i;
+        std::sort(co.begin(), co.end(), [&](int a, int b) { return h.cam_off_host[cam_sel[a]] < h.cam_off_host[cam_sel[b]]; });
+        std::vector<int> kmin((size_t)n, h.T), po((size_t)n);
+        for (int r = 0; r < R.n_rec; ++r) kmin[rec[r].x] = std::min(kmin[rec[r].x], col_of(rec[r].y));
+        for (int i = 0; i < n; ++i) po[i] = i;
+        std::sort(po.begin(), po.end(), [&](int a, int b) { return kmin[a] != kmin[b] ? kmin[a] < kmin[b] : a < b; });
+        const int n_cch = cdiv(n_cs, kCovCamsPerChunk), n_ch = n_cch + cdiv(n, kCovPtsPerChunk), T = h.T;
+        CovLists L;
+        std::vector<std::vector<int>> seeds((size_t)n_ch);
+        std::vector<int4> colv((size_t)N, make_int4(-1, 0, 0, 1));
+        L.sel_row.assign((size_t)n_cch * kCovCamsPerChunk, 0);
+        for (int j = 0; j < n_cs; ++j) {
+            const int i = co[j], cam = cam_sel[i], ch = j / kCovCamsPerChunk;
+            L.sel_row[j] = h.cam_off_host[cam];
+            seeds[ch].push_back(col_of(cam));
+            for (int a = 0; a < 6; ++a) colv[6 * (size_t)i + a] = make_int4(kNB * ch + 6 * (j % kCovCamsPerChunk) + a, cam, a, 0);
+        }
+        for (int j = 0; j < n; ++j) {
+            const int i = po[j], ch = n_cch + j / kCovPtsPerChunk;
+            for (int q = rptr[i]; q < rptr[i + 1]; ++q)
+                if (!cam_fixed(rec[ro[q]].y)) seeds[ch].push_back(col_of(rec[ro[q]].y));
+            for (int a = 0; a < 3; ++a)
+                colv[6 * (size_t)n_cs + 3 * (size_t)sel[i] + a] = make_int4(kNB * ch + 3 * (j % kCovPtsPerChunk) + a, sel_pt[i], a, 1);
+        }
+        cov_build_lists(h, seeds, L, true);
+        // every chunk keeps panel slots of its own: base[ch] .. base[ch + 1)
+        std::vector<size_t> base((size_t)n_ch + 1, 0);
+        for (int ch = 0; ch < n_ch; ++ch) base[ch + 1] = base[ch] + (size_t)L.chunk_slots[ch];
+        if (base[n_ch] > (size_t)0x7fffffff) return XRSFM_BA_ENOMEM;
+        std::vector<int4> sc_ent; std::vector<int> sc_off((size_t)n_ch + 1, 0);
+        for (int j = 0; j < n; ++j) {
+            const int i = po[j], ch = n_cch + j / kCovPtsPerChunk;
+            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
+                const int row = h.cam_off_host[rec[ro[q]].y];
+                const int sl = L.slot_of[(size_t)ch * T + row / kNB];
+                if (sl >= 0) sc_ent.push_back(make_int4(ro[q], sl, row % kNB, 3 * (j % kCovPtsPerChunk)));
+            }
+            sc_off[ch + 1] = (int)sc_ent.size();
+        }
+        // chunk pairs (A <= B), row by row (k_cov_joint_finish indexes them so), and the tile columns both reach, ascending
+        std::vector<int2> g_ent, g_slots;
+        for (int A = 0; A < n_ch; ++A)
+            for (int B = A; B < n_ch; ++B) {
+                const int q0 = (int)g_slots.size();
+                for (int k = 0; k < T; ++k) {
+                    const int sa = L.slot_of[(size_t)A * T + k], sb = L.slot_of[(size_t)B * T + k];
+                    if (sa >= 0 && sb >= 0) g_slots.push_back(make_int2((int)base[A] + sa, (int)base[B] + sb));
+                }
+                g_ent.push_back(make_int2(q0, (int)g_slots.size()));
+            }
+        int4 *d_ent = nullptr, *d_sc = nullptr, *d_col = nullptr; int2 *d_lj = nullptr, *d_gent = nullptr, *d_gsl = nullptr; int* d_row = nullptr;
+        double *d_Z = nullptr, *d_G = nullptr, *d_cov = nullptr;
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, sc_ent)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_col, colv)) ||
+            (e = ds.put(&d_gent, g_ent)) || (e = ds.put(&d_gsl, g_slots)) || (e = ds.get(&d_Z, base[n_ch] * kCovPanel)) ||
+            (e = ds.get(&d_G, g_ent.size() * kCovPanel)) || (e = ds.get(&d_cov, (size_t)N * N))) return e;
+        // (a camera chunk's kernel writes every element of its slots; a point chunk's slots receive the scattered right-hand side)
+        if (base[n_ch] > base[n_cch]) HIPCHK(hipMemsetAsync(d_Z + base[n_cch] * kCovPanel, 0, sizeof(double) * (base[n_ch] - base[n_cch]) * kCovPanel, c->stream));
+        size_t li = 0;
+        for (int ch = 0; ch < n_ch; ++ch) {
+            double* Zc = d_Z + base[ch] * kCovPanel;
+            const int ne = sc_off[ch + 1] - sc_off[ch];
+            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + sc_off[ch]), ne, (const double*)R.d_blk, Zc);
+            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li) {
+                if (ch < n_cch)
+                    LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<false>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, Zc,
+                           (const int*)(d_row + (size_t)ch * kCovCamsPerChunk), std::min(kCovCamsPerChunk, n_cs - ch * kCovCamsPerChunk));
+                else
+                    LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<true>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, Zc,
+                           (const int*)nullptr, 0);
+            }
+        }
+        LAUNCH(c, K_TRISOLVE, k_cov_joint_gram, dim3((unsigned)g_ent.size()), dim3(256), 0, (const int2*)d_gent, (const int2*)d_gsl, (const double*)d_Z, d_G);
+        LAUNCH(c, K_SMALL, k_cov_joint_finish, dim3(cdiv((long long)N * N, 256)), dim3(256), 0, d, (const int4*)d_col, N, n_ch, (const double*)d_G, d_cov);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out.data(), d_cov, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
     for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
     memcpy(cov, out.data(), out.size() * sizeof(double));
@@ -3364,5 +3589,8 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
 int xrsfm_ba_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) { return no_throw([&] { return covariance_impl(c, huber_a, n_sel, cam_sel, cov); }); }
 int xrsfm_ba_point_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) { return no_throw([&] { return point_covariance_impl(c, huber_a, n_sel, pt_sel, cov); }); }
+int xrsfm_ba_joint_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel, const int32_t* cam_sel, int32_t n_pt_sel, const int32_t* pt_sel, double* cov) {
+    return no_throw([&] { return joint_covariance_impl(c, huber_a, n_cam_sel, cam_sel, n_pt_sel, pt_sel, cov); });
+}
 int xrsfm_pg_solve(const xrsfm_pg_options* opt, xrsfm_pg_problem* p, xrsfm_pg_summary* summary) { return no_throw([&] { return pg_solve_impl(opt, p, summary); }); }
 int xrsfm_tag_refine(const xrsfm_pg_options* opt, xrsfm_tag_problem* p, int32_t stages, xrsfm_pg_summary* summaries) { return no_throw([&] { return tag_refine_impl(opt, p, stages, summaries); }); }
