@@ -21,7 +21,10 @@ blocks all-reduced with RCCL inside the library (xrsfm_ba_comm_init).
       1000 cameras at config L; every rank generates and holds one config-sized
       shard) -- the regime the sharding is for (maps that outgrow one GPU).
 
-The JSON line carries `roofline` (dominant HBM-streaming kernel — of those within 10 % of the largest total the one furthest below its roofline —, algorithmic
+A plain run does what the headline figure needs and no more: set-up, the warm-up steps, the timed steps, --dump-outputs,
+the JSON line.  Everything else the benchmark measures takes runs of its own and waits behind --full.
+
+With --full the JSON line also carries `roofline` (dominant HBM-streaming kernel — of those within 10 % of the largest total the one furthest below its roofline —, algorithmic
 bytes of SURVEY.md section 8d / DESIGN.md section 5, duration from HIP events
 recorded by the library on its own stream; `roofline.iteration` = the whole LM
 iteration against BASELINE.md section 4's B_iter), `cpu_baseline` (oracle/ C
@@ -264,7 +267,8 @@ def self_profile(config: str, solver: str):
     if rp is None:
         return None
     env = dict(os.environ, XRSFM_BENCH_CHILD="1", TMPDIR="/tmp")
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--solver", solver, "--no-cpu", "--no-extras", "--steps", "1", "--warmup", "1"]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--solver", solver, "--full", "--no-cpu", "--no-extras",
+             "--steps", "1", "--warmup", "1"]
 
     def one_pass(extra):
         d = tempfile.mkdtemp(prefix="xba_prof_", dir="/tmp")
@@ -292,7 +296,7 @@ def self_profile(config: str, solver: str):
     stats = one_pass(["--kernel-trace", "--stats"])
     if stats is None:
         return None
-    out = {"source": "rocprofv3 passes launched by this bench.py run (child: --steps 1 --warmup 1 --no-cpu --no-extras)",
+    out = {"source": "rocprofv3 passes launched by this bench.py run (child: --full --steps 1 --warmup 1 --no-cpu --no-extras)",
            "kernel_avg_us": {k: round(a / 1e3, 3) for k, (c, a) in stats.items() if not k.startswith("__amd")},
            "kernel_calls": {k: c for k, (c, a) in stats.items() if not k.startswith("__amd")}}
     fetch = one_pass(["--pmc", "FETCH_SIZE", "--kernel-trace"])
@@ -399,6 +403,17 @@ def mapper_bench(args):
     print(json.dumps(out), flush=True)
 
 
+def print_result_line(out: dict) -> None:
+    """The one JSON line of the job.  RCCL prints its version banner through C stdio: that is flushed first, so that the JSON
+    line is the last line on stdout."""
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -409,8 +424,13 @@ def main():
     ap.add_argument("--solver", default="auto", choices=["auto", "pcg", "cholesky"])
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="N > 1: strong = the config split N ways (BASELINE.json config 4); weak = N x the points of the config over the same cameras")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-inclusive one-shot solve and the config-D MFMA measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: per-kernel HIP-event times and the roofline block "
+                         "(an untimed profiled solve, rocprofv3 child runs), the CPU baseline with its parity blocks, the host-inclusive "
+                         "one-shot solve and the config-D MFMA rate; the headline figures are those of a plain run")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and its parity blocks")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the rocprofv3 child runs, the host-inclusive one-shot solve and the config-D MFMA measurement")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (cameras, points, summary; bal9: intrinsics) as DIR/<name>.npy")
@@ -500,6 +520,38 @@ def main():
         if args.config == "Lb9":
             res["intr_params"] = ctx.download_intrinsics()
         dump_outputs(args.dump_outputs, res)
+
+    out = None
+    if rank == 0:
+        n_res = 2 * n_obs
+        out = {
+            "metric": "BA iterations/sec x (cams+points)", "value": iters * (n_cams + n_points) / dt,
+            "unit": "cam-pts*iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": ("synthetic clustered photo collection (shape and size of BASELINE config 5) " if args.config == "T" else "synthetic BAL-style ")
+                                   + f"{args.config}: {n_cams} cams / {n_points} points / {n_obs} obs, "
+                                   f"GBA accurate (ba_solver.cc:626-629), seed {cfg['seed']}"
+                                   + (f"; {args.scaling} scaling: " + ("this problem split over the ranks" if args.scaling == "strong"
+                                                                      else f"{world} config-sized point shards over the same cameras") if world > 1 else ""),
+                       "parallelism": (f"points sharded x{world} ({prob.n_points} points / {prob.n_obs} obs on rank 0), cameras replicated, "
+                                       f"2 RCCL all-reduces per accepted LM step") if world > 1 else "single GPU",
+                       "linear_solver": "cholesky (explicit reduced camera matrix, exact)" if last.linear_solver_used == 1
+                       else f"implicit-Schur PCG tol {opt.pcg_tolerance:g}"},
+            "lm_iterations_per_step": iters / args.steps, "pcg_iterations_per_step": pcg / args.steps,
+            "final_rmse_px": math.sqrt(last.final_cost / n_res),
+            "initial_rmse_px": math.sqrt(last.initial_cost / n_res),
+            "termination_reason": last.termination_reason, "full": args.full,
+        }
+        if args.config == "Lb9":
+            out["config"]["workload"] += "; bal9 mode: every camera's {f, k1, k2} variable, 9-wide camera blocks"
+    if not args.full:       # a plain run ends here: the line above is all of its result
+        ctx.close()
+        if rank == 0:
+            print_result_line(out)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # one extra, untimed, profiled solve: HIP-event durations per kernel class on the library's stream
     popt = capi.default_options(profile=1)
@@ -611,31 +663,9 @@ def main():
         except Exception:
             per_rank = None
     if rank == 0:
-        n_res = 2 * n_obs
-        out = {
-            "metric": "BA iterations/sec x (cams+points)", "value": iters * (n_cams + n_points) / dt,
-            "unit": "cam-pts*iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("synthetic clustered photo collection (shape and size of BASELINE config 5) " if args.config == "T" else "synthetic BAL-style ")
-                                   + f"{args.config}: {n_cams} cams / {n_points} points / {n_obs} obs, "
-                                   f"GBA accurate (ba_solver.cc:626-629), seed {cfg['seed']}"
-                                   + (f"; {args.scaling} scaling: " + ("this problem split over the ranks" if args.scaling == "strong"
-                                                                      else f"{world} config-sized point shards over the same cameras") if world > 1 else ""),
-                       "parallelism": (f"points sharded x{world} ({prob.n_points} points / {prob.n_obs} obs on rank 0), cameras replicated, "
-                                       f"2 RCCL all-reduces per accepted LM step") if world > 1 else "single GPU",
-                       "linear_solver": "cholesky (explicit reduced camera matrix, exact)" if last.linear_solver_used == 1
-                       else f"implicit-Schur PCG tol {opt.pcg_tolerance:g}"},
-            "lm_iterations_per_step": iters / args.steps, "pcg_iterations_per_step": pcg / args.steps,
-            "final_rmse_px": math.sqrt(last.final_cost / n_res),
-            "initial_rmse_px": math.sqrt(last.initial_cost / n_res),
-            "termination_reason": last.termination_reason,
-            "roofline": roofline, "cpu_baseline": None, "kernels": kernel_table,
-        }
+        out.update({"roofline": roofline, "cpu_baseline": None, "kernels": kernel_table})
         if per_rank is not None and roofline is not None:
             roofline["per_rank"] = per_rank
-        if args.config == "Lb9":
-            out["config"]["workload"] += "; bal9 mode: every camera's {f, k1, k2} variable, 9-wide camera blocks"
         if world == 1 and not args.no_cpu:
             res = cpu_baseline(arr, n_cams, n_points, opt.max_iterations)
             if res is not None:
@@ -667,12 +697,7 @@ def main():
                 out["mfma_utilisation"] = mfma_utilisation() if args.config in ("L", "S") else None
             except Exception as exc:       # the side measurement must never cost the headline line
                 out["mfma_utilisation"] = {"error": str(exc)}
-        try:        # RCCL prints its version banner through C stdio: flush it first, so that the JSON line is the last line on stdout
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(json.dumps(out), flush=True)
+        print_result_line(out)
     if world > 1:
         dist.destroy_process_group()
 

@@ -81,7 +81,7 @@ def test_torchrun_launch_line_of_the_driver(tmp_path):
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_rank_launch_contract(tmp_path, scaling):
     port = _free_port()
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "S", "--no-cpu", "--scaling", scaling]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "S", "--full", "--no-cpu", "--scaling", scaling]
     script = tmp_path / "driver.py"
     script.write_text(DRIVER.format(root=ROOT, argv=argv))
     procs = []
@@ -136,13 +136,13 @@ def test_two_ranks_on_the_collection_config(tmp_path):
 
 
 def test_dump_outputs_of_the_last_timed_step(tmp_path):
-    """`bench.py --dump-outputs DIR` on one rank with the stand-in device layer: --warmup + --steps solves (+ the untimed
-    profiled one), then the cameras, points and summary of the last timed step as float64 .npy files; a second run with the
+    """`bench.py --full --dump-outputs DIR` on one rank with the stand-in device layer: --warmup + --steps solves (+ the untimed
+    profiled one of --full), then the cameras, points and summary of the last timed step as float64 .npy files; a second run with the
     same arguments writes the same files (the inputs are generated from fixed seeds)."""
     dumps = []
     for run in range(2):
         d = tmp_path / f"out{run}"
-        argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--config", "S", "--no-cpu", "--no-extras", "--dump-outputs", str(d)]
+        argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--config", "S", "--full", "--no-cpu", "--no-extras", "--dump-outputs", str(d)]
         script = tmp_path / "driver.py"
         script.write_text(DRIVER.format(root=ROOT, argv=argv))
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -159,6 +159,39 @@ def test_dump_outputs_of_the_last_timed_step(tmp_path):
     assert out["cam_q"].shape == (12, 4) and out["cam_t"].shape == (12, 3) and out["points"].shape == (300, 3)
     assert list(out["summary"]) == [10.0, 1.0, 5, 1, 3, 0, 1]
     assert all(np.array_equal(out[k], dumps[1][k]) for k in out)
+
+
+def test_plain_run_does_what_the_headline_needs(tmp_path):
+    """Without --full a run is set-up, --warmup + --steps solves, the dump and the JSON line: no profiled solve, none of the
+    blocks that take runs of their own (--no-cpu / --no-extras change nothing then), and the same headline fields and the
+    same dumped arrays as the --full run of the same arguments."""
+    results = {}
+    for name, extra in (("plain", []), ("plain_no", ["--no-cpu", "--no-extras"]), ("full", ["--full", "--no-cpu", "--no-extras"])):
+        d = tmp_path / name
+        argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--config", "S", "--dump-outputs", str(d)] + extra
+        script = tmp_path / "driver.py"
+        script.write_text(DRIVER.format(root=ROOT, argv=argv))
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        p = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        log = eval([l for l in p.stdout.splitlines() if l.startswith("LOG")][0][4:])
+        results[name] = (json.loads(lines[0]), log.count(("run",)), {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    moved = {"roofline", "cpu_baseline", "kernels", "host_inclusive", "mfma_utilisation"}
+    for name in ("plain", "plain_no"):
+        j, runs, _ = results[name]
+        assert runs == 2 + 3 and j["full"] is False and not moved & set(j)
+        assert j["steps"] == 3 and j["warmup"] == 2 and j["lm_iterations_per_step"] == 6
+        assert abs(j["value"] - 18 * (12 + 300) / (j["ms_per_step"] * 3e-3)) <= 1e-6 * j["value"]       # 3 steps x 6 LM iterations
+    jf, runs_full, dump_full = results["full"]
+    assert runs_full == 2 + 3 + 1 and jf["full"] is True and {"roofline", "cpu_baseline", "kernels"} <= set(jf)
+    headline = ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data", "config",
+                "lm_iterations_per_step", "final_rmse_px", "initial_rmse_px", "termination_reason")
+    jp, _, dump_plain = results["plain"]
+    assert all(jp[k] == jf[k] for k in headline)
+    assert sorted(dump_plain) == sorted(dump_full) == ["cam_q", "cam_t", "points", "summary"]
+    assert all(np.array_equal(dump_plain[k], dump_full[k]) for k in dump_plain)
 
 
 def test_dump_outputs_samples_large_point_sets(tmp_path, monkeypatch):

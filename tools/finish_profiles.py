@@ -21,19 +21,19 @@ def main():
         line = [l for l in rd("stats_bench.log").splitlines() if l.startswith('{"metric"')][-1]
     nproc = rd("nproc.txt").strip()
     with open(os.path.join(dst, f"{tag}_L_kernel_stats.md"), "w") as f:
-        f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config L --no-cpu --steps 2 (MI355X, 1 GPU)\n\n"
-                "Command (tools/make_profiles.sh): `rocprofv3 --kernel-trace --stats -d DIR -o stats -- python bench.py --config L --no-cpu --steps 2`\n"
+        f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config L --full --no-cpu --steps 2 (MI355X, 1 GPU)\n\n"
+                "Command (tools/make_profiles.sh): `rocprofv3 --kernel-trace --stats -d DIR -o stats -- python bench.py --config L --full --no-cpu --steps 2`\n"
                 "(4 solves: 1 warm-up, 2 timed, 1 profiled with HIP events; 13 LM iterations each).  Per-kernel table from the rocpd\n"
                 "database with `tools/rocprof_summary.py`.\n\nbench.py line of the same (profiled) run:\n\n```\n" + line + "\n```\n\n" + rd("kernel_stats_table.md"))
     with open(os.path.join(dst, f"{tag}_L_pmc_traffic.md"), "w") as f:
-        f.write(f"# Round {tag[1:]} — HBM traffic per kernel from rocprofv3 PMC counters, bench.py --config L (MI355X, 1 GPU)\n\n"
+        f.write(f"# Round {tag[1:]} — HBM traffic per kernel from rocprofv3 PMC counters, bench.py --config L --full (MI355X, 1 GPU)\n\n"
                 "Two separate passes (tools/make_profiles.sh; TCC slots do not fit both counters):\n"
-                "`rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --config L --no-cpu --steps 1 --warmup 0` and the same with `--pmc WRITE_SIZE`.\n"
+                "`rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --config L --full --no-cpu --steps 1 --warmup 0` and the same with `--pmc WRITE_SIZE`.\n"
                 "Corrections and their calibration: see the docstring of `tools/pmc_summary.py`.  Averages per launch.\n\n" + rd("pmc_table.md"))
     shutil.copy(os.path.join(src, "pmc_traffic_L.json"), os.path.join(dst, "pmc_traffic_L.json"))
     with open(os.path.join(dst, f"{tag}_bench_lines.md"), "w") as f:
-        f.write(f"# Round {tag[1:]} — bench.py lines (MI355X, 1 GPU, host with {nproc} cores), `python bench.py --config C --steps 5 --warmup 2`\n")
-        for cfg, note in (("L", "default workload: `python bench.py --steps 20 --warmup 5`, incl. the rocprofv3 passes the run launches itself"), ("S", ""),
+        f.write(f"# Round {tag[1:]} — bench.py lines (MI355X, 1 GPU, host with {nproc} cores), `python bench.py --config C --full --steps 5 --warmup 2`\n")
+        for cfg, note in (("L", "default workload: `python bench.py --full --steps 20 --warmup 5`, incl. the rocprofv3 passes the run launches itself"), ("S", ""),
                           ("LP", "config 4 as a parity workload: + 24 hub frames x 50 distant landmarks; literal north-star bounds in cpu_baseline"), ("K", "KITTI-00-sized sequential problem"),
                           ("X", "5000 cameras: 30 000 camera unknowns on the exact Cholesky path"),
                           ("R", "ragged tracks: windows of 8 frames, 35 % missed detections"),
@@ -69,7 +69,7 @@ def main():
                     "counter rows (32 rows per dispatch: multiply by 32 for a whole launch; SQ_WAVES x 32 = waves of a launch).\n\n" + rd("pmc_mix.md"))
     if os.path.exists(os.path.join(src, "kernel_stats_table_D.md")):
         with open(os.path.join(dst, f"{tag}_D_kernel_stats.md"), "w") as f:
-            f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config D --no-cpu --steps 1 --warmup 1 (dense reduced solve: 12 000 camera unknowns, 188 tile columns)\n\n"
+            f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config D --full --no-cpu --steps 1 --warmup 1 (dense reduced solve: 12 000 camera unknowns, 188 tile columns)\n\n"
                     "k_panel2_part = 128x128 macro-tile left-looking update of two tile columns, k_ll_update_reduce = fixed-order sum of its partial tiles, "
                     "k_lv_factor = pivot factorisation + triangular solve of one tile column, k_bwd = backward substitution.\n\n" + rd("kernel_stats_table_D.md"))
             if os.path.exists(os.path.join(src, "mfma_rate.txt")):
@@ -78,7 +78,7 @@ def main():
                         ("T", "config T (BASELINE config 5's shape: 7500 photos in viewpoint clusters, exact path on the dissected camera graph)")):
         if os.path.exists(os.path.join(src, f"kernel_stats_table_{cfgk}.md")):
             with open(os.path.join(dst, f"{tag}_{cfgk}_kernel_stats.md"), "w") as f:
-                f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config {cfgk} --no-cpu --no-extras --steps 2: {title}\n\n" + rd(f"kernel_stats_table_{cfgk}.md"))
+                f.write(f"# Round {tag[1:]} — rocprofv3 kernel-trace summary, bench.py --config {cfgk} --full --no-cpu --no-extras --steps 2: {title}\n\n" + rd(f"kernel_stats_table_{cfgk}.md"))
     for extra in ("lba_phases.txt", "lba_timing.txt", "probe.txt", "mapper_trace.txt", "potrf.txt", "lat.txt", "pack_crossover.txt", "pack_phases.txt", "adapter_timing.txt", "pipes.txt"):
         if os.path.exists(os.path.join(src, extra)):
             shutil.copy(os.path.join(src, extra), os.path.join(dst, f"{tag}_{extra}"))
