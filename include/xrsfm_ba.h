@@ -209,8 +209,8 @@ int xrsfm_ba_download_intrinsics(xrsfm_ba_context *ctx, double *intr_params);
  * (a nearly singular S whose Z^T Z overflows).  The result is staged and checked before it is copied: on every error code cov is
  * left UNTOUCHED, it never receives a NaN or an Inf.  A singular point block is named on stderr (how many, and the first one's
  * index).  n_sel == 0 is success and touches nothing.
- * Cross blocks between cameras (and between cameras and points): xrsfm_ba_joint_covariance.  Not built: bal9, several ranks, a PCG
- * variant. */
+ * Cross blocks between cameras (and between cameras and points): xrsfm_ba_joint_covariance.  Every camera of the map at once:
+ * xrsfm_ba_map_covariance.  Not built: bal9, several ranks, a PCG variant. */
 int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *cam_sel, double *cov);
 
 /* Marginal covariance of selected 3-D points at the CURRENT device state: block (p,p) of (J^T J)^-1 with the conventions of
@@ -238,8 +238,8 @@ int xrsfm_ba_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, co
  * it is not part of it), ANY free point's undamped 3x3 block is singular (named on stderr like the camera call does), the solution
  * of the factored system is not finite, or a block would hold a NaN / Inf.  The result is staged: on every error code cov is left
  * UNTOUCHED.  n_sel == 0 is success and touches nothing.
- * Cross blocks between points (and between cameras and points): xrsfm_ba_joint_covariance.  Not built: the covariance of ALL points
- * by selected inversion, bal9, several ranks, a PCG variant. */
+ * Cross blocks between points (and between cameras and points): xrsfm_ba_joint_covariance.  Every point of the map at once:
+ * xrsfm_ba_map_covariance.  Not built: bal9, several ranks, a PCG variant. */
 int xrsfm_ba_point_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_sel, const int32_t *pt_sel, double *cov);
 
 /* Joint covariance of selected cameras AND points with every cross block: the sub-matrix of (J^T J)^-1 on the selected parameter
@@ -275,10 +275,52 @@ int xrsfm_ba_point_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_s
  * undamped 3x3 block is singular (named on stderr like the calls above), the solution of the factored system is not finite, or the
  * result would hold a NaN / Inf.  The result is staged and checked: on every error code cov is left UNTOUCHED.  N == 0 is success
  * and touches nothing; either count may be zero on its own.
- * Not built: the covariance of ALL points by selected inversion, bal9, several ranks, a PCG variant, a kernel path on panel plans. */
+ * The marginal blocks of the WHOLE map (no cross blocks): xrsfm_ba_map_covariance.
+ * Not built: bal9, several ranks, a PCG variant, a kernel path on panel plans. */
 #define XRSFM_BA_JOINT_COV_MAX_COLS 1024
 int xrsfm_ba_joint_covariance(xrsfm_ba_context *ctx, double huber_a, int32_t n_cam_sel, const int32_t *cam_sel, int32_t n_pt_sel,
                               const int32_t *pt_sel, double *cov);
+
+/* Marginal covariance of EVERY camera and EVERY point of the map in one call: the diagonal blocks of (J^T J)^-1 with the conventions
+ * of the three calls above (current device state, robustified J with Huber huber_a, tangent space of the library's Plus for the
+ * cameras: rotation 3, translation 3, UNSCALED coordinates, no damping, no sigma^2 factor).  cam_cov [n_cams][6][6] and
+ * pt_cov [n_points][3][3] row-major, rows in the caller's indexing whatever the packing did to it; every block is exactly
+ * symmetric, constant degrees of freedom give exact zero rows and columns.  Any of the four outputs may be NULL.
+ * cam_status [n_cams] / pt_status [n_points]:
+ *     0  estimated,
+ *     1  every degree of freedom constant (zero block),
+ *     2  not in the program (zero block): a camera without an observation, a point without one.  The selected calls return
+ *        ESINGULAR there because the caller asked for that block; this call has no selection and reports the case instead.
+ * Does not change the state or the trust region of a later run.
+ *
+ * How: the front half of the calls above, once (S = L L^T undamped, in Jacobi-scaled coordinates).  With Z = S^-1,
+ *     Sigma_pp = Hinv_p + sum over the observers c, c' of p:  V_c^T Z_cc' V_c',    V_c = F_c^T E_p Hinv_p  (6x3),
+ * needs only the 6x6 blocks Z_cc' of camera pairs that observe a common point: the structurally non-zero blocks of S, hence
+ * entries of S^-1 on the pattern of the factor, and the diagonal blocks Z_cc are the camera covariances.  The Takahashi recurrence
+ * forms exactly these entries from L (SELECTED INVERSION, xrsfm_amd/csrc/ba_cov.h: k_selinv_off / k_selinv_diag): with I_k the
+ * rows of the off-diagonal tiles of tile column k,
+ *     Z_ik = -(sum_{m in I_k} Z_im L_mk) Linv_k   (i in I_k),      Z_kk = Linv_k^T (Linv_k - sum_{m in I_k} L_mk^T Z_mk),
+ * the levels of the elimination tree from the root down, two launches per level, one workgroup per tile, 64x64x64 products on the
+ * FP64 matrix cores, m ascending (two calls agree bit for bit).  Z lives in a SECOND tile storage with the factor's own layout,
+ * dense or packed (as many bytes as the factor: xrsfm_ba_device_memory's tile storage once more for the duration of the call;
+ * XRSFM_BA_ENOMEM if the device cannot give it); dense and packed tiles give bit-identical results.  One streaming pass over
+ * the packed tracks then forms the point blocks (k_cov_map_points: one wave per point, lane = observation, the track's V_c in LDS,
+ * the pairs in a fixed order; one workgroup per track of more than 64 slots), looking Z_cc' up through the cameras' elimination
+ * rows, and the camera blocks are D_c Z_cc D_c.  Cost: about two factorisations plus that pass, against one forward
+ * substitution per 21 points of xrsfm_ba_point_covariance.
+ * Panel / look-ahead panel plans and XRSFM_BA_COV_FALLBACK=1 (read per call) take the fallback: xrsfm_ba_covariance and
+ * xrsfm_ba_point_covariance with everything that is in the program selected (slow, exact: the A/B oracle of the kernels).
+ *
+ * Errors: XRSFM_BA_EINVAL — NULL context, bal9 context, multi-rank context (communicator or test hook), a track observed twice by
+ * one camera; XRSFM_BA_ESTATE — poisoned context; XRSFM_BA_ETOOBIG exactly where XRSFM_BA_SOLVER_CHOLESKY returns it;
+ * XRSFM_BA_ENOMEM — the second tile storage does not fit; XRSFM_BA_ESINGULAR — ANY free point's undamped 3x3 block is singular
+ * (named on stderr like the calls above), the solution of the factored system is not finite, or the result would hold a NaN / Inf.
+ * The result is staged and checked: on every error code all four outputs are left UNTOUCHED.  All four pointers NULL is success
+ * and touches nothing.
+ * Not built: cross blocks of the whole map (xrsfm_ba_joint_covariance has them for a selection), bal9, several ranks, a PCG
+ * variant, a kernel path on panel plans, an adapter method, any use inside the LM loop. */
+int xrsfm_ba_map_covariance(xrsfm_ba_context *ctx, double huber_a, double *cam_cov, double *pt_cov, uint8_t *cam_status,
+                            uint8_t *pt_status);
 
 void xrsfm_ba_destroy(xrsfm_ba_context *ctx);
 

@@ -7,10 +7,13 @@ the fallback at the smallest size, each next to the sum of the two marginal call
 nothing but the joint rows (--joint-size picks one) and prints the number of joint calls made on the kernel path: under
 `rocprofv3 --kernel-trace --stats` that gives the device time of k_cov_joint_gram per call, and --gram-us (one value per joint
 size) puts it into the table as a share of the call.  Host clock around blocking calls (every call ends in a device synchronise); the first call of each size is a
-warm-up and is not counted.
+warm-up and is not counted.  --map prints the whole-map table of xrsfm_ba_map_covariance instead: config L, config R and the
+20 000-camera sequential shape on packed tiles; selected inversion, point pass (the library's own phase clocks, XRSFM_BA_COV_TIMING),
+the whole call, and the bytes of the second tile storage.
 
     python tools/cov_timing.py [--config L] [--repeat 5] [--fallback-cams 10] [--fallback-points 21]
     python tools/cov_timing.py --joint-only [--joint-size 0|1|2] [--gram-us A,B,C]
+    python tools/cov_timing.py --map [--repeat 3]
 """
 import argparse
 import os
@@ -24,8 +27,58 @@ import torch  # noqa: F401  (first, so that both share one HIP runtime)
 from xrsfm_amd import capi, synth
 
 
+def _stderr_of(f):
+    """Run f() and return what the process wrote to file descriptor 2 meanwhile (the library prints from C)."""
+    import tempfile
+    sys.stderr.flush()
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)
+        try:
+            f()
+        finally:
+            os.dup2(saved, 2); os.close(saved)
+        tmp.seek(0)
+        return tmp.read().decode(errors="replace")
+
+
+def map_table(repeat):
+    """One row per shape: the phases of xrsfm_ba_map_covariance as the library clocks them, median of `repeat` calls after a warm-up."""
+    import re
+    shapes = [("config L", lambda: synth.make_problem(**synth.CONFIGS["L"]), None),
+              ("config R", lambda: synth.make_problem(**synth.CONFIGS["R"]), None),
+              ("20 000 cameras, sequential", lambda: synth.make_problem(20000, 400000, 4, seed=13), 2000)]
+    print("| shape | tile columns / levels / packed | selected inversion ms | point pass ms | whole call ms | second tile storage bytes |")
+    print("|---|---|---|---|---|---|")
+    for name, make, const_every in shapes:
+        d = make()
+        arr = {k: np.array(d[k], copy=True) for k in capi.ProblemArrays.FIELDS}
+        cc = arr["cam_const"].copy(); cc[0] |= 3; cc[1] |= 2
+        if const_every:
+            cc[::const_every] |= 3          # (a loop this long with two constant frames is not positive definite in float64)
+        arr["cam_const"] = cc
+        plan = capi.debug_chol_plan(capi.ProblemArrays(**arr))
+        ctx = capi.Context(capi.ProblemArrays(**arr))
+        os.environ["XRSFM_BA_COV_TIMING"] = "1"
+        try:
+            ctx.map_covariance()
+            vals = []
+            for _ in range(repeat):
+                t0 = time.perf_counter()
+                err = _stderr_of(ctx.map_covariance)
+                dt = 1e3 * (time.perf_counter() - t0)
+                m = re.search(r"selected_inversion_ms ([0-9.]+) point_pass_ms ([0-9.]+) total_ms ([0-9.]+) z_bytes (\d+)", err)
+                vals.append((float(m.group(1)), float(m.group(2)), dt, int(m.group(4))))
+        finally:
+            del os.environ["XRSFM_BA_COV_TIMING"]
+            ctx.close()
+        med = np.median(np.array([v[:3] for v in vals]), axis=0)
+        print(f"| {name} | {plan['tiles']} / {plan['levels']} / {int(plan['facts']['packed'])} | {med[0]:.3f} | {med[1]:.3f} | {med[2]:.3f} | {vals[0][3]} |", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--map", action="store_true", help="the whole-map table of xrsfm_ba_map_covariance (configs L, R, 20 000 cameras) and nothing else")
     ap.add_argument("--config", default="L")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--fallback-cams", type=int, default=10, help="also time the fallback path for this many cameras (0: skip)")
@@ -36,6 +89,9 @@ def main():
     args = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("cov_timing: no HIP device")
+    if args.map:
+        map_table(max(1, min(args.repeat, 3)))
+        return
     d = synth.make_problem(**synth.CONFIGS[args.config])
     arr = {k: np.array(d[k], copy=True) for k in capi.ProblemArrays.FIELDS}
     cc = arr["cam_const"].copy(); cc[0] |= 3; cc[1] |= 2; arr["cam_const"] = cc      # the gauge of the reference's GBA

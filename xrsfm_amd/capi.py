@@ -91,6 +91,7 @@ EXPORTS = [
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
+    "xrsfm_ba_map_covariance",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -194,6 +195,8 @@ def load(path: str | None = None):
     lib.xrsfm_ba_point_covariance.restype = C.c_int
     lib.xrsfm_ba_joint_covariance.argtypes = [vp, C.c_double, C.c_int32, _c_int32_p, C.c_int32, _c_int32_p, _c_double_p]
     lib.xrsfm_ba_joint_covariance.restype = C.c_int
+    lib.xrsfm_ba_map_covariance.argtypes = [vp, C.c_double, _c_double_p, _c_double_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+    lib.xrsfm_ba_map_covariance.restype = C.c_int
     _lib = lib
     return lib
 
@@ -368,6 +371,22 @@ class Context:
         check(self.lib.xrsfm_ba_joint_covariance(self._h, huber_a, cs.shape[0], cs.ctypes.data_as(_c_int32_p), ps.shape[0], ps.ctypes.data_as(_c_int32_p), _dp(cov)),
               "xrsfm_ba_joint_covariance")
         return cov
+
+    def map_covariance(self, cameras: bool = True, points: bool = True, huber_a: float = 5.99) -> dict:
+        """Marginal covariance of EVERY camera ([n_cams][6][6]) and EVERY point ([n_points][3][3], the caller's indices) at the current
+        device state by selected inversion of the tile factor: xrsfm_ba_map_covariance.  Returns a dict with "cam_cov" / "cam_status"
+        (cameras=True) and "pt_cov" / "pt_status" (points=True); status 0 estimated, 1 all constant, 2 not in the program (zero
+        blocks).  Raises RuntimeError naming the code (EINVAL, ETOOBIG, ESINGULAR, ENOMEM) on failure."""
+        p = self.problem
+        out = {}
+        if cameras:
+            out["cam_cov"] = np.zeros((p.n_cams, 6, 6)); out["cam_status"] = np.zeros(p.n_cams, np.uint8)
+        if points:
+            out["pt_cov"] = np.zeros((p.n_points, 3, 3)); out["pt_status"] = np.zeros(p.n_points, np.uint8)
+        u8 = lambda k: out[k].ctypes.data_as(C.POINTER(C.c_uint8)) if k in out else None
+        check(self.lib.xrsfm_ba_map_covariance(self._h, huber_a, _dp(out["cam_cov"]) if cameras else None, _dp(out["pt_cov"]) if points else None,
+                                               u8("cam_status"), u8("pt_status")), "xrsfm_ba_map_covariance")
+        return out
 
     def debug_linearize(self, huber_a: float = 5.99, use_scaling: bool = False):
         p = self.problem

@@ -1,6 +1,8 @@
 // Marginal covariance of selected cameras from the tile-Cholesky factor of the UNDAMPED reduced camera matrix
 // (include/xrsfm_ba.h: xrsfm_ba_covariance), and of selected points through the same forward substitution with a general
-// right-hand side (xrsfm_ba_point_covariance: the second half of this file).
+// right-hand side (xrsfm_ba_point_covariance: the second half of this file).  Then the joint matrix of a selection
+// (xrsfm_ba_joint_covariance) and, last, every camera and point block of the whole map by selected inversion of the factor
+// (xrsfm_ba_map_covariance: k_selinv_off / k_selinv_diag and the point pass k_cov_map_points).
 //
 // With S = L L^T and E_c the 6 unit columns of camera c in elimination order, Z_c = L^-1 E_c and block (c,c) of S^-1 is
 // Z_c^T Z_c: a forward substitution with a right-hand-side PANEL, no backward pass.  The panel holds 6 columns per camera,
@@ -372,6 +374,336 @@ __global__ __launch_bounds__(256) void k_cov_joint_finish(Dev d, const int4* __r
     }
     cov[(size_t)i * N + j] = v;
     cov[(size_t)j * N + i] = v;
+}
+
+// ---------------------------------------------------------------- whole-map covariance by selected inversion (xrsfm_ba_map_covariance)
+// Z = S^-1 on the tile pattern of the factor (Takahashi recurrence).  From Z L = L^-T, with I_k the rows of the off-diagonal tiles
+// of tile column k:
+//     Z_ik = -(sum_{m in I_k} Z_im L_mk) Linv_k                      i in I_k        (k_selinv_off)
+//     Z_kk = Linv_k^T (Linv_k - sum_{m in I_k} L_mk^T Z_mk)                          (k_selinv_diag)
+// (the issue's N_mk = L_mk Linv_k with Linv_k taken out of the sum: one product with Linv_k per target tile, and L stays as the
+// factorisation left it).  Z_im is tile (i, m) of Z for m <= i and tile (m, i) transposed for m > i; both lie on the pattern (the
+// fill closure of the factorisation) and belong to ancestors of k, that is to higher levels: the levels are walked from the root
+// down, per level one launch for the off-diagonal tiles and one for the diagonal tiles (which read the former), one workgroup
+// per target tile, the kernel boundary the only synchronisation.  Z lives in a second tile storage with the factor's own layout
+// (tile_ptr with S replaced): dense and packed tiles run the same instructions on the same values.  m ascends: two calls agree
+// bit for bit.  The products are A B^T on the FP64 matrix cores (tile_abt_mfma); an operand that the formula wants transposed
+// is transposed on its way from the registers into LDS (store_tile_lds_t).  LDS and staging as in k_lv_fwd_multi.
+__device__ __forceinline__ void store_tile_lds_t(double* dst, const double2 (&v)[8]) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int e = threadIdx.x + 256 * it;
+        const int r = e >> 5, c2 = (e & 31) * 2;
+        dst[c2 * kLdT + r] = v[it].x; dst[(c2 + 1) * kLdT + r] = v[it].y;
+    }
+}
+
+//   ent [b] = {i, k, q0, q1}: target tile (i, k), i > k, and its list lm[q0 .. q1) = I_k, ascending
+__global__ __launch_bounds__(256) void k_selinv_off(CholDev c, double* __restrict__ Zs, const int4* __restrict__ ent, const int* __restrict__ lm) {
+    __shared__ __attribute__((aligned(16))) double As[kNB * kLdT];
+    __shared__ __attribute__((aligned(16))) double Bs[kNB * kLdT];
+    const int4 en = ent[blockIdx.x];
+    const int i = en.x, k = en.y, q0 = en.z, q1 = en.w;
+    CholDev z = c; z.S = Zs;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = (wave >> 1) * 32, c0 = (wave & 1) * 32;
+    v4d acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) acc[m][n2] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double2 ra[8], rb[8];
+    int m_cur = lm[q0];
+    load_tile_regs(ra, m_cur <= i ? tile_ptr(z, i, m_cur) : tile_ptr(z, m_cur, i), c.ld);
+    load_tile_regs(rb, tile_ptr(c, m_cur, k), c.ld);
+    for (int q = q0; q < q1; ++q) {
+        __syncthreads();                       // the previous product no longer reads LDS
+        if (m_cur <= i) store_tile_lds(As, ra); else store_tile_lds_t(As, ra);      // Z_im
+        store_tile_lds_t(Bs, rb);                                                    // L_mk^T
+        __syncthreads();
+        if (q + 1 < q1) {
+            m_cur = lm[q + 1];
+            load_tile_regs(ra, m_cur <= i ? tile_ptr(z, i, m_cur) : tile_ptr(z, m_cur, i), c.ld);
+            load_tile_regs(rb, tile_ptr(c, m_cur, k), c.ld);
+        }
+        tile_abt_mfma(As, Bs, acc);            // += Z_im L_mk
+    }
+    load_tile_regs(rb, c.Linv + (size_t)k * kNB * kNB, kNB);
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) As[(r0 + 16 * m + lk + 4 * g) * kLdT + c0 + 16 * n2 + li] = acc[m][n2][g];
+    store_tile_lds_t(Bs, rb);                  // Linv_k^T
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) acc[m][n2] = (v4d){0.0, 0.0, 0.0, 0.0};
+    tile_abt_mfma(As, Bs, acc);                // (sum) Linv_k
+    double* out = tile_ptr(z, i, k);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) out[(size_t)(r0 + 16 * m + lk + 4 * g) * c.ld + c0 + 16 * n2 + li] = -acc[m][n2][g];
+}
+
+//   ent [b] = {k, 0, q0, q1}: diagonal tile k and its list lm[q0 .. q1) = I_k, ascending (empty at a root).  The tile is written
+// symmetrised, 0.5 (X + X^T) with both halves from one sum: the camera blocks read from it are exactly symmetric.
+__global__ __launch_bounds__(256) void k_selinv_diag(CholDev c, double* __restrict__ Zs, const int4* __restrict__ ent, const int* __restrict__ lm) {
+    __shared__ __attribute__((aligned(16))) double As[kNB * kLdT];
+    __shared__ __attribute__((aligned(16))) double Bs[kNB * kLdT];
+    const int4 en = ent[blockIdx.x];
+    const int k = en.x, q0 = en.z, q1 = en.w;
+    CholDev z = c; z.S = Zs;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = (wave >> 1) * 32, c0 = (wave & 1) * 32;
+    v4d acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) acc[m][n2] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double2 ra[8], rb[8];
+    if (q0 < q1) {
+        const int m0 = lm[q0];
+        load_tile_regs(ra, tile_ptr(c, m0, k), c.ld);
+        load_tile_regs(rb, tile_ptr(z, m0, k), c.ld);
+    }
+    for (int q = q0; q < q1; ++q) {
+        __syncthreads();                       // the previous product no longer reads LDS
+        store_tile_lds_t(As, ra);              // L_mk^T
+        store_tile_lds_t(Bs, rb);              // Z_mk^T
+        __syncthreads();
+        if (q + 1 < q1) {
+            const int m1 = lm[q + 1];
+            load_tile_regs(ra, tile_ptr(c, m1, k), c.ld);
+            load_tile_regs(rb, tile_ptr(z, m1, k), c.ld);
+        }
+        tile_abt_mfma(As, Bs, acc);            // += L_mk^T Z_mk
+    }
+    load_tile_regs(rb, c.Linv + (size_t)k * kNB * kNB, kNB);
+    __syncthreads();
+    store_tile_lds_t(As, rb);                  // Linv_k^T
+    store_tile_lds_t(Bs, rb);
+    __syncthreads();
+    // Bs = (Linv_k - sum)^T: every element has one owner
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) Bs[(c0 + 16 * n2 + li) * kLdT + r0 + 16 * m + lk + 4 * g] -= acc[m][n2][g];
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) acc[m][n2] = (v4d){0.0, 0.0, 0.0, 0.0};
+    tile_abt_mfma(As, Bs, acc);                // Linv_k^T (Linv_k - sum)
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) As[(r0 + 16 * m + lk + 4 * g) * kLdT + c0 + 16 * n2 + li] = acc[m][n2][g];
+    __syncthreads();
+    double* out = tile_ptr(z, k, k);
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const int e = t + 256 * it, r = e >> 6, cc = e & 63;
+        out[(size_t)r * c.ld + cc] = 0.5 * (As[r * kLdT + cc] + As[cc * kLdT + r]);
+    }
+}
+
+// Camera blocks of the whole map: D_c Z_cc D_c from the diagonal tile of the camera's elimination row; thread = (camera, entry).
+// Zeros on constant degrees of freedom and for cameras that are not in the program.
+__global__ __launch_bounds__(256) void k_cov_map_cams(Dev d, CholDev c, const double* __restrict__ Zs, double* __restrict__ cov) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= d.n_cams * 36) return;
+    const int cam = id / 36, e = id % 36, a = e / 6, b = e % 6;
+    const unsigned cc = d.cam_const[cam];
+    const double* sc = d.scale_c + 6 * (size_t)cam;
+    const double da = (a < 3 ? (cc & 1u) : (cc & 2u)) ? 0.0 : sc[a];
+    const double db = (b < 3 ? (cc & 1u) : (cc & 2u)) ? 0.0 : sc[b];
+    double v = 0.0;
+    if (d.cam_act[cam] > 0.0 && da != 0.0 && db != 0.0) {
+        CholDev z = c; z.S = const_cast<double*>(Zs);
+        const int row = c.cam_off[cam], tk = row >> 6, o = row & 63;
+        v = tile_ptr(z, tk, tk)[(size_t)(o + a) * c.ld + o + b] * (da * db);
+    }
+    cov[id] = v;
+}
+
+// First and last slot of every packed point (a track's slots are consecutive; the walk below tests every slot all the same).
+// first[] starts at INT_MAX, last[] at -1.
+__global__ __launch_bounds__(kBlock) void k_cov_map_ranges(Dev d, int* __restrict__ first, int* __restrict__ last) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= d.n_slots || d.slot_cam[slot] < 0) return;
+    const int pt = d.slot_pt[slot];
+    atomicMin(first + pt, slot);
+    atomicMax(last + pt, slot);
+}
+
+// V_c = F_c^T E_p Hinv_p of one observation (6x3, [a][b]: what k_cov_pt_rhs records)
+__device__ __forceinline__ void cov_map_v(const Dev& d, int slot, int cam, int pt, double (&V)[18]) {
+    double F[12], E[6], r0, r1;
+    load_FE_rc(d, slot, cam, pt, F, E, r0, r1);
+    const double* Hi = d.Hinv + 6 * (size_t)pt;
+    const double h[6] = {Hi[0], Hi[1], Hi[2], Hi[3], Hi[4], Hi[5]};
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const double w0 = F[a] * E[0] + F[6 + a] * E[3], w1 = F[a] * E[1] + F[6 + a] * E[4], w2 = F[a] * E[2] + F[6 + a] * E[5];
+        V[3 * a + 0] = w0 * h[0] + w1 * h[1] + w2 * h[2];
+        V[3 * a + 1] = w0 * h[1] + w1 * h[3] + w2 * h[4];
+        V[3 * a + 2] = w0 * h[2] + w1 * h[4] + w2 * h[5];
+    }
+}
+
+// M += V_o^T sum_{o'} Z(c_o, c_o') V_o' for one observation o (elimination row `row`, block V) against the n observations of its
+// track (rows Rs[], < 0: no observation; blocks Vs[][18]), o' ascending.  The 6x6 block of Z: tile (row >> 6, row' >> 6) at
+// (row & 63, row' & 63) when row >= row', otherwise tile (row' >> 6, row >> 6) read transposed; two cameras of one tile column
+// meet in its (symmetric) diagonal tile.
+__device__ __forceinline__ void cov_map_pairs(const CholDev& z, int row, const double (&V)[18], int n, const int* Rs, const double* Vs, double (&M)[9]) {
+    double U[18];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) U[q] = 0.0;
+    for (int o = 0; o < n; ++o) {
+        const int ro = Rs[o];
+        if (ro < 0) continue;
+        const bool low = row >= ro;
+        const int hi = low ? row : ro, lo = low ? ro : row;
+        const double* base = tile_ptr(z, hi >> 6, lo >> 6) + (size_t)(hi & 63) * z.ld + (lo & 63);
+        const size_t sa = low ? z.ld : 1, sb = low ? 1 : z.ld;
+        const double* vo = Vs + 18 * (size_t)o;
+        double W[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) W[q] = vo[q];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; ++b) {
+                const double zab = base[a * sa + b * sb];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) U[3 * a + j] = fma(zab, W[3 * b + j], U[3 * a + j]);
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = M[3 * i + j];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s = fma(V[3 * a + i], U[3 * a + j], s);
+            M[3 * i + j] = s;
+        }
+}
+
+// cov_p = D_p (Hinv_p + sum_{c, c'} V_c^T Z_cc' V_c') D_p from the 9 sums of a point; (a, b) and (b, a) from one value
+__device__ __forceinline__ void cov_map_write(const Dev& d, int pt, const double (&M)[9], double* __restrict__ cov) {
+    const double* Hi = d.Hinv + 6 * (size_t)pt;
+    const double* sp = d.scale_p + 3 * (size_t)pt;
+    double* o = cov + 9 * (size_t)pt;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            const double s = a == b ? M[3 * a + a] : 0.5 * (M[3 * a + b] + M[3 * b + a]);
+            const double v = (Hi[a == 0 ? b : a + b + 1] + s) * (sp[a] * sp[b]);      // upper storage: 00 01 02 11 12 22
+            o[3 * a + b] = v; o[3 * b + a] = v;
+        }
+}
+
+// The point pass of the whole map: one wave per packed point whose track spans at most 64 slots (4 points per workgroup), lane =
+// observation.  The wave keeps the track's V_c and elimination rows in LDS, every lane adds its row of pairs (c, c') in ascending
+// order of c', and the lanes are added by the fixed shuffle tree of wave_sum.  Constant points and longer tracks are left to the
+// zero fill and to k_cov_map_long.  cov [n_pts][9], packed point order.
+__global__ __launch_bounds__(256) void k_cov_map_points(Dev d, CholDev c, const double* __restrict__ Zs, const int* __restrict__ first, const int* __restrict__ last,
+                                                        double* __restrict__ cov) {
+    __shared__ double Vs[4][kWave * 18];
+    __shared__ int Rs[4][kWave];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pt = blockIdx.x * 4 + wave;
+    int s0 = 0, n = 0;
+    if (pt < d.n_pts && !d.pt_const[pt]) { s0 = first[pt]; n = last[pt] - s0 + 1; }
+    const bool active = n > 0 && n <= kWave;
+    CholDev z = c; z.S = const_cast<double*>(Zs);
+    double V[18];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) V[q] = 0.0;
+    int row = -1;
+    if (active && lane < n) {
+        const int slot = s0 + lane, cam = d.slot_cam[slot];
+        if (cam >= 0 && d.slot_pt[slot] == pt) { cov_map_v(d, slot, cam, pt, V); row = c.cam_off[cam]; }
+    }
+    Rs[wave][lane] = row;
+#pragma unroll
+    for (int q = 0; q < 18; ++q) Vs[wave][18 * lane + q] = V[q];
+    __syncthreads();
+    double M[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) M[q] = 0.0;
+    if (active && row >= 0) cov_map_pairs(z, row, V, n, Rs[wave], Vs[wave], M);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) M[q] = wave_sum(M[q]);
+    if (active && lane == 0) cov_map_write(d, pt, M, cov);
+}
+
+// ... and one workgroup per point of a longer track (ent = {packed point, offset of its span in the scratch arrays}): the V_c and
+// rows of the span go to global scratch (Vg [18 per slot], Rg), thread = observations t, t + 256, ..., the threads' sums are added
+// in LDS by a fixed tree.
+__global__ __launch_bounds__(256) void k_cov_map_long(Dev d, CholDev c, const double* __restrict__ Zs, const int* __restrict__ first, const int* __restrict__ last,
+                                                      const int2* __restrict__ ent, double* __restrict__ Vg, int* __restrict__ Rg, double* __restrict__ cov) {
+    __shared__ double red[256][9];
+    const int2 en = ent[blockIdx.x];
+    const int pt = en.x, t = threadIdx.x;
+    const int s0 = first[pt], n = last[pt] - s0 + 1;
+    double* Vp = Vg + 18 * (size_t)en.y;
+    int* Rp = Rg + en.y;
+    CholDev z = c; z.S = const_cast<double*>(Zs);
+    for (int o = t; o < n; o += 256) {
+        const int slot = s0 + o, cam = d.slot_cam[slot];
+        double V[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) V[q] = 0.0;
+        int row = -1;
+        if (cam >= 0 && d.slot_pt[slot] == pt) { cov_map_v(d, slot, cam, pt, V); row = c.cam_off[cam]; }
+        Rp[o] = row;
+#pragma unroll
+        for (int q = 0; q < 18; ++q) Vp[18 * (size_t)o + q] = V[q];
+    }
+    __threadfence();
+    __syncthreads();
+    double M[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) M[q] = 0.0;
+    for (int o = t; o < n; o += 256) {
+        const int row = Rp[o];
+        if (row < 0) continue;
+        double V[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) V[q] = Vp[18 * (size_t)o + q];
+        cov_map_pairs(z, row, V, n, Rp, Vp, M);
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) red[t][q] = M[q];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off)
+#pragma unroll
+            for (int q = 0; q < 9; ++q) red[t][q] += red[t + off][q];
+        __syncthreads();
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) M[q] = red[0][q];
+        cov_map_write(d, pt, M, cov);
+    }
 }
 
 }  // namespace xba

@@ -2101,6 +2101,133 @@ int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel
     return XRSFM_BA_OK;
 }
 
+// ---------------------------------------------------------------- covariance of the whole map by selected inversion (ba_cov.h)
+int map_covariance_impl(xrsfm_ba_context* c, double huber_a, double* cam_cov, double* pt_cov, uint8_t* cam_status, uint8_t* pt_status) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    if (c->wide || c->multi()) return XRSFM_BA_EINVAL;
+    if (!cam_cov && !pt_cov && !cam_status && !pt_status) return XRSFM_BA_OK;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Nc = d.n_cams, Np = c->n_points_caller;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int e;
+    CovFront f;
+    if ((e = cov_front(c, huber_a, f, [] { return 0; }))) return e;
+    // status of every camera and point, and the packed point of a caller's point (only points with an observation are packed)
+    std::vector<uint8_t> cst((size_t)Nc), pst((size_t)Np, 2);
+    for (int i = 0; i < Nc; ++i) cst[i] = !(f.act[i] > 0.0) ? 2 : ((f.cc[i] & 3u) == 3u ? 1 : 0);
+    const int n_pk = (int)c->pk.pt_orig.size();
+    for (int j = 0; j < n_pk; ++j) pst[c->pk.pt_orig[j]] = c->pk.pt_const[j] ? 1 : 0;
+    // staged: the outputs are written only when every value is finite
+    std::vector<double> oc(cam_cov ? (size_t)Nc * 36 : 0, 0.0), op(pt_cov ? (size_t)Np * 9 : 0, 0.0);
+    double ms_inv = 0.0, ms_pts = 0.0; size_t z_bytes = 0;
+    if (f.fallback) {
+        // the selected calls with everything that is in the program selected: slow, exact, the A/B oracle of the kernels below
+        if (cam_cov) {
+            std::vector<int32_t> sel;
+            for (int i = 0; i < Nc; ++i) if (cst[i] != 2) sel.push_back(i);
+            std::vector<double> tmp(sel.size() * 36);
+            if (!sel.empty() && (e = covariance_impl(c, huber_a, (int32_t)sel.size(), sel.data(), tmp.data()))) return e;
+            for (size_t i = 0; i < sel.size(); ++i) memcpy(oc.data() + 36 * (size_t)sel[i], tmp.data() + 36 * i, 36 * sizeof(double));
+        }
+        if (pt_cov) {
+            std::vector<int32_t> sel;
+            for (int i = 0; i < Np; ++i) if (pst[i] != 2) sel.push_back(i);
+            std::vector<double> tmp(sel.size() * 9);
+            if (!sel.empty() && (e = point_covariance_impl(c, huber_a, (int32_t)sel.size(), sel.data(), tmp.data()))) return e;
+            for (size_t i = 0; i < sel.size(); ++i) memcpy(op.data() + 9 * (size_t)sel[i], tmp.data() + 9 * i, 9 * sizeof(double));
+        }
+    } else if (cam_cov || pt_cov) {
+        std::vector<double> x;
+        if ((e = cov_factor(c, x))) return e;
+        const auto t_inv = std::chrono::steady_clock::now();
+        DevScratch ds;
+        // work lists, the levels from the root down: per level the off-diagonal targets (i, k), then the diagonal tiles
+        std::vector<int4> ent; std::vector<int> lm;
+        struct Lv { int off0, n_off, diag0, n_diag; };
+        std::vector<Lv> lvs;
+        for (int lv = h.n_levels - 1; lv >= 0; --lv) {
+            Lv L{(int)ent.size(), 0, 0, 0};
+            std::vector<int4> dg;
+            for (int en = h.lv_k_off[lv]; en < h.lv_k_off[lv + 1]; ++en) {
+                const int k = h.lv_k_host[en], q0 = (int)lm.size();
+                for (int q = h.lv_bptr_host[en]; q < h.lv_bptr_host[en + 1]; ++q) lm.push_back(h.lv_bi_host[q]);      // (ascending: ba_plan.h)
+                const int q1 = (int)lm.size();
+                for (int q = q0; q < q1; ++q) ent.push_back(make_int4(lm[q], k, q0, q1));
+                dg.push_back(make_int4(k, 0, q0, q1));
+            }
+            L.n_off = (int)ent.size() - L.off0;
+            L.diag0 = (int)ent.size(); L.n_diag = (int)dg.size();
+            ent.insert(ent.end(), dg.begin(), dg.end());
+            lvs.push_back(L);
+        }
+        int4* d_ent = nullptr; int* d_lm = nullptr; double* d_Z = nullptr;
+        if ((e = ds.put(&d_ent, ent)) || (e = ds.put(&d_lm, lm)) || (e = ds.get(&d_Z, h.S_doubles))) return e;
+        z_bytes = h.S_doubles * sizeof(double);
+        HIPCHK(hipMemsetAsync(d_Z, 0, z_bytes, c->stream));      // (the shared zero tile of the packed form, the zero regions of the dense one)
+        for (const Lv& L : lvs) {
+            if (L.n_off > 0) LAUNCH(c, K_TRISOLVE, k_selinv_off, dim3(L.n_off), dim3(256), 0, h.dev, d_Z, (const int4*)(d_ent + L.off0), (const int*)d_lm);
+            LAUNCH(c, K_TRISOLVE, k_selinv_diag, dim3(L.n_diag), dim3(256), 0, h.dev, d_Z, (const int4*)(d_ent + L.diag0), (const int*)d_lm);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const auto t_pts = std::chrono::steady_clock::now();
+        ms_inv = 1e3 * std::chrono::duration<double>(t_pts - t_inv).count();
+        if (cam_cov) {
+            double* d_cc = nullptr;
+            if ((e = ds.get(&d_cc, (size_t)Nc * 36))) return e;
+            LAUNCH(c, K_SMALL, k_cov_map_cams, dim3(cdiv((long long)Nc * 36, 256)), dim3(256), 0, d, h.dev, (const double*)d_Z, d_cc);
+            HIPCHK(hipMemcpyAsync(oc.data(), d_cc, oc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (pt_cov && d.n_pts > 0) {
+            int *d_first = nullptr, *d_last = nullptr; double* d_pc = nullptr;
+            if ((e = ds.get(&d_first, (size_t)d.n_pts)) || (e = ds.get(&d_last, (size_t)d.n_pts)) || (e = ds.get(&d_pc, (size_t)d.n_pts * 9))) return e;
+            HIPCHK(hipMemsetAsync(d_first, 0x7f, sizeof(int) * (size_t)d.n_pts, c->stream));
+            HIPCHK(hipMemsetAsync(d_last, 0xff, sizeof(int) * (size_t)d.n_pts, c->stream));
+            HIPCHK(hipMemsetAsync(d_pc, 0, sizeof(double) * (size_t)d.n_pts * 9, c->stream));
+            LAUNCH(c, K_SMALL, k_cov_map_ranges, dim3(cdiv(d.n_slots, kBlock)), dim3(kBlock), 0, d, d_first, d_last);
+            LAUNCH(c, K_SMALL, k_cov_map_points, dim3(cdiv(d.n_pts, 4)), dim3(256), 0, d, h.dev, (const double*)d_Z, (const int*)d_first, (const int*)d_last, d_pc);
+            // tracks that span more than one wave: one workgroup each
+            std::vector<int> first((size_t)d.n_pts), last((size_t)d.n_pts);
+            HIPCHK(hipMemcpyAsync(first.data(), d_first, sizeof(int) * first.size(), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(last.data(), d_last, sizeof(int) * last.size(), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            std::vector<int2> lg; size_t n_span = 0;
+            for (int j = 0; j < d.n_pts && j < n_pk; ++j) {
+                const long long n = (long long)last[j] - first[j] + 1;
+                if (c->pk.pt_const[j] || n <= kWave) continue;
+                if (n_span + (size_t)n > 0x7fffffffu) return XRSFM_BA_ETOOBIG;
+                lg.push_back(make_int2(j, (int)n_span)); n_span += (size_t)n;
+            }
+            if (!lg.empty()) {
+                int2* d_lg = nullptr; double* d_Vg = nullptr; int* d_Rg = nullptr;
+                if ((e = ds.put(&d_lg, lg)) || (e = ds.get(&d_Vg, n_span * 18)) || (e = ds.get(&d_Rg, n_span))) return e;
+                LAUNCH(c, K_SMALL, k_cov_map_long, dim3((unsigned)lg.size()), dim3(256), 0, d, h.dev, (const double*)d_Z, (const int*)d_first, (const int*)d_last, (const int2*)d_lg,
+                       d_Vg, d_Rg, d_pc);
+            }
+            HIPCHK(hipGetLastError());
+            std::vector<double> hp((size_t)d.n_pts * 9);
+            HIPCHK(hipMemcpyAsync(hp.data(), d_pc, hp.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (int j = 0; j < n_pk; ++j) memcpy(op.data() + 9 * (size_t)c->pk.pt_orig[j], hp.data() + 9 * (size_t)j, 9 * sizeof(double));
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        ms_pts = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pts).count();
+    }
+    for (double v : oc) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    for (double v : op) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    if (cam_cov) memcpy(cam_cov, oc.data(), oc.size() * sizeof(double));
+    if (pt_cov) memcpy(pt_cov, op.data(), op.size() * sizeof(double));
+    if (cam_status) memcpy(cam_status, cst.data(), cst.size());
+    if (pt_status) memcpy(pt_status, pst.data(), pst.size());
+    if (std::getenv("XRSFM_BA_COV_TIMING"))       // (developer aid, tools/cov_timing.py: host clock around the phases of one call)
+        fprintf(stderr, "[xrsfm_ba] map_covariance: selected_inversion_ms %.3f point_pass_ms %.3f total_ms %.3f z_bytes %zu fallback %d\n", ms_inv, ms_pts,
+                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), z_bytes, f.fallback ? 1 : 0);
+    return XRSFM_BA_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -3589,6 +3716,9 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
 int xrsfm_ba_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) { return no_throw([&] { return covariance_impl(c, huber_a, n_sel, cam_sel, cov); }); }
 int xrsfm_ba_point_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) { return no_throw([&] { return point_covariance_impl(c, huber_a, n_sel, pt_sel, cov); }); }
+int xrsfm_ba_map_covariance(xrsfm_ba_context* c, double huber_a, double* cam_cov, double* pt_cov, uint8_t* cam_status, uint8_t* pt_status) {
+    return no_throw([&] { return map_covariance_impl(c, huber_a, cam_cov, pt_cov, cam_status, pt_status); });
+}
 int xrsfm_ba_joint_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel, const int32_t* cam_sel, int32_t n_pt_sel, const int32_t* pt_sel, double* cov) {
     return no_throw([&] { return joint_covariance_impl(c, huber_a, n_cam_sel, cam_sel, n_pt_sel, pt_sel, cov); });
 }
