@@ -88,6 +88,24 @@ typedef struct xrsfm_ba_problem {
                                       ring graphs (sequential data: shallow elimination tree) while the tile storage
                                       fits (XRSFM_BA_ETOOBIG otherwise)                                      */
 #define XRSFM_BA_SOLVER_AUTO 2     /* CHOLESKY whenever the rule above allows it, else PCG                  */
+#define XRSFM_BA_SOLVER_RESIDENT 3 /* the whole LM loop in ONE kernel launch of one workgroup (ba_lba.h): linearisation,
+                                      damped point blocks, reduced camera system, its Cholesky factorisation and solve,
+                                      back-substitution, candidate cost, step test, radius update and the tolerance
+                                      exits all run on the device; the host passes the options with the launch and
+                                      reads one result block (summary fields and, with verbose, the iteration rows)
+                                      back.  The same restated Ceres loop and the same exact reduced system as
+                                      _CHOLESKY, for local-BA-sized problems.  Opt-in only: AUTO never selects it.
+                                      Eligibility (else XRSFM_BA_EINVAL, one line on stderr, state untouched):
+                                      a 6-wide context (not bal9 mode); one rank (no communicator, no test hook);
+                                      n_cams <= 10 (the reduced system is one 64x64 tile: what
+                                      xrsfm_ba_debug_chol_plan reports as stats[0] == 1); no track observed twice by
+                                      one camera (as for _CHOLESKY); n_obs <= 32768 (one compute unit streams the
+                                      observations three times per LM step).  Measured (profiles/lba_resident.md):
+                                      same result as _CHOLESKY to 1e-11, but 9-38 x SLOWER per call at 6000-30000
+                                      observations: a cross-check and a base for further work, not a fast path.  After the call the context holds what a _CHOLESKY run
+                                      would have left: download, reset, a further run with any solver and the
+                                      covariance calls work on it unchanged.  profile != 0: xrsfm_ba_profile_entry
+                                      lists k_lba_resident with one launch and no other kernel                    */
 
 typedef struct xrsfm_ba_options {
     int32_t max_iterations;      /* GBA accurate 50 / fast 20 / KGBA 20 / LBA 5        */
@@ -126,7 +144,7 @@ typedef struct xrsfm_ba_summary {
     double dom_kernel_ms;           /* profile!=0: sum of HIP-event durations of the costliest kernel */
     int32_t dom_kernel_launches;    /* profile!=0: launches counted in dom_kernel_ms   */
     int32_t dom_kernel_id;          /* profile!=0: index for xrsfm_ba_profile_entry    */
-    int32_t linear_solver_used;     /* XRSFM_BA_SOLVER_PCG or _CHOLESKY                */
+    int32_t linear_solver_used;     /* XRSFM_BA_SOLVER_PCG, _CHOLESKY or _RESIDENT     */
     int32_t reserved;
 } xrsfm_ba_summary;
 

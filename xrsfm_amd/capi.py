@@ -111,6 +111,7 @@ def _facts(v) -> dict:
     return f
 
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
+SOLVER_RESIDENT = 3     # the whole LM loop in one kernel launch (local-BA-sized problems: include/xrsfm_ba.h)
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
           -4: "ECOMM", -5: "ESTATE", -6: "ETOOBIG", -7: "EINTERNAL (unexpected exception inside the library)",

@@ -45,6 +45,13 @@ struct TrustRegion {
         radius = std::fmin(kMaxRadius, radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
         decrease = 2.0;
     }
+    // The same rule with the cube written out, for k_lba_resident (ba_lba.h): the inlined pow() cost that kernel a scratch segment.
+    // (2 rho - 1)^3 by two multiplications is within an ulp of pow()'s.
+    XTR_HD void grow_cubed(double rho) {
+        const double x = 2.0 * rho - 1.0;
+        radius = std::fmin(kMaxRadius, radius / std::fmax(1.0 / 3.0, 1.0 - x * x * x));
+        decrease = 2.0;
+    }
     // 4 once the radius is below kMinRadius, else 0
     XTR_HD int shrink() {
         radius /= decrease; decrease *= 2.0;

@@ -252,7 +252,10 @@ class FlatProblem {
     }
 
     // ceres::Solve replacement; writes the result back into the Map on success.
-    int Solve(const xrsfm_ba_options &opt, xrsfm_ba_summary *summary) {
+    // try_resident (LBA with XRSFM_BA_LBA_RESIDENT=1): request XRSFM_BA_SOLVER_RESIDENT when the flattened problem is eligible for it
+    // (include/xrsfm_ba.h: at most 10 cameras and 32768 observations, no track observed twice by one camera); else today's call.
+    int Solve(const xrsfm_ba_options &opt_in, xrsfm_ba_summary *summary, bool try_resident = false) {
+        xrsfm_ba_options opt = opt_in;
         BuildObservations();
         GatherPoints();
         xrsfm_ba_problem p;
@@ -264,6 +267,16 @@ class FlatProblem {
         p.intr_model = intr_model_.data(); p.intr_params = intr_params_.data();
         p.points = points_.get(); p.point_const = point_const_.data();
         p.obs_cam = obs_cam_.get(); p.obs_pt = obs_pt_.get(); p.obs_uv = obs_uv_.get();
+        if (try_resident && p.n_cams >= 1 && p.n_cams <= 10 && p.n_obs <= 32768) {
+            std::vector<uint16_t> seen(tracks_.size(), 0);          // cameras that observe the track, one bit each
+            bool twice = false;
+            for (size_t i = 0; i < n_obs_ && !twice; ++i) {
+                const uint16_t bit = static_cast<uint16_t>(1u << p.obs_cam[i]);
+                twice = (seen[p.obs_pt[i]] & bit) != 0;
+                seen[p.obs_pt[i]] |= bit;
+            }
+            if (!twice) opt.linear_solver = XRSFM_BA_SOLVER_RESIDENT;
+        }
         const auto t_packed = std::chrono::steady_clock::now();
         const int rc = xrsfm_ba_solve(&opt, &p, summary);
         const auto t_solved = std::chrono::steady_clock::now();
@@ -516,7 +529,9 @@ void BASolver::LBA(int frame_id, Map &map) {
     }
     xrsfm_ba_options opt = ReferenceOptions(5, 1e-4, 1e-5);
     xrsfm_ba_summary summary;
-    last_status_ = problem.Solve(opt, &summary);   // the reference prints nothing for LBA (:586-591)
+    // XRSFM_BA_LBA_RESIDENT=1 (read per call): the one-launch solver for eligible calls; the default is unchanged
+    const char *resident_env = std::getenv("XRSFM_BA_LBA_RESIDENT");
+    last_status_ = problem.Solve(opt, &summary, resident_env && resident_env[0] == '1');   // the reference prints nothing for LBA (:586-591)
 }
 
 int RefineFramePose(Frame &frame, const Camera &camera, const std::vector<vector3> &points3ds,

@@ -29,6 +29,7 @@
 #include "ba_cov.h"
 #include "ba_filter.h"
 #include "ba_kernels.h"
+#include "ba_lba.h"
 #include "ba_pack.h"
 #include "ba_plan.h"
 #include "ba_refine.h"
@@ -85,11 +86,11 @@ constexpr int kNcclSum = 0, kNcclMax = 2;
 // kernel classes for the HIP-event profile
 enum Kid {
     K_LINEARIZE = 0, K_COST, K_CAM_SEGSUM, K_SCHUR_PREP, K_SCHUR_MATVEC, K_PCG_VEC, K_BACKSUB, K_SCHUR_PAIRS, K_BLOCK_SEGSUM,
-    K_DENSE_FILL, K_POTRF, K_TRSM, K_UPDATE, K_TRISOLVE, K_SMALL, K_COUNT
+    K_DENSE_FILL, K_POTRF, K_TRSM, K_UPDATE, K_TRISOLVE, K_LBA, K_SMALL, K_COUNT
 };
 const char* kKidName[K_COUNT] = {
     "k_linearize", "k_cost", "k_cam_segsum", "k_schur_prep", "k_schur_matvec", "k_pcg_update", "k_backsub", "k_schur_pairs",
-    "k_block_segsum", "k_dense_fill", "k_potrf", "k_trsm", "k_update", "k_fwd_bwd", "small_kernels"};
+    "k_block_segsum", "k_dense_fill", "k_potrf", "k_trsm", "k_update", "k_fwd_bwd", "k_lba_resident", "small_kernels"};
 
 constexpr int kMaxRanks = 64;          // slots for the per-rank point-gradient maxima behind camlin
 constexpr int kCholMaxN = 12288;          // dense-pattern reduced systems (right-looking schedule) up to this many unknowns
@@ -2688,6 +2689,67 @@ static int assemble_wide(xrsfm_ba_context* c, double radius) {
     return 0;
 }
 
+// XRSFM_BA_SOLVER_RESIDENT (ba_lba.h): the LM loop of ba_run_impl below as one launch of one workgroup.  The options travel as
+// kernel arguments, the result block (summary fields, then the iteration rows when asked) is written by the kernel straight into
+// a pinned block and read after the stream has drained.  Every refusal happens before anything of the state is written.
+static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_summary* sum) {
+    Dev& d = c->d;
+    const char* why = nullptr;
+    if (c->wide) why = "a bal9 context (9-wide camera blocks)";
+    else if (c->multi()) why = "a context with a communicator or the test hook (one rank only)";
+    else if (d.n_cams > kLbaMaxCams) why = "more than 10 cameras (the reduced system must be one 64x64 tile)";
+    else if (c->pk.n_obs > kLbaMaxObs) why = "more than 32768 observations";
+    else if (d.n_slots != d.n_tiles * kWave || opt.max_iterations < 0) why = "an unexpected packing or a negative max_iterations";
+    if (why) {
+        fprintf(stderr, "[xrsfm_ba] XRSFM_BA_SOLVER_RESIDENT is not available for %s\n", why);
+        return XRSFM_BA_EINVAL;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    c->profiling = opt.profile != 0;
+    for (int i = 0; i < K_COUNT; ++i) { c->prof_ms[i] = 0.0; c->prof_n[i] = 0; }
+    c->recs.clear(); c->ev_used = 0;
+    const size_t n_rows_max = opt.verbose ? (size_t)opt.max_iterations + 1 : 0;
+    const size_t bytes = sizeof(LbaResult) + sizeof(LbaRow) * n_rows_max;
+    size_t cap = 0;
+    unsigned char* host = static_cast<unsigned char*>(g_pinned.get(bytes, &cap));
+    if (!host) { c->profiling = false; return XRSFM_BA_ENOMEM; }
+    LbaResult* res = reinterpret_cast<LbaResult*>(host);
+    LbaRow* rows = reinterpret_cast<LbaRow*>(host + sizeof(LbaResult));
+    memset(res, 0, sizeof(*res));
+    res->status = -1;
+    const LbaOpt lo{opt.max_iterations, opt.verbose ? 1 : 0, opt.function_tolerance, opt.parameter_tolerance, opt.gradient_tolerance,
+                    opt.initial_radius, opt.huber_a};
+    c->linearized = false; c->step_valid = false; c->gradmax_done = false; c->published = false;
+    LAUNCH(c, K_LBA, k_lba_resident, dim3(1), dim3(kLbaBlock), 0, lba_dev(d), lo, res, rows);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = (hipStreamSynchronize(c->stream) == hipSuccess) && ok;
+    const LbaResult r = *res;
+    int e = ok && r.status >= 0 ? XRSFM_BA_OK : XRSFM_BA_ENODEV;
+    if (!e && r.status == 1) {
+        fprintf(stderr, "[xrsfm_ba] XRSFM_BA_SOLVER_RESIDENT is not available for a track observed twice by one camera: use AUTO or PCG\n");
+        e = XRSFM_BA_EINVAL;
+    }
+    if (!e) {
+        sum->linear_solver_used = XRSFM_BA_SOLVER_RESIDENT;
+        sum->num_residuals = 2 * c->pk.n_obs;
+        sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p);
+        sum->initial_cost = r.initial_cost; sum->final_cost = r.final_cost;
+        sum->n_successful = r.n_successful; sum->n_unsuccessful = r.n_unsuccessful;
+        sum->termination = r.termination; sum->termination_reason = r.reason; sum->lm_steps_attempted = r.attempted;
+        for (int i = 0; i < r.n_rows && (size_t)i < n_rows_max; ++i)
+            print_progress(opt, rows[i].it, rows[i].cost, rows[i].change, rows[i].gmax, rows[i].step, rows[i].rho, rows[i].radius);
+        sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+        if (c->profiling) {
+            profile_collect(c);
+            sum->dom_kernel_id = K_LBA; sum->dom_kernel_ms = c->prof_ms[K_LBA]; sum->dom_kernel_launches = c->prof_n[K_LBA];
+        }
+    }
+    c->recs.clear(); c->ev_used = 0;
+    c->profiling = false;
+    g_pinned.put(host, cap);
+    return e;
+}
+
 static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) {
     if (!c || !optp || !sum) return XRSFM_BA_EINVAL;
     if (c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context: only xrsfm_ba_destroy is left
@@ -2700,6 +2762,7 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
     hipStream_t st = c->stream;
     int solver = opt.linear_solver;
     int e;
+    if (solver == XRSFM_BA_SOLVER_RESIDENT) return lba_run(c, opt, sum);        // one launch, one workgroup (ba_lba.h)
     if (c->wide) {      // bal9 mode: exact solver, one rank
         if (solver == XRSFM_BA_SOLVER_PCG || c->multi()) {
             fprintf(stderr, "[xrsfm_ba] variable intrinsics (9-wide camera blocks): only the exact solver on one rank is implemented\n");
