@@ -564,12 +564,25 @@ int xrsfm_ba_debug_reduced_system(xrsfm_ba_context *ctx, double radius, int32_t 
 int xrsfm_ba_debug_wide(xrsfm_ba_context *ctx, double huber_a, double radius, double *cost, double *r, double *Jc, double *Jp,
                         double *Hcc_diag, double *gc, double *y);
 
-/* After debug_cholesky_solve: one back-substitution (k_backsub) from the camera solution it left.  Outputs in the
+/* After debug_cholesky_solve (bal9 contexts: after a debug_wide that solved a step, y != NULL, which launches k9_backsub at that
+ * radius): one back-substitution (k_backsub) from the camera solution it left.  Outputs in the
  * library's PACKED order (for comparing two builds of the library on the same problem, tools/backsub_waves_probe.py):
  * per work item the model-decrease and squared point-step partials [n_items] (n_items = debug_pack stats), candidate
  * points and scaled point steps [n_points_packed][3], candidate cameras [n_cams][4] / [n_cams][3].  Any pointer may be NULL. */
 int xrsfm_ba_debug_backsub(xrsfm_ba_context *ctx, double *part_model, double *part_step2, double *cand_points,
                            double *point_step, double *cand_cam_q, double *cand_cam_t);
+
+/* TEST ENTRY.  What a context holds next to the packed-order outputs of debug_backsub, so that a caller can put them into its
+ * own order; every output may be NULL.  pt_orig [n_points_packed]: the caller's point index of every packed point.  item_tiles
+ * [n_items][2]: first tile and number of tiles of every work item (with slot_obs of debug_pack: the caller's observations of the
+ * item, 64 slots per tile).  flags [2]: [0] 1 = the last step's kernels form the point factors themselves (k_backsub<true>;
+ * always 1 for bal9 contexts), [1] 1 = the per-observation residual and Jacobian are stored (always 1 for bal9 contexts).
+ * Of the last debug_backsub on the current step (XRSFM_BA_ESTATE without one): campart [2][n_cams] the per-camera squared step
+ * and squared norm partials; cand_intr [n_cams][3] the candidate {f, k1, k2} (bal9 contexts; the current values otherwise).
+ * Of the current linearisation (XRSFM_BA_ESTATE without one): the Jacobi scales scale_c [n_cams][cw], cw = 6 (9 for bal9
+ * contexts), and scale_p [n_points_packed][3]. */
+int xrsfm_ba_debug_backsub_layout(xrsfm_ba_context *ctx, int32_t *pt_orig, int32_t *item_tiles, double *campart, int32_t flags[2],
+                                  double *cand_intr, double *scale_c, double *scale_p);
 
 /* Whether the context currently keeps the per-observation residual and Jacobian stored (1) or recomputes them in the
  * consumers (0, the J-free linearisation of the Cholesky path): after xrsfm_ba_run, the mode its last iterations used. */

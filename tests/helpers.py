@@ -245,6 +245,17 @@ def reduced_system_oracle(arr, radius, use_scaling=True):
     return S, b
 
 
+def long_problem(lengths, seed):
+    """210 cameras, 900 short tracks and one track of each of `lengths` observations (more than 64: an item of several tiles)."""
+    n_cams = 210
+    rng = np.random.default_rng(seed)
+    tracks = [np.arange(c, c + 4) % n_cams for c in rng.integers(0, n_cams, 900)]
+    tracks = [np.sort(np.unique(t)) for t in tracks]
+    for L in lengths:
+        tracks.append(np.sort(rng.choice(n_cams, L, replace=False)))
+    return make_tracks(n_cams, tracks, seed=seed)
+
+
 def make_bal9(n_cams=12, n_pts=600, k_obs=4, seed=5, **kw):
     """bal9 mode (BASELINE north_star "2x9 camera blocks"): every camera has its own intrinsics of the extension
     model 5 {f, k1, k2} (no principal point) and keeps them VARIABLE (cam_const bit 2): 9-wide camera blocks.  Same geometry and

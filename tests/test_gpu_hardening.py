@@ -119,14 +119,7 @@ def test_shape_tiles_match_oracle(lib, idx):
     _assert_solve_matches(arr, (idx, "pcg", mine), solver=0)
 
 
-def _long_problem(lengths, seed):
-    n_cams = 210
-    rng = np.random.default_rng(seed)
-    tracks = [np.arange(c, c + 4) % n_cams for c in rng.integers(0, n_cams, 900)]
-    tracks = [np.sort(np.unique(t)) for t in tracks]
-    for L in lengths:
-        tracks.append(np.sort(rng.choice(n_cams, L, replace=False)))
-    return H.make_tracks(n_cams, tracks, seed=seed)
+_long_problem = H.long_problem      # (moved to tests/helpers.py: tests/backsub_yardstick.py uses it too)
 
 
 @pytest.mark.gpu

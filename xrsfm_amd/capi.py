@@ -91,7 +91,7 @@ EXPORTS = [
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
-    "xrsfm_ba_map_covariance",
+    "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -158,6 +158,9 @@ def load(path: str | None = None):
     if hasattr(lib, "xrsfm_ba_debug_backsub"):      # (absent in the round-2 repro builds of tools/backsub_waves_probe.py)
         lib.xrsfm_ba_debug_backsub.argtypes = [vp] + [_c_double_p] * 6
         lib.xrsfm_ba_debug_backsub.restype = C.c_int
+    if hasattr(lib, "xrsfm_ba_debug_backsub_layout"):
+        lib.xrsfm_ba_debug_backsub_layout.argtypes = [vp, _c_int32_p, _c_int32_p, _c_double_p, _c_int32_p] + [_c_double_p] * 3
+        lib.xrsfm_ba_debug_backsub_layout.restype = C.c_int
     lib.xrsfm_ba_debug_set_block_pattern.argtypes = [vp, C.c_int, _c_int32_p]
     lib.xrsfm_ba_debug_set_block_pattern.restype = C.c_int
     lib.xrsfm_pg_default_options.argtypes = [C.POINTER(CPgOptions)]
@@ -482,6 +485,54 @@ class Context:
                    cand_cam_q=np.zeros((nc, 4)), cand_cam_t=np.zeros((nc, 3)))
         check(self.lib.xrsfm_ba_debug_backsub(self._h, *[_dp(out[k]) for k in ("part_model", "part_step2", "cand_points", "point_step",
                                                                                   "cand_cam_q", "cand_cam_t")]), "debug_backsub")
+        return out
+
+    def debug_backsub_layout(self, after_backsub: bool = False, scales: bool = False) -> dict:
+        """xrsfm_ba_debug_backsub_layout: pt_orig [n_points_packed], item_tiles [n_items][2] (first tile, tiles), the flags step_prep
+        (the last step ran k_backsub<true>) and stored_j.  after_backsub (needs a debug_backsub on the current step): also campart
+        [2][n_cams] and cand_intr [n_cams][3].  scales (needs a linearisation only): also the Jacobi scales scale_c [n_cams][6 or 9]
+        and scale_p [n_points_packed][3] — bal9 contexts have no unscaled linearisation to recompute them from (debug_wide returns
+        the scaled one), and a test of the candidate state needs the scales the kernel used."""
+        st = debug_pack(self.problem)
+        nc = self.problem.n_cams
+        out = dict(pt_orig=np.zeros(st["active_points"], np.int32), item_tiles=np.zeros((st["items"], 2), np.int32))
+        flags = np.zeros(2, np.int32)
+        if after_backsub:
+            out["campart"] = np.zeros((2, nc)); out["cand_intr"] = np.zeros((nc, 3))
+        if scales:
+            cw = 9 if (self.problem.cam_const & 4).any() else 6
+            out["scale_c"] = np.zeros((nc, cw)); out["scale_p"] = np.zeros((st["active_points"], 3))
+        i32 = lambda a: a.ctypes.data_as(_c_int32_p)
+        check(self.lib.xrsfm_ba_debug_backsub_layout(self._h, i32(out["pt_orig"]), i32(out["item_tiles"]), _dp(out.get("campart")), i32(flags),
+                                                     _dp(out.get("cand_intr")), _dp(out.get("scale_c")), _dp(out.get("scale_p"))),
+              "debug_backsub_layout")
+        out["step_prep"] = bool(flags[0]); out["stored_j"] = bool(flags[1])
+        out["slot_obs"] = st["slot_obs"]
+        return out
+
+    def debug_backsub_caller_order(self) -> dict:
+        """debug_backsub with everything in the CALLER's order: cand_points / point_step [n_points][3] (rows of points without an
+        observation: the input point / zero) and `packed` [n_points] (False for those rows); per work item part_model / part_step2
+        [n_items], item_obs (list of the caller's observation indices of the item) and item_points (list of the caller's point
+        indices headed in the item); cand_cam_q / cand_cam_t / cand_intr per camera, campart [2][n_cams]; the Jacobi scales scale_c, scale_p [n_points][3]
+        (1 for points without an observation); step_prep, stored_j."""
+        raw = self.debug_backsub()
+        lay = self.debug_backsub_layout(after_backsub=True, scales=True)
+        p = self.problem
+        po = lay["pt_orig"]
+        out = {k: raw[k] for k in ("part_model", "part_step2", "cand_cam_q", "cand_cam_t")}
+        out.update({k: lay[k] for k in ("campart", "cand_intr", "step_prep", "stored_j", "item_tiles", "scale_c")})
+        out["scale_p"] = np.ones((p.n_points, 3)); out["scale_p"][po] = lay["scale_p"]
+        out["cand_points"] = np.array(p.points, copy=True); out["cand_points"][po] = raw["cand_points"]
+        out["point_step"] = np.zeros((p.n_points, 3)); out["point_step"][po] = raw["point_step"]
+        out["packed"] = np.zeros(p.n_points, bool); out["packed"][po] = True
+        so = lay["slot_obs"]
+        out["item_obs"], out["item_points"] = [], []
+        for first, n in lay["item_tiles"]:
+            o = so[64 * first:64 * (first + n)]
+            o = o[o >= 0]
+            out["item_obs"].append(o)
+            out["item_points"].append(np.unique(p.obs_pt[o]))
         return out
 
     def debug_set_block_pattern(self, row_col: np.ndarray):

@@ -195,6 +195,7 @@ struct xrsfm_ba_context {
     double step_radius = 0.0;       // radius of the step being assembled / solved (prepare_step, assemble_wide)
     bool step_prep = false;         // ... and whether its kernels form the point factors themselves
     bool step_valid = false;        // a step of the current linearisation has been assembled and solved (xrsfm_ba_debug_backsub needs it)
+    bool backsub_done = false;      // ... and xrsfm_ba_debug_backsub has run on it (xrsfm_ba_debug_backsub_layout: campart, candidate intrinsics)
     bool gradmax_done = false, published = false;    // the linearisation tail did these in its own launch
     double* part2 = nullptr; unsigned* ticket = nullptr;      // k_lin_tail
     // Second set of linearisation buffers: every LM step linearises at the CANDIDATE point right after the back-substitution
@@ -640,6 +641,7 @@ int linearize_wide(xrsfm_ba_context* c, double huber_a) {
     if (int e = use_stored_j(c, true)) return e;        // (bal9 keeps stored J)
     Dev& d = c->d;
     c->gradmax_done = false; c->published = false;
+    c->step_valid = false;          // (like linearize(): a step solved by xrsfm_ba_debug_wide belongs to the linearisation it was solved on)
     if (d.n_items > 0) LAUNCH(c, K_LINEARIZE, k9_linearize, dim3(cdiv(d.n_items, kWavesPerBlock)), dim3(kBlock), 0, d, c->w, huber_a);
     if (d.n_cams > 0) LAUNCH(c, K_CAM_SEGSUM, k_cam_segsum<18>, dim3(d.n_cams), dim3(kBlock), 0, c->w.scat, d.cam_ptr_g, c->w.camlin, (const PcgStatus*)nullptr);
     ReduceJobs j{};
@@ -3390,6 +3392,7 @@ int xrsfm_ba_debug_wide(xrsfm_ba_context* c, double huber_a, double radius, doub
         if ((e = chol_setup(c))) return e == kErrDuplicateObs ? XRSFM_BA_EINVAL : e;
         if ((e = assemble_wide(c, radius))) return e;
         if ((e = chol_factor_solve(c))) return e;
+        c->step_valid = true; c->backsub_done = false;      // (xrsfm_ba_debug_backsub: k9_backsub at this radius)
         HIPCHK(hipMemcpyAsync(y, c->w.px, sizeof(double) * (size_t)k.n_cams * kW, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
@@ -3597,7 +3600,7 @@ int xrsfm_ba_debug_cholesky_solve(xrsfm_ba_context* c, double radius, double* y,
                     }
     }
     if ((e = chol_factor_solve(c))) return e;
-    c->step_valid = true;
+    c->step_valid = true; c->backsub_done = false;
     HIPCHK(hipMemcpyAsync(y, d.px, sizeof(double) * (size_t)cd.n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -3684,19 +3687,22 @@ int xrsfm_ba_debug_reduced_system(xrsfm_ba_context* c, double radius, int32_t fa
 int xrsfm_ba_debug_backsub(xrsfm_ba_context* c, double* part_model, double* part_step2, double* cand_points, double* point_step,
                            double* cand_cam_q, double* cand_cam_t) {
     if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
-    if (!c || c->wide) return XRSFM_BA_EINVAL;
-    // needs the camera part of a step (d.px) and the radius / point factors it was assembled with: without a preceding
-    // xrsfm_ba_debug_cholesky_solve of the SAME linearisation the kernel would read uninitialised Hinv / px (or divide by a zero radius)
+    if (!c) return XRSFM_BA_EINVAL;
+    // needs the camera part of a step (d.px; bal9: w.px) and the radius / point factors it was assembled with: without a preceding
+    // xrsfm_ba_debug_cholesky_solve (bal9: xrsfm_ba_debug_wide with y) of the SAME linearisation the kernel would read uninitialised
+    // Hinv / px (or divide by a zero radius)
     if (!c->linearized || !c->chol.ready || !c->step_valid) return XRSFM_BA_ESTATE;
     HIPCHK(hipSetDevice(c->device));
     Dev& d = c->d;
     const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cdiv(d.n_cams, kBlock);
     if (nbi + nbc > 0) {
-        if (c->step_prep) hipLaunchKernelGGL(k_backsub<true>, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, nbi, (CamLin*)nullptr, c->step_radius);
+        if (c->wide) hipLaunchKernelGGL(k9_backsub, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, c->w, nbi, c->step_radius);
+        else if (c->step_prep) hipLaunchKernelGGL(k_backsub<true>, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, nbi, (CamLin*)nullptr, c->step_radius);
         else hipLaunchKernelGGL(k_backsub<false>, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, nbi, (CamLin*)nullptr, c->step_radius);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->backsub_done = true;
     const size_t ni = (size_t)d.n_items, np = (size_t)d.n_pts;
     if (part_model && ni) HIPCHK(hipMemcpy(part_model, d.part + 2 * ni, ni * sizeof(double), hipMemcpyDeviceToHost));
     if (part_step2 && ni) HIPCHK(hipMemcpy(part_step2, d.part + 3 * ni, ni * sizeof(double), hipMemcpyDeviceToHost));
@@ -3708,6 +3714,38 @@ int xrsfm_ba_debug_backsub(xrsfm_ba_context* c, double* part_model, double* part
         for (int i = 0; i < d.n_cams; ++i) {
             if (cand_cam_q) for (int j = 0; j < 4; ++j) cand_cam_q[4 * (size_t)i + j] = cams[i].q[j];
             if (cand_cam_t) for (int j = 0; j < 3; ++j) cand_cam_t[3 * (size_t)i + j] = cams[i].t[j];
+        }
+    }
+    return 0;
+}
+
+// What the context holds next to the packed-order outputs of xrsfm_ba_debug_backsub (host- or device-packed alike: pt_orig and the
+// items are on the host either way).  The per-camera partials and the candidate intrinsics are those of the last debug_backsub.
+int xrsfm_ba_debug_backsub_layout(xrsfm_ba_context* c, int32_t* pt_orig, int32_t* item_tiles, double* campart, int32_t flags[2],
+                                  double* cand_intr, double* scale_c, double* scale_p) {
+    if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
+    if (!c) return XRSFM_BA_EINVAL;
+    const Packed& k = c->pk;
+    const Dev& d = c->d;
+    if (pt_orig) for (int j = 0; j < k.n_pts; ++j) pt_orig[j] = k.pt_orig[j];
+    if (item_tiles) for (size_t i = 0; i < k.items.size(); ++i) item_tiles[i] = k.items[i];
+    if (flags) { flags[0] = (c->wide || c->step_prep) ? 1 : 0; flags[1] = (c->wide || d.Jp != nullptr) ? 1 : 0; }
+    if (scale_c || scale_p) {       // the Jacobi scales of the current linearisation (packed point order)
+        if (!c->linearized) return XRSFM_BA_ESTATE;
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const size_t ncw = (size_t)d.n_cams * (c->wide ? kW : 6);
+        if (scale_c && ncw) HIPCHK(hipMemcpy(scale_c, c->wide ? c->w.scale_c : d.scale_c, ncw * sizeof(double), hipMemcpyDeviceToHost));
+        if (scale_p && d.n_pts) HIPCHK(hipMemcpy(scale_p, d.scale_p, 3 * (size_t)d.n_pts * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (campart || cand_intr) {
+        if (!c->step_valid || !c->backsub_done) return XRSFM_BA_ESTATE;
+        HIPCHK(hipSetDevice(c->device));
+        if (campart && d.n_cams) HIPCHK(hipMemcpy(campart, d.campart, 2 * (size_t)d.n_cams * sizeof(double), hipMemcpyDeviceToHost));
+        if (cand_intr && d.n_cams) {
+            std::vector<CamRec> cams(d.n_cams);
+            HIPCHK(hipMemcpy(cams.data(), d.cam_cand, sizeof(CamRec) * (size_t)d.n_cams, hipMemcpyDeviceToHost));
+            for (int i = 0; i < d.n_cams; ++i) for (int j = 0; j < 3; ++j) cand_intr[3 * (size_t)i + j] = cams[i].intr[j];
         }
     }
     return 0;
