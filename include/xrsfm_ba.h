@@ -361,6 +361,48 @@ int xrsfm_ba_device_memory(int device, uint64_t *free_bytes, uint64_t *total_byt
  * the call that replaces ceres::Solve(options, &problem, &summary). */
 int xrsfm_ba_solve(const xrsfm_ba_options *opt, xrsfm_ba_problem *problem, xrsfm_ba_summary *summary);
 
+/* Many local-BA-sized problems in ONE launch: every context of ctxs [n_ctx] gets exactly the result (bit for bit: state and every
+ * summary field but the times) of its own xrsfm_ba_run with XRSFM_BA_SOLVER_RESIDENT, whatever its position in the batch and
+ * whatever else is in it: windows of a trajectory after a loop correction, the sub-maps of a partitioned reconstruction, the
+ * candidates of a local BA.  One `opt` for the whole batch; opt->linear_solver must be XRSFM_BA_SOLVER_RESIDENT.
+ * summaries [n_ctx]: filled like xrsfm_ba_run fills them; total_time_s is the wall time of the whole call, the same value in every
+ * summary; with profile != 0 dom_kernel_ms is the HIP-event time of the one launch and dom_kernel_launches is 1, and
+ * xrsfm_ba_profile_entry of the FIRST context lists k_lba_resident with that one launch (the other contexts list nothing).
+ * codes [n_ctx] (may be NULL): 0, or XRSFM_BA_EINVAL for a problem the kernel refused (below).  With verbose != 0 the progress
+ * tables are printed one after another in index order, each under a line "problem <index>".
+ *
+ * How: the resident kernel has one workgroup and nothing in it waits for another, so N problems are N workgroups of one grid
+ * (xrsfm_amd/csrc/ba_lba.h: k_lba_batch): no protocol between workgroups, no floating-point atomics, every loop bounded as in the
+ * single launch.  The contexts' streams are drained; the kernel's descriptors of the contexts and the launch order (problems by
+ * descending tile count, ties by index: with more problems than compute units the longest start first) are uploaded from one
+ * pinned block; one launch on the first context's stream; one pinned block of results (and, with verbose, iteration rows) is read
+ * back.  One workgroup occupies one compute unit (157.6 KiB of LDS): a batch is as fast as its longest problem up to 256 problems
+ * on an MI355X and proceeds in waves beyond.  Afterwards every context holds what a _CHOLESKY run would have left: download,
+ * reset, a further run with any solver and the covariance calls work on it unchanged.  Measured against n_ctx sequential _CHOLESKY
+ * runs on the same contexts (profiles/lba_batch.md): 7 cameras / 6000 observations: 3.9 against 5.9 ms at 16 problems, 4.2 against
+ * 92.9 ms at 256, 16.3 against 359 ms at 1024 (22 x); 5 cameras / 600 observations: 0.52 against 5.0 ms at 16, 0.72 against 82.9 ms
+ * at 256 (115 x); crossover near 11 and 2 problems.  A batch of ONE is XRSFM_BA_SOLVER_RESIDENT again: slower than the engine.
+ *
+ * Errors, checked before anything is launched or written (one line on stderr naming the first offending index; every context's
+ * state, summaries and codes stay untouched): XRSFM_BA_EINVAL — n_ctx < 0 or above XRSFM_BA_BATCH_MAX, a NULL ctxs / opt /
+ * summaries with n_ctx > 0, another linear_solver, a NULL entry, the same context twice, contexts on different devices, a context
+ * XRSFM_BA_SOLVER_RESIDENT refuses (bal9, communicator or test hook, more than 10 cameras, more than 32768 observations, negative
+ * max_iterations); XRSFM_BA_ESTATE — a poisoned context.  n_ctx == 0 is success, touches nothing, needs no device and is checked
+ * first.  Found by the kernel: a track observed twice by one camera — before anything of THAT problem's state is written; it gets
+ * codes[i] = XRSFM_BA_EINVAL and an all-zero summary, its state stays untouched, the other problems are solved, and the call
+ * returns XRSFM_BA_EINVAL: the batch is then PARTLY ADVANCED, and codes says where (pass it whenever a duplicate observation is
+ * possible).  XRSFM_BA_ENODEV: the HIP runtime reported an error; XRSFM_BA_ENOMEM: no staging memory.
+ * Not built: per-problem options, an adapter method, contexts on several devices, bal9. */
+#define XRSFM_BA_BATCH_MAX 4096
+int xrsfm_ba_run_batch(int32_t n_ctx, xrsfm_ba_context *const *ctxs, const xrsfm_ba_options *opt,
+                       xrsfm_ba_summary *summaries /* [n_ctx] */, int32_t *codes /* [n_ctx], may be NULL */);
+/* One-shot convenience = xrsfm_ba_create for each problem (device 0) + xrsfm_ba_run_batch + xrsfm_ba_download into each problem's
+ * {cam_q, cam_t, points} + destroy.  A problem whose create fails (codes[i] = that code, summary zeroed) or that the kernel refuses
+ * (codes[i] = XRSFM_BA_EINVAL) keeps its arrays untouched while the others are solved; the call then returns the first such code.
+ * On a failing host check of xrsfm_ba_run_batch no array, summary or code of any problem is touched. */
+int xrsfm_ba_solve_batch(const xrsfm_ba_options *opt, int32_t n_problems, xrsfm_ba_problem *problems,
+                         xrsfm_ba_summary *summaries /* [n_problems] */, int32_t *codes /* [n_problems], may be NULL */);
+
 /* Pose-only refinement of one frame against fixed 3-D points: the "pose estimate [refine]" block of RegisterImage
  * (/root/reference/src/geometry/pnp.cc:38-71): one ReProjectionCost + HuberLoss(5.99) per inlier correspondence, points
  * and intrinsics constant, EigenQuaternionParameterization on q, ceres::Solver::Options defaults with

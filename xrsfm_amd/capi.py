@@ -91,7 +91,7 @@ EXPORTS = [
     "xrsfm_tag_default_options", "xrsfm_tag_refine", "xrsfm_ba_refine_poses", "xrsfm_ba_quiesce", "xrsfm_ba_debug_backsub", "xrsfm_ba_device_memory", "xrsfm_ba_download_intrinsics", "xrsfm_ba_debug_wide",
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
-    "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout",
+    "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -112,6 +112,8 @@ def _facts(v) -> dict:
 
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
 SOLVER_RESIDENT = 3     # the whole LM loop in one kernel launch (local-BA-sized problems: include/xrsfm_ba.h)
+BATCH_MAX = 4096        # XRSFM_BA_BATCH_MAX: most contexts of one xrsfm_ba_run_batch
+EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
           -4: "ECOMM", -5: "ESTATE", -6: "ETOOBIG", -7: "EINTERNAL (unexpected exception inside the library)",
@@ -201,6 +203,10 @@ def load(path: str | None = None):
     lib.xrsfm_ba_joint_covariance.restype = C.c_int
     lib.xrsfm_ba_map_covariance.argtypes = [vp, C.c_double, _c_double_p, _c_double_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
     lib.xrsfm_ba_map_covariance.restype = C.c_int
+    lib.xrsfm_ba_run_batch.argtypes = [C.c_int32, C.POINTER(vp), C.POINTER(COptions), C.POINTER(CSummary), _c_int32_p]
+    lib.xrsfm_ba_run_batch.restype = C.c_int
+    lib.xrsfm_ba_solve_batch.argtypes = [C.POINTER(COptions), C.c_int32, C.POINTER(CProblem), C.POINTER(CSummary), _c_int32_p]
+    lib.xrsfm_ba_solve_batch.restype = C.c_int
     _lib = lib
     return lib
 
@@ -565,6 +571,36 @@ def solve(problem: ProblemArrays, options: COptions | None = None) -> CSummary:
     cs = problem.c_struct()
     check(load().xrsfm_ba_solve(C.byref(options), C.byref(cs), C.byref(s)), "xrsfm_ba_solve")
     return s
+
+
+def run_batch(contexts, options: COptions, n_ctx: int | None = None):
+    """xrsfm_ba_run_batch: every Context of `contexts` solved by XRSFM_BA_SOLVER_RESIDENT in ONE launch (options.linear_solver must
+    be SOLVER_RESIDENT).  Returns (code, [summary per context], codes): the call does not raise, because with code EINVAL the batch
+    may be partly advanced and `codes` (int32 per context: 0 or EINVAL) says where.  An entry may be None (a NULL pointer), and
+    n_ctx overrides the count handed to the library (both for the argument checks; the array holds max(n_ctx, len) entries, the
+    tail repeating the last one)."""
+    lib = load()
+    hs = [None if c is None else c._h for c in contexts]
+    n = len(hs) if n_ctx is None else int(n_ctx)
+    m = max(n, len(hs), 1)
+    arr = (C.c_void_p * m)(*(hs + [hs[-1] if hs else None] * (m - len(hs))))
+    sums = (CSummary * m)()
+    codes = np.zeros(m, np.int32)
+    code = lib.xrsfm_ba_run_batch(n, arr, C.byref(options), sums, codes.ctypes.data_as(_c_int32_p))
+    k = max(min(n, m), 0)
+    return code, [sums[i] for i in range(k)], codes[:k]
+
+
+def solve_batch(problems, options: COptions):
+    """One-shot xrsfm_ba_solve_batch: results are written into every problem's cam_q / cam_t / points; a problem whose code is
+    non-zero keeps its arrays.  Returns (code, [summary per problem], codes) like run_batch."""
+    lib = load()
+    n = len(problems)
+    cs = (CProblem * max(n, 1))(*[p.c_struct() for p in problems])
+    sums = (CSummary * max(n, 1))()
+    codes = np.zeros(max(n, 1), np.int32)
+    code = lib.xrsfm_ba_solve_batch(C.byref(options), n, cs, sums, codes.ctypes.data_as(_c_int32_p))
+    return code, [sums[i] for i in range(n)], codes[:n]
 
 
 def filter_tracks(problem: ProblemArrays, max_reproj_error: float, min_tri_angle_rad: float) -> dict:

@@ -9,7 +9,8 @@
 // tracks per tile, lane = observation.
 //
 // One workgroup of kLbaBlock threads = kLbaWaves waves; there is no other workgroup and therefore nothing to wait for: every
-// loop is bounded by the tile count, the camera count or max_iterations.
+// loop is bounded by the tile count, the camera count or max_iterations.  For the same reason N problems run as N workgroups of
+// one launch (k_lba_batch at the end of this file, xrsfm_ba_run_batch): both kernels call lba_resident_solve.
 //
 //   pass A (lba_linearize): a chunk = kLbaWaves tiles, one per wave.  Every lane forms r, F (2x6), E (2x3) of its observation;
 //     H_pp / g_p per track by segmented wave sums; the head lane factors the damped point block (H_pp + D^2)^-1 = C C^T and
@@ -468,8 +469,10 @@ __device__ __forceinline__ void lba_backsub(const LbaDev& d, LbaSm& sm, const do
     lba_block_reduce<3>(sm, tot, 0u, sm.tot);
 }
 
-__global__ __launch_bounds__(kLbaBlock) void k_lba_resident(LbaDev d, LbaOpt opt, LbaResult* __restrict__ result, LbaRow* __restrict__ rows) {
-    __shared__ __attribute__((aligned(16))) double lba_smem[kLbaSmemBytes / 8];        // static: the code object states the whole group segment
+// The whole solve of ONE problem by ONE workgroup on the LDS block lba_smem (kLbaSmemBytes): what both kernels below run.  Reads
+// and writes nothing but the arrays of d, *result and rows[0 .. max_it].
+__device__ __forceinline__ void lba_resident_solve(const LbaDev& d, const LbaOpt& opt, LbaResult* __restrict__ result, LbaRow* __restrict__ rows,
+                                                   double* __restrict__ lba_smem) {
     LbaSm& sm = *reinterpret_cast<LbaSm*>(lba_smem + kLbaOffSm);
     const int tid = threadIdx.x;
     const int nc = d.n_cams, n = 6 * nc;
@@ -639,6 +642,24 @@ __global__ __launch_bounds__(kLbaBlock) void k_lba_resident(LbaDev d, LbaOpt opt
         *result = r;
         __threadfence_system();
     }
+}
+
+__global__ __launch_bounds__(kLbaBlock) void k_lba_resident(LbaDev d, LbaOpt opt, LbaResult* __restrict__ result, LbaRow* __restrict__ rows) {
+    __shared__ __attribute__((aligned(16))) double lba_smem[kLbaSmemBytes / 8];        // static: the code object states the whole group segment
+    lba_resident_solve(d, opt, result, rows, lba_smem);
+}
+
+// N independent problems as N workgroups of one launch (xrsfm_ba_run_batch): workgroup b solves problem p = order[b] (the host's
+// permutation by descending tile count, so that the longest start first when the grid exceeds the compute units) with the
+// descriptor devs[p], and writes results[p] and, with opt.want_rows, rows[p * rows_stride ...].  A workgroup touches nothing of
+// another problem and waits for none: every loop is bounded as in the single launch, whose arithmetic this is instruction for
+// instruction.  The descriptor is read once, at a workgroup-uniform address.
+__global__ __launch_bounds__(kLbaBlock) void k_lba_batch(const LbaDev* __restrict__ devs, const int* __restrict__ order, LbaOpt opt,
+                                                         LbaResult* __restrict__ results, LbaRow* __restrict__ rows, int rows_stride) {
+    __shared__ __attribute__((aligned(16))) double lba_smem[kLbaSmemBytes / 8];
+    const int p = order[blockIdx.x];
+    const LbaDev d = devs[p];
+    lba_resident_solve(d, opt, results + p, rows + (size_t)p * (size_t)rows_stride, lba_smem);
 }
 
 }  // namespace xba

@@ -2694,14 +2694,28 @@ static int assemble_wide(xrsfm_ba_context* c, double radius) {
 // XRSFM_BA_SOLVER_RESIDENT (ba_lba.h): the LM loop of ba_run_impl below as one launch of one workgroup.  The options travel as
 // kernel arguments, the result block (summary fields, then the iteration rows when asked) is written by the kernel straight into
 // a pinned block and read after the stream has drained.  Every refusal happens before anything of the state is written.
+static const char* lba_refusal(const xrsfm_ba_context* c, const xrsfm_ba_options& opt) {
+    const Dev& d = c->d;
+    if (c->wide) return "a bal9 context (9-wide camera blocks)";
+    if (c->multi()) return "a context with a communicator or the test hook (one rank only)";
+    if (d.n_cams > kLbaMaxCams) return "more than 10 cameras (the reduced system must be one 64x64 tile)";
+    if (c->pk.n_obs > kLbaMaxObs) return "more than 32768 observations";
+    if (d.n_slots != d.n_tiles * kWave || opt.max_iterations < 0) return "an unexpected packing or a negative max_iterations";
+    return nullptr;
+}
+
+static void lba_fill_summary(const xrsfm_ba_context* c, const LbaResult& r, xrsfm_ba_summary* sum) {
+    sum->linear_solver_used = XRSFM_BA_SOLVER_RESIDENT;
+    sum->num_residuals = 2 * c->pk.n_obs;
+    sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p);
+    sum->initial_cost = r.initial_cost; sum->final_cost = r.final_cost;
+    sum->n_successful = r.n_successful; sum->n_unsuccessful = r.n_unsuccessful;
+    sum->termination = r.termination; sum->termination_reason = r.reason; sum->lm_steps_attempted = r.attempted;
+}
+
 static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_summary* sum) {
     Dev& d = c->d;
-    const char* why = nullptr;
-    if (c->wide) why = "a bal9 context (9-wide camera blocks)";
-    else if (c->multi()) why = "a context with a communicator or the test hook (one rank only)";
-    else if (d.n_cams > kLbaMaxCams) why = "more than 10 cameras (the reduced system must be one 64x64 tile)";
-    else if (c->pk.n_obs > kLbaMaxObs) why = "more than 32768 observations";
-    else if (d.n_slots != d.n_tiles * kWave || opt.max_iterations < 0) why = "an unexpected packing or a negative max_iterations";
+    const char* why = lba_refusal(c, opt);
     if (why) {
         fprintf(stderr, "[xrsfm_ba] XRSFM_BA_SOLVER_RESIDENT is not available for %s\n", why);
         return XRSFM_BA_EINVAL;
@@ -2732,12 +2746,7 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
         e = XRSFM_BA_EINVAL;
     }
     if (!e) {
-        sum->linear_solver_used = XRSFM_BA_SOLVER_RESIDENT;
-        sum->num_residuals = 2 * c->pk.n_obs;
-        sum->num_effective_params = 3 * (c->pk.n_var_q + c->pk.n_var_t + c->pk.n_var_p);
-        sum->initial_cost = r.initial_cost; sum->final_cost = r.final_cost;
-        sum->n_successful = r.n_successful; sum->n_unsuccessful = r.n_unsuccessful;
-        sum->termination = r.termination; sum->termination_reason = r.reason; sum->lm_steps_attempted = r.attempted;
+        lba_fill_summary(c, r, sum);
         for (int i = 0; i < r.n_rows && (size_t)i < n_rows_max; ++i)
             print_progress(opt, rows[i].it, rows[i].cost, rows[i].change, rows[i].gmax, rows[i].step, rows[i].rho, rows[i].radius);
         sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
@@ -2750,6 +2759,169 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     c->profiling = false;
     g_pinned.put(host, cap);
     return e;
+}
+
+// xrsfm_ba_run_batch: n contexts, each eligible for lba_run, as n workgroups of ONE launch (ba_lba.h: k_lba_batch).  Every host
+// check comes first and leaves everything untouched; then the descriptors and the launch order travel in one pinned block, the
+// kernel writes one LbaResult per problem (and the iteration rows with verbose) straight into pinned memory, and every context
+// gets the bookkeeping of lba_run.  `label` (may be NULL): the caller's index of every context for the messages (solve_batch
+// drops the problems whose create failed).  *launched: whether the call got past the host checks.
+static int lba_run_batch(int32_t n, xrsfm_ba_context* const* ctxs, const xrsfm_ba_options* optp, xrsfm_ba_summary* sums, int32_t* codes,
+                         const int32_t* label, bool* launched) {
+    if (launched) *launched = false;
+    if (n == 0) return XRSFM_BA_OK;
+    if (n < 0 || n > XRSFM_BA_BATCH_MAX) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_run_batch: %d contexts (0 .. %d are possible)\n", (int)n, XRSFM_BA_BATCH_MAX);
+        return XRSFM_BA_EINVAL;
+    }
+    if (!ctxs || !optp || !sums) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_run_batch: NULL %s\n", !ctxs ? "ctxs" : (!optp ? "opt" : "summaries"));
+        return XRSFM_BA_EINVAL;
+    }
+    const xrsfm_ba_options opt = *optp;
+    if (opt.linear_solver != XRSFM_BA_SOLVER_RESIDENT) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_run_batch: linear_solver must be XRSFM_BA_SOLVER_RESIDENT\n");
+        return XRSFM_BA_EINVAL;
+    }
+    auto name = [&](int i) { return label ? (int)label[i] : i; };
+    {
+        std::vector<const xrsfm_ba_context*> seen(ctxs, ctxs + n);
+        std::sort(seen.begin(), seen.end());
+        for (int i = 0; i < n; ++i) {
+            const xrsfm_ba_context* c = ctxs[i];
+            const char* why = nullptr;
+            int code = XRSFM_BA_EINVAL;
+            if (!c) why = "a NULL entry";
+            else if (c->poisoned) { why = "a poisoned context"; code = XRSFM_BA_ESTATE; }
+            else if (c->device != ctxs[0]->device) why = "a context on another device than the first";
+            else if (std::upper_bound(seen.begin(), seen.end(), c) - std::lower_bound(seen.begin(), seen.end(), c) > 1) why = "a context that is in the batch twice";
+            else why = lba_refusal(c, opt);
+            if (why) {
+                fprintf(stderr, "[xrsfm_ba] xrsfm_ba_run_batch: context %d: not available for %s\n", name(i), why);
+                return code;
+            }
+        }
+    }
+    if (launched) *launched = true;
+    const auto t_begin = std::chrono::steady_clock::now();
+    xrsfm_ba_context* c0 = ctxs[0];
+    const int device = c0->device;
+    HIPCHK(hipSetDevice(device));
+    for (int i = 0; i < n; ++i) HIPCHK(hipStreamSynchronize(ctxs[i]->stream));        // nothing of an earlier call is in flight
+    // one pinned block: descriptors | order (uploaded)  ||  results | rows (written by the kernel)
+    const int rows_stride = opt.verbose ? opt.max_iterations + 1 : 0;
+    static_assert(sizeof(LbaDev) % 8 == 0 && sizeof(LbaResult) % 8 == 0 && sizeof(LbaRow) % 8 == 0, "staging layout");
+    const size_t off_order = sizeof(LbaDev) * (size_t)n;
+    const size_t off_res = (off_order + sizeof(int) * (size_t)n + 255) & ~(size_t)255;
+    const size_t off_rows = off_res + sizeof(LbaResult) * (size_t)n;
+    const size_t total = off_rows + sizeof(LbaRow) * (size_t)rows_stride * (size_t)n;
+    struct Pin { unsigned char* p = nullptr; size_t cap = 0; ~Pin() { if (p) g_pinned.put(p, cap); } } stage;
+    stage.p = static_cast<unsigned char*>(g_pinned.get(total, &stage.cap));
+    if (!stage.p) return XRSFM_BA_ENOMEM;
+    size_t cls = 0;
+    unsigned char* dev = static_cast<unsigned char*>(g_cache.get(device, off_res, &cls));
+    if (!dev) return XRSFM_BA_ENOMEM;
+    LbaDev* h_devs = reinterpret_cast<LbaDev*>(stage.p);
+    int* h_order = reinterpret_cast<int*>(stage.p + off_order);
+    LbaResult* res = reinterpret_cast<LbaResult*>(stage.p + off_res);
+    LbaRow* rows = reinterpret_cast<LbaRow*>(stage.p + off_rows);
+    memset(stage.p, 0, off_rows);
+    for (int i = 0; i < n; ++i) {
+        xrsfm_ba_context* c = ctxs[i];
+        h_devs[i] = lba_dev(c->d);
+        h_order[i] = i;
+        res[i].status = -1;
+        c->profiling = false;
+        for (int k = 0; k < K_COUNT; ++k) { c->prof_ms[k] = 0.0; c->prof_n[k] = 0; }
+        c->recs.clear(); c->ev_used = 0;
+        c->linearized = false; c->step_valid = false; c->gradmax_done = false; c->published = false;
+        if (codes) codes[i] = XRSFM_BA_OK;
+    }
+    // the longest problems first (ties by index): with more problems than compute units the tail of the launch is the short ones
+    std::stable_sort(h_order, h_order + n, [&](int a, int b) { return h_devs[a].n_tiles > h_devs[b].n_tiles; });
+    const LbaOpt lo{opt.max_iterations, opt.verbose ? 1 : 0, opt.function_tolerance, opt.parameter_tolerance, opt.gradient_tolerance,
+                    opt.initial_radius, opt.huber_a};
+    c0->profiling = opt.profile != 0;
+    hipLaunchKernelGGL(k_copy_words, dim3(cdiv((long long)(off_res / 8), 256)), dim3(256), 0, c0->stream, reinterpret_cast<const double*>(stage.p),
+                       reinterpret_cast<double*>(dev), off_res / 8);
+    LAUNCH(c0, K_LBA, k_lba_batch, dim3(n), dim3(kLbaBlock), 0, reinterpret_cast<const LbaDev*>(dev), reinterpret_cast<const int*>(dev + off_order), lo,
+           res, rows, rows_stride);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = (hipStreamSynchronize(c0->stream) == hipSuccess) && ok;
+    g_cache.put(device, dev, cls);
+    for (int i = 0; ok && i < n; ++i) ok = res[i].status >= 0;
+    int e = ok ? XRSFM_BA_OK : XRSFM_BA_ENODEV;
+    if (!e) {
+        if (c0->profiling) profile_collect(c0);
+        for (int i = 0; i < n; ++i) {
+            memset(sums + i, 0, sizeof(sums[i]));
+            if (res[i].status == 1) {
+                fprintf(stderr, "[xrsfm_ba] xrsfm_ba_run_batch: context %d: not available for a track observed twice by one camera: use xrsfm_ba_run with AUTO or PCG\n", name(i));
+                if (codes) codes[i] = XRSFM_BA_EINVAL;
+                e = XRSFM_BA_EINVAL;
+                continue;
+            }
+            lba_fill_summary(ctxs[i], res[i], sums + i);
+            if (opt.verbose) {
+                printf("problem %d\n", name(i));
+                const LbaRow* w = rows + (size_t)i * rows_stride;
+                for (int k = 0; k < res[i].n_rows && k < rows_stride; ++k)
+                    print_progress(opt, w[k].it, w[k].cost, w[k].change, w[k].gmax, w[k].step, w[k].rho, w[k].radius);
+            }
+        }
+        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+        for (int i = 0; i < n; ++i) {
+            if (res[i].status != 0) continue;
+            sums[i].total_time_s = secs;
+            if (c0->profiling) { sums[i].dom_kernel_id = K_LBA; sums[i].dom_kernel_ms = c0->prof_ms[K_LBA]; sums[i].dom_kernel_launches = c0->prof_n[K_LBA]; }
+        }
+    }
+    c0->recs.clear(); c0->ev_used = 0;
+    c0->profiling = false;
+    return e;
+}
+
+static int lba_solve_batch(const xrsfm_ba_options* opt, int32_t n, xrsfm_ba_problem* problems, xrsfm_ba_summary* sums, int32_t* codes) {
+    if (n == 0) return XRSFM_BA_OK;
+    if (n < 0 || n > XRSFM_BA_BATCH_MAX || !opt || !problems || !sums) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_solve_batch: a NULL argument or %d problems (0 .. %d are possible)\n", (int)n, XRSFM_BA_BATCH_MAX);
+        return XRSFM_BA_EINVAL;
+    }
+    if (opt->linear_solver != XRSFM_BA_SOLVER_RESIDENT) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_solve_batch: linear_solver must be XRSFM_BA_SOLVER_RESIDENT\n");
+        return XRSFM_BA_EINVAL;
+    }
+    struct Owned {          // (destroyed on every way out)
+        std::vector<xrsfm_ba_context*> v;
+        ~Owned() { for (xrsfm_ba_context* c : v) xrsfm_ba_destroy(c); }
+    } live;
+    std::vector<int32_t> index, create_code(n, 0);
+    int first = XRSFM_BA_OK;
+    for (int i = 0; i < n; ++i) {
+        xrsfm_ba_context* c = nullptr;
+        const int e = xrsfm_ba_create(problems + i, 0, &c);
+        create_code[i] = e;
+        if (e) { if (!first) first = e; continue; }
+        live.v.push_back(c); index.push_back(i);
+    }
+    const int m = (int)live.v.size();
+    std::vector<xrsfm_ba_summary> s(m);
+    std::vector<int32_t> k(m, 0);
+    bool launched = false;
+    const int e = lba_run_batch(m, live.v.data(), opt, s.data(), k.data(), index.data(), &launched);
+    if (m > 0 && !launched) return e;                   // a host check failed: nothing was written anywhere
+    if (e && e != XRSFM_BA_EINVAL) return e;            // (a HIP error)
+    for (int i = 0; i < n; ++i) { memset(sums + i, 0, sizeof(sums[i])); if (codes) codes[i] = create_code[i]; }
+    int dl = XRSFM_BA_OK;
+    for (int j = 0; j < m; ++j) {
+        const int i = index[j];
+        if (codes) codes[i] = k[j];
+        if (k[j]) continue;
+        sums[i] = s[j];
+        const int e2 = xrsfm_ba_download(live.v[j], problems[i].cam_q, problems[i].cam_t, problems[i].points);
+        if (e2 && !dl) dl = e2;
+    }
+    return first ? first : (e ? e : dl);
 }
 
 static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) {
@@ -3815,6 +3987,12 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 
 // ---------------------------------------------------------------- exception barrier of the entry points that allocate on the host
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
+int xrsfm_ba_run_batch(int32_t n_ctx, xrsfm_ba_context* const* ctxs, const xrsfm_ba_options* opt, xrsfm_ba_summary* summaries, int32_t* codes) {
+    return no_throw([&] { return lba_run_batch(n_ctx, ctxs, opt, summaries, codes, nullptr, nullptr); });
+}
+int xrsfm_ba_solve_batch(const xrsfm_ba_options* opt, int32_t n_problems, xrsfm_ba_problem* problems, xrsfm_ba_summary* summaries, int32_t* codes) {
+    return no_throw([&] { return lba_solve_batch(opt, n_problems, problems, summaries, codes); });
+}
 int xrsfm_ba_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) { return no_throw([&] { return covariance_impl(c, huber_a, n_sel, cam_sel, cov); }); }
 int xrsfm_ba_point_covariance(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) { return no_throw([&] { return point_covariance_impl(c, huber_a, n_sel, pt_sel, cov); }); }
 int xrsfm_ba_map_covariance(xrsfm_ba_context* c, double huber_a, double* cam_cov, double* pt_cov, uint8_t* cam_status, uint8_t* pt_status) {
