@@ -199,6 +199,55 @@ def test_kernel_against_fallback(lib, tmp_path):
         assert Jy.entry_err(F, want) <= Jy.tolerance(eps) and Jy.entry_err(G, want) <= Jy.tolerance(eps)
 
 
+_FB_SEL = {"const_q": [5, 17, 33], "ring12": [2, 7, 11]}          # (const_q: level plan, camera 17 rotation-constant; ring12: panel plan)
+_FB_CHILD = textwrap.dedent("""
+    import sys, numpy as np
+    sys.path.insert(0, %r)
+    import torch  # noqa: F401
+    from tests import cov_joint_yardstick as Jy
+    from tests import helpers as H
+    from xrsfm_amd import capi
+    out = {}
+    for spec in sys.argv[2:]:
+        name, cams = spec.split(":")[0], [int(v) for v in spec.split(":")[1].split(",")]
+        arr = dict(Jy.FIXTURES[name][0]())
+        pts = Jy.observed_points(arr)[[8, 100, 250]]
+        pc = np.array(arr["point_const"], np.uint8, copy=True)
+        pc[pts[1]] = 1
+        arr["point_const"] = pc
+        ctx = capi.Context(H.to_product(arr))
+        out[name + "_joint"] = ctx.joint_covariance(cams, pts)
+        out[name + "_cams"] = ctx.covariance(cams)
+        out[name + "_pts"] = ctx.point_covariance(pts)
+        ctx.close()
+    np.savez(sys.argv[1], **out)
+""")
+
+
+@pytest.mark.gpu
+def test_fallback_marginals_are_joint_diagonal_blocks(lib, tmp_path):
+    """With XRSFM_BA_COV_FALLBACK=1 (a fresh child process) the three calls share one solver: the 6x6 and 3x3 diagonal blocks of the
+    joint matrix are the blocks of the two marginal calls bit for bit (the same right-hand sides reach the same factor-and-solve and
+    the sums run in the same order).  3 cameras and 3 observed points, the second point constant."""
+    assert Jy.FIXTURES["ring12"][1] == "panel" and Jy.FIXTURES["const_q"][1] == "level" and Jy.CONST_Q_CAM in _FB_SEL["const_q"]
+    env = dict(os.environ)
+    env["XRSFM_BA_COV_FALLBACK"] = "1"
+    out = str(tmp_path / "fallback_blocks.npz")
+    specs = [f"{name}:{','.join(str(v) for v in cams)}" for name, cams in _FB_SEL.items()]
+    r = subprocess.run([sys.executable, "-c", _FB_CHILD % ROOT, out] + specs, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fb = np.load(out)
+    for name in _FB_SEL:
+        G, Gc, Gp = fb[name + "_joint"], fb[name + "_cams"], fb[name + "_pts"]
+        assert G.shape == (27, 27) and Gc.shape == (3, 6, 6) and Gp.shape == (3, 3, 3) and np.isfinite(G).all()
+        for i in range(3):
+            assert (G[6 * i:6 * i + 6, 6 * i:6 * i + 6] == Gc[i]).all(), (name, "camera", i)
+            assert (G[18 + 3 * i:21 + 3 * i, 18 + 3 * i:21 + 3 * i] == Gp[i]).all(), (name, "point", i)
+        assert (Gp[1] == 0).all() and (Gp[0] != 0).all() and (Gp[2] != 0).all() and (np.diagonal(Gc, axis1=1, axis2=2)[[0, 2]] > 0).all()
+        if name == "const_q":
+            assert (Gc[1][:3] == 0).all() and (Gc[1][3:, 3:] != 0).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["level40", "ring12"])
 def test_repeatable(lib, name):

@@ -15,7 +15,7 @@
 // of a camera's columns do not depend on which other cameras share its chunk (bit-identical for any selection).
 //
 // Sparsity: column block c of L^-1 is non-zero only on c's tile column and its ancestors in the elimination tree.  The
-// host marks the tile columns a chunk reaches (ba_cov_chunk_lists), gives them compact panel slots and launches, per
+// host marks the tile columns a chunk reaches (cov_build_lists, xrsfm_ba.hip), gives them compact panel slots and launches, per
 // level, one workgroup per reached column with a list of the reached columns j it reads; nothing else is touched.
 #pragma once
 #include "ba_chol.h"

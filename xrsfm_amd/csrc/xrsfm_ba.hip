@@ -1575,16 +1575,55 @@ static void cov_build_lists(const CholHost& h, const std::vector<std::vector<int
     }
 }
 
-// What the camera and the point call share.  cov_front: set-up of the factorisation, the selection's own test (sel_check, with the
-// constant bits and the activity of the cameras on the host), the linearisation at the current state like the first iteration of a
-// run (Jacobi scaling from the unscaled column norms), the undamped point blocks and the zero damping.
+// ---- the host steps the four calls are composed of
+// Who is refused before anything is looked at: no context, a poisoned one, the wide model and multi-rank contexts.
+static int cov_refusal(const xrsfm_ba_context* c) {
+    if (!c) return XRSFM_BA_EINVAL;
+    if (c->poisoned) return XRSFM_BA_ESTATE;
+    return (c->wide || c->multi()) ? XRSFM_BA_EINVAL : 0;
+}
+
+// A selection's indices: each in [0, limit), none twice.
+static int cov_check_indices(const int32_t* sel, int n, int limit) {
+    if (n == 0) return 0;
+    std::vector<char> seen((size_t)std::max(limit, 1), 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = sel[i];
+        if (s < 0 || s >= limit || seen[s]) return XRSFM_BA_EINVAL;
+        seen[s] = 1;
+    }
+    return 0;
+}
+
+// What a call selects, as the caller numbers it, checked before any device work.  packed_of: caller's point -> packed point
+// (only points with an observation are packed; -1: none), filled when points are selected.
+struct CovSel {
+    int n_cs = 0; const int32_t* cam_sel = nullptr;
+    int n_ps = 0; const int32_t* pt_sel = nullptr;
+    std::vector<int> packed_of;
+};
+static int cov_select(const xrsfm_ba_context* c, int n_cs, const int32_t* cam_sel, int n_ps, const int32_t* pt_sel, CovSel& S) {
+    const int Np = c->n_points_caller;
+    if (int e = cov_check_indices(cam_sel, n_cs, c->d.n_cams)) return e;
+    if (int e = cov_check_indices(pt_sel, n_ps, Np)) return e;
+    S.n_cs = n_cs; S.cam_sel = cam_sel; S.n_ps = n_ps; S.pt_sel = pt_sel;
+    if (n_ps > 0) {
+        S.packed_of.assign((size_t)std::max(Np, 1), -1);
+        for (size_t j = 0; j < c->pk.pt_orig.size(); ++j) S.packed_of[c->pk.pt_orig[j]] = (int)j;
+    }
+    return 0;
+}
+
+// cov_front: set-up of the factorisation, the selection's own test (with the constant bits and the activity of the cameras on
+// the host), the linearisation at the current state like the first iteration of a run (Jacobi scaling from the unscaled column
+// norms), the undamped point blocks and the zero damping.
 struct CovFront {
     std::vector<unsigned char> cc; std::vector<double> act;
     bool fallback = false;
     bool dof_const(int cam, int a) const { return (a < 3 ? (cc[cam] & 1u) : (cc[cam] & 2u)) != 0; }
+    bool cam_const(int cam) const { return (cc[cam] & 3u) == 3u; }      // an all-constant camera: zero rows of W_p
 };
-template <typename Check>
-static int cov_front(xrsfm_ba_context* c, double huber_a, CovFront& f, Check&& sel_check) {
+static int cov_front(xrsfm_ba_context* c, double huber_a, CovFront& f, const CovSel& S) {
     Dev& d = c->d;
     CholHost& h = c->chol;
     const int Nc = d.n_cams;
@@ -1594,7 +1633,8 @@ static int cov_front(xrsfm_ba_context* c, double huber_a, CovFront& f, Check&& s
     f.cc.resize((size_t)Nc); f.act.resize((size_t)Nc);
     HIPCHK(hipMemcpy(f.cc.data(), d.cam_const, (size_t)Nc, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(f.act.data(), d.cam_act, sizeof(double) * (size_t)Nc, hipMemcpyDeviceToHost));
-    if ((e = sel_check())) return e;
+    for (int i = 0; i < S.n_cs; ++i) if (!(f.act[S.cam_sel[i]] > 0.0)) return XRSFM_BA_ESINGULAR;      // no observation: no information
+    for (int i = 0; i < S.n_ps; ++i) if (S.packed_of[S.pt_sel[i]] < 0) return XRSFM_BA_ESINGULAR;
     if ((e = use_stored_j(c, !jfree_for_run(c, XRSFM_BA_SOLVER_CHOLESKY)))) return e;
     if ((e = init_scaling_and_linearize(c, huber_a, true))) return e;
     if ((e = fetch_scalars(c))) return e;
@@ -1638,95 +1678,13 @@ static int cov_factor(xrsfm_ba_context* c, std::vector<double>& x, const std::ve
     return cov_solution_status(c, x);
 }
 
-int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) {
-    if (!c) return XRSFM_BA_EINVAL;
-    if (c->poisoned) return XRSFM_BA_ESTATE;
-    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
-    if (n_sel == 0) return XRSFM_BA_OK;
-    if (!cam_sel || !cov) return XRSFM_BA_EINVAL;
-    Dev& d = c->d;
-    CholHost& h = c->chol;
-    const int Nc = d.n_cams;
-    {
-        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
-        for (int i = 0; i < n_sel; ++i) {
-            const int s = cam_sel[i];
-            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
-            seen[s] = 1;
-        }
-    }
-    int e;
-    CovFront f;
-    if ((e = cov_front(c, huber_a, f, [&] {
-            for (int i = 0; i < n_sel; ++i) if (!(f.act[cam_sel[i]] > 0.0)) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
-            return 0;
-        }))) return e;
-    std::vector<double> sc((size_t)Nc * 6);
-    HIPCHK(hipMemcpy(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost));
-    DevScratch ds;
-    auto dof_const = [&](int cam, int a) { return f.dof_const(cam, a); };
-    std::vector<double> x;
-    std::vector<double> out((size_t)n_sel * 36);      // staged: cov is written only when every value is finite
-    if (f.fallback) {
-        // S x = e_j for the 6 unit vectors of each selected camera with the run path's factor-and-solve; the factorisation
-        // overwrites S, so every solve assembles it again.  Rows c of x are column j of block (c, c).
-        for (int i = 0; i < n_sel; ++i) {
-            const int cam = cam_sel[i];
-            double M[6][6] = {{0.0}};
-            for (int a = 0; a < 6; ++a) {
-                if (dof_const(cam, a)) continue;
-                if ((e = chol_assemble(c, true))) return e;
-                HIPCHK(hipMemsetAsync(h.dev.rhs, 0, sizeof(double) * (size_t)h.dev.n_pad, c->stream));
-                LAUNCH(c, K_SMALL, k_fill, dim3(1), dim3(kBlock), 0, h.dev.rhs + h.cam_off_host[cam] + a, 1.0, (size_t)1);
-                if ((e = chol_factor_solve(c))) return e;
-                if ((e = cov_solution_status(c, x))) return e;
-                for (int b = 0; b < 6; ++b) M[b][a] = x[6 * (size_t)cam + b];
-            }
-            for (int a = 0; a < 6; ++a)
-                for (int b = 0; b < 6; ++b) {
-                    const bool fixed = dof_const(cam, a) || dof_const(cam, b);
-                    out[36 * (size_t)i + 6 * a + b] = fixed ? 0.0 : 0.5 * (M[a][b] + M[b][a]) * (sc[6 * (size_t)cam + a] * sc[6 * (size_t)cam + b]);
-                }
-        }
-    } else {
-        if ((e = cov_factor(c, x))) return e;
-        std::vector<int> order((size_t)n_sel), cams_sorted((size_t)n_sel);
-        for (int i = 0; i < n_sel; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return h.cam_off_host[cam_sel[a]] < h.cam_off_host[cam_sel[b]]; });
-        for (int i = 0; i < n_sel; ++i) cams_sorted[i] = cam_sel[order[i]];
-        CovLists L;
-        std::vector<std::vector<int>> seeds;
-        for (int c0 = 0; c0 < n_sel; c0 += kCovCamsPerChunk) {
-            const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
-            seeds.emplace_back();
-            for (int i = 0; i < nc; ++i) {
-                const int cam = cams_sorted[c0 + i];
-                L.sel_cam.push_back(cam); L.sel_row.push_back(h.cam_off_host[cam]);
-                seeds.back().push_back(h.cam_off_host[cam] / kNB);
-            }
-            for (int i = nc; i < kCovCamsPerChunk; ++i) { L.sel_cam.push_back(-1); L.sel_row.push_back(0); }      // (fixed stride per chunk)
-        }
-        cov_build_lists(h, seeds, L, false);
-        int4* d_ent = nullptr; int2* d_lj = nullptr; int *d_row = nullptr, *d_cam = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
-        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_cam, L.sel_cam)) ||
-            (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n_sel * 36))) return e;
-        size_t li = 0;
-        for (int ch = 0, c0 = 0; c0 < n_sel; ++ch, c0 += kCovCamsPerChunk) {
-            const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
-            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li)
-                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<false>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
-                       (const int*)(d_row + (size_t)ch * kCovCamsPerChunk), nc);
-            LAUNCH(c, K_SMALL, k_cov_gram, dim3(nc), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_cam + (size_t)ch * kCovCamsPerChunk), d_cov + 36 * (size_t)c0);
-        }
-        HIPCHK(hipGetLastError());
-        std::vector<double> hc((size_t)n_sel * 36);
-        HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < n_sel; ++i) memcpy(out.data() + 36 * (size_t)order[i], hc.data() + 36 * (size_t)i, 36 * sizeof(double));
-    }
-    // (a nearly singular S can pass the factorisation and still overflow in Z^T Z: the caller never sees a NaN or an Inf)
+// Staged results reach the caller only when every value of them is finite (a nearly singular S can pass the factorisation and
+// still overflow in Z^T Z: the caller never sees a NaN or an Inf); two arrays are written both or not at all.
+static int cov_publish(const std::vector<double>& out, double* dst, const std::vector<double>& out2 = {}, double* dst2 = nullptr) {
     for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
-    memcpy(cov, out.data(), out.size() * sizeof(double));
+    for (double v : out2) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
+    if (dst) memcpy(dst, out.data(), out.size() * sizeof(double));
+    if (dst2) memcpy(dst2, out2.data(), out2.size() * sizeof(double));
     return XRSFM_BA_OK;
 }
 
@@ -1769,298 +1727,321 @@ static int cov_point_records(xrsfm_ba_context* c, DevScratch& ds, const std::vec
     return 0;
 }
 
+// The free points of a selection (a constant point keeps its all-zero block, rows and columns): sel[] = index in pt_sel, by
+// ascending packed index, sel_pt[] = their packed indices, R = their records (none: well-formed and empty, no device work).
+struct CovPoints {
+    std::vector<int> sel, sel_pt;
+    CovPtRecords R;
+};
+static int cov_free_points(xrsfm_ba_context* c, DevScratch& ds, const CovSel& S, CovPoints& P) {
+    for (int i = 0; i < S.n_ps; ++i) if (!c->pk.pt_const[S.packed_of[S.pt_sel[i]]]) P.sel.push_back(i);
+    std::sort(P.sel.begin(), P.sel.end(), [&](int a, int b) { return S.packed_of[S.pt_sel[a]] < S.packed_of[S.pt_sel[b]]; });
+    for (int i : P.sel) P.sel_pt.push_back(S.packed_of[S.pt_sel[i]]);
+    P.R.rptr.assign(1, 0);
+    return P.sel.empty() ? 0 : cov_point_records(c, ds, P.sel_pt, P.R);
+}
+
+// The fallback (XRSFM_BA_COV_FALLBACK: slow, exact, the A/B oracle of every kernel path).  One factor-and-solve S x = rhs per
+// free column with the run path's factor-and-solve (the factorisation overwrites S, so every solve assembles it again; rhs: a
+// unit vector for a camera's degree of freedom, column a of W_p Hinv_p for a point's), then per group of columns
+// M = the group's rows of [E | -W Hinv]^T S^-1 [E | -W Hinv] (+ Hinv_p), symmetrised and unscaled.  Columns gptr[g] .. gptr[g + 1)
+// are group g; blocks: the dense block of every group, one after the other.  A constant degree of freedom costs no solve and
+// stays zero; neither does a point seen by all-constant cameras only (W_p = 0: x = 0).
+struct CovCol { int pt, cam, a; };      // pt: -1 degree of freedom a of camera cam; -2 nothing (a constant point's place); else a of free point sel[pt]
+static int cov_fallback(xrsfm_ba_context* c, const CovFront& f, const CovPoints& P, const std::vector<CovCol>& cols, const std::vector<int>& gptr,
+                        std::vector<double>& blocks) {
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    const int Nc = d.n_cams, n = (int)P.sel.size(), N = (int)cols.size();
+    const std::vector<int2>& rec = P.R.rec;
+    const std::vector<int>& ro = P.R.ro;
+    const std::vector<int>& rptr = P.R.rptr;
+    int e;
+    DevScratch ds;
+    std::vector<double> blk((size_t)P.R.n_rec * 18), hs((size_t)n * 9), sc((size_t)Nc * 6), rhs((size_t)h.dev.n_pad), scl((size_t)N, 0.0), x, M;
+    int* d_selpt = nullptr; double* d_hs = nullptr;
+    if ((e = ds.put(&d_selpt, P.sel_pt)) || (e = ds.get(&d_hs, (size_t)n * 9))) return e;
+    if (n > 0) {
+        LAUNCH(c, K_SMALL, k_cov_pt_gather, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, d, (const int*)d_selpt, n, d_hs);
+        HIPCHK(hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (P.R.n_rec > 0) HIPCHK(hipMemcpyAsync(blk.data(), P.R.d_blk, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    static const int up[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};      // Hinv in upper storage: 00 01 02 11 12 22
+    for (int j = 0; j < N; ++j) {       // the Jacobi scale of a column; 0: not free
+        const CovCol q = cols[j];
+        if (q.pt == -1) scl[j] = f.dof_const(q.cam, q.a) ? 0.0 : sc[6 * (size_t)q.cam + q.a];
+        else if (q.pt >= 0) scl[j] = hs[9 * (size_t)q.pt + 6 + q.a];
+    }
+    size_t total = 0;
+    for (size_t g = 0; g + 1 < gptr.size(); ++g) total += (size_t)(gptr[g + 1] - gptr[g]) * (gptr[g + 1] - gptr[g]);
+    blocks.assign(total, 0.0);
+    double* out = blocks.data();
+    for (size_t g = 0; g + 1 < gptr.size(); ++g) {
+        const int g0 = gptr[g], G = gptr[g + 1] - g0;
+        M.assign((size_t)G * G, 0.0);
+        for (int j = 0; j < G; ++j) {
+            if (scl[g0 + j] == 0.0) continue;
+            const CovCol cj = cols[g0 + j];
+            bool any = cj.pt < 0;
+            std::fill(rhs.begin(), rhs.end(), 0.0);
+            if (cj.pt < 0) rhs[h.cam_off_host[cj.cam] + cj.a] = 1.0;
+            else
+                for (int q = rptr[cj.pt]; q < rptr[cj.pt + 1]; ++q) {
+                    any = any || !f.cam_const(rec[ro[q]].y);
+                    for (int r = 0; r < 6; ++r) rhs[h.cam_off_host[rec[ro[q]].y] + r] = blk[18 * (size_t)ro[q] + 3 * r + cj.a];
+                }
+            if (any) { if ((e = cov_factor(c, x, &rhs))) return e; }
+            else x.assign((size_t)Nc * 6, 0.0);
+            for (int i = 0; i < G; ++i) {
+                if (scl[g0 + i] == 0.0) continue;
+                const CovCol ci = cols[g0 + i];
+                double u = 0.0;
+                if (ci.pt < 0) u = x[6 * (size_t)ci.cam + ci.a];
+                else
+                    for (int q = rptr[ci.pt]; q < rptr[ci.pt + 1]; ++q)
+                        for (int r = 0; r < 6; ++r) u += blk[18 * (size_t)ro[q] + 3 * r + ci.a] * x[6 * (size_t)rec[ro[q]].y + r];
+                if ((ci.pt < 0) != (cj.pt < 0)) u = -u;
+                else if (ci.pt >= 0 && ci.pt == cj.pt) u += hs[9 * (size_t)ci.pt + up[ci.a][cj.a]];
+                M[(size_t)i * G + j] = u;
+            }
+        }
+        for (int i = 0; i < G; ++i)
+            for (int j = i; j < G; ++j) {
+                const double sij = scl[g0 + i] * scl[g0 + j];
+                const double v = sij == 0.0 ? 0.0 : 0.5 * (M[(size_t)i * G + j] + M[(size_t)j * G + i]) * sij;
+                out[(size_t)i * G + j] = v; out[(size_t)j * G + i] = v;
+            }
+        out += (size_t)G * G;
+    }
+    return 0;
+}
+
+// Chunks of the kernel path: the cameras by elimination row, 10 per chunk, then the free points by the smallest tile column of
+// their observers (then by packed index: their cameras are close in elimination order), 21 per chunk.  The order of cam_sel /
+// pt_sel has no say, and chunking affects no value (ba_cov.h).  co[j] / po[j]: index in cam_sel / in CovPoints::sel of the j-th
+// camera / point in chunk order; chunk_pt: the packed points in that order; L.sel_row / L.sel_cam: a fixed stride per camera chunk.
+struct CovPlan {
+    CovLists L;
+    std::vector<std::vector<int>> seeds;
+    std::vector<int> co, po, chunk_pt;
+    std::vector<int4> sc_ent; std::vector<int> sc_off;       // entries of k_cov_pt_scatter, sc_off[ch] .. sc_off[ch + 1) of chunk ch
+    int n_cch = 0, n_ch = 0;                                 // camera chunks, all chunks
+};
+static void cov_plan_cameras(const CholHost& h, const CovSel& S, CovPlan& P) {
+    P.co.resize((size_t)S.n_cs);
+    for (int i = 0; i < S.n_cs; ++i) P.co[i] = i;
+    std::sort(P.co.begin(), P.co.end(), [&](int a, int b) { return h.cam_off_host[S.cam_sel[a]] < h.cam_off_host[S.cam_sel[b]]; });
+    P.n_cch = P.n_ch = cdiv(S.n_cs, kCovCamsPerChunk);
+    P.seeds.resize((size_t)P.n_cch);
+    P.L.sel_row.assign((size_t)P.n_cch * kCovCamsPerChunk, 0); P.L.sel_cam.assign((size_t)P.n_cch * kCovCamsPerChunk, -1);
+    for (int j = 0; j < S.n_cs; ++j) {
+        const int cam = S.cam_sel[P.co[j]];
+        P.L.sel_cam[j] = cam; P.L.sel_row[j] = h.cam_off_host[cam];
+        P.seeds[j / kCovCamsPerChunk].push_back(h.cam_off_host[cam] / kNB);
+    }
+}
+// The point chunks after the camera chunks of P (if any), the work lists of all chunks, and the scatter entries, which need the
+// panel slots of the lists.
+static void cov_plan_points(const CholHost& h, const CovFront& f, const CovPoints& Q, CovPlan& P) {
+    const int n = (int)Q.sel.size(), n_pch = cdiv(n, kCovPtsPerChunk);
+    const std::vector<int2>& rec = Q.R.rec;
+    const std::vector<int>& ro = Q.R.ro;
+    const std::vector<int>& rptr = Q.R.rptr;
+    std::vector<int> kmin((size_t)n, h.T);
+    for (int r = 0; r < Q.R.n_rec; ++r) kmin[rec[r].x] = std::min(kmin[rec[r].x], h.cam_off_host[rec[r].y] / kNB);
+    P.po.resize((size_t)n);
+    for (int i = 0; i < n; ++i) P.po[i] = i;
+    std::sort(P.po.begin(), P.po.end(), [&](int a, int b) { return kmin[a] != kmin[b] ? kmin[a] < kmin[b] : a < b; });
+    P.n_ch = P.n_cch + n_pch;
+    P.seeds.resize((size_t)P.n_ch);
+    P.chunk_pt.assign((size_t)n_pch * kCovPtsPerChunk, 0);
+    for (int j = 0; j < n; ++j) {
+        const int i = P.po[j], ch = P.n_cch + j / kCovPtsPerChunk;
+        P.chunk_pt[j] = Q.sel_pt[i];
+        for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
+            const int cam = rec[ro[q]].y;
+            if (!f.cam_const(cam)) P.seeds[ch].push_back(h.cam_off_host[cam] / kNB);
+        }
+    }
+    cov_build_lists(h, P.seeds, P.L, true);
+    P.sc_off.assign((size_t)P.n_ch + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        const int i = P.po[j], ch = P.n_cch + j / kCovPtsPerChunk;
+        for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
+            const int row = h.cam_off_host[rec[ro[q]].y];
+            const int sl = P.L.slot_of[(size_t)ch * h.T + row / kNB];
+            if (sl >= 0) P.sc_ent.push_back(make_int4(ro[q], sl, row % kNB, 3 * (j % kCovPtsPerChunk)));
+        }
+        P.sc_off[ch + 1] = (int)P.sc_ent.size();
+    }
+}
+
+// The forward substitutions of chunk ch into its panel Z, level by level (li: the next of L.launches, which go by chunk): unit
+// columns at the rows sel_row[0 .. nc) of a camera chunk, or (no sel_row) the right-hand side that Z holds already.
+static void cov_fwd_chunk(xrsfm_ba_context* c, const CovLists& L, size_t& li, int ch, const int4* d_ent, const int2* d_lj, double* Z, const int* sel_row, int nc) {
+    for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li) {
+        const int4* ent = d_ent + L.launches[li].ent0;
+        if (sel_row) LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<false>, dim3(L.launches[li].n), dim3(256), 0, c->chol.dev, ent, d_lj, Z, sel_row, nc);
+        else LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<true>, dim3(L.launches[li].n), dim3(256), 0, c->chol.dev, ent, d_lj, Z, (const int*)nullptr, 0);
+    }
+}
+
+// ---------------------------------------------------------------- marginal covariance of selected cameras (ba_cov.h)
+int covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* cam_sel, double* cov) {
+    int e;
+    if ((e = cov_refusal(c))) return e;
+    if (n_sel < 0) return XRSFM_BA_EINVAL;
+    if (n_sel == 0) return XRSFM_BA_OK;
+    if (!cam_sel || !cov) return XRSFM_BA_EINVAL;
+    Dev& d = c->d;
+    CholHost& h = c->chol;
+    CovSel S;
+    CovFront f;
+    if ((e = cov_select(c, n_sel, cam_sel, 0, nullptr, S)) || (e = cov_front(c, huber_a, f, S))) return e;
+    std::vector<double> out((size_t)n_sel * 36);      // staged (cov_publish)
+    if (f.fallback) {
+        // one group per camera: rows c of the 6 solutions are block (c, c)
+        std::vector<CovCol> cols;
+        std::vector<int> gptr(1, 0);
+        for (int i = 0; i < n_sel; ++i) {
+            for (int a = 0; a < 6; ++a) cols.push_back(CovCol{-1, cam_sel[i], a});
+            gptr.push_back((int)cols.size());
+        }
+        if ((e = cov_fallback(c, f, CovPoints(), cols, gptr, out))) return e;
+    } else {
+        std::vector<double> x;
+        if ((e = cov_factor(c, x))) return e;
+        CovPlan P;
+        cov_plan_cameras(h, S, P);
+        cov_build_lists(h, P.seeds, P.L, false);
+        const CovLists& L = P.L;
+        DevScratch ds;
+        int4* d_ent = nullptr; int2* d_lj = nullptr; int *d_row = nullptr, *d_cam = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_cam, L.sel_cam)) ||
+            (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n_sel * 36))) return e;
+        size_t li = 0;
+        for (int ch = 0, c0 = 0; c0 < n_sel; ++ch, c0 += kCovCamsPerChunk) {
+            const int nc = std::min(kCovCamsPerChunk, n_sel - c0);
+            cov_fwd_chunk(c, L, li, ch, d_ent, d_lj, d_Z, d_row + c0, nc);      // (writes every element of the chunk's slots: no memset)
+            LAUNCH(c, K_SMALL, k_cov_gram, dim3(nc), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_cam + c0), d_cov + 36 * (size_t)c0);
+        }
+        HIPCHK(hipGetLastError());
+        std::vector<double> hc((size_t)n_sel * 36);
+        HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int j = 0; j < n_sel; ++j) memcpy(out.data() + 36 * (size_t)P.co[j], hc.data() + 36 * (size_t)j, 36 * sizeof(double));
+    }
+    return cov_publish(out, cov);
+}
+
 // ---------------------------------------------------------------- marginal covariance of selected points (ba_cov.h)
 int point_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_sel, const int32_t* pt_sel, double* cov) {
-    if (!c) return XRSFM_BA_EINVAL;
-    if (c->poisoned) return XRSFM_BA_ESTATE;
-    if (c->wide || c->multi() || n_sel < 0) return XRSFM_BA_EINVAL;
+    int e;
+    if ((e = cov_refusal(c))) return e;
+    if (n_sel < 0) return XRSFM_BA_EINVAL;
     if (n_sel == 0) return XRSFM_BA_OK;
     if (!pt_sel || !cov) return XRSFM_BA_EINVAL;
     Dev& d = c->d;
     CholHost& h = c->chol;
-    const int Np = c->n_points_caller;
-    // caller's point -> packed point (only points with an observation are packed), then -> index in the selection
-    std::vector<int> packed_of((size_t)std::max(Np, 1), -1);
-    {
-        std::vector<char> seen((size_t)std::max(Np, 1), 0);
-        for (int i = 0; i < n_sel; ++i) {
-            const int s = pt_sel[i];
-            if (s < 0 || s >= Np || seen[s]) return XRSFM_BA_EINVAL;
-            seen[s] = 1;
-        }
-        for (size_t j = 0; j < c->pk.pt_orig.size(); ++j) packed_of[c->pk.pt_orig[j]] = (int)j;
-    }
-    int e;
+    CovSel S;
     CovFront f;
-    if ((e = cov_front(c, huber_a, f, [&] {
-            for (int i = 0; i < n_sel; ++i) if (packed_of[pt_sel[i]] < 0) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
-            return 0;
-        }))) return e;
+    if ((e = cov_select(c, 0, nullptr, n_sel, pt_sel, S)) || (e = cov_front(c, huber_a, f, S))) return e;
     DevScratch ds;
-    std::vector<double> out((size_t)n_sel * 9, 0.0);      // staged: cov is written only when every value is finite
-    // the free points of the selection (a constant point keeps its all-zero block): sel[] = index in pt_sel, by ascending packed index
-    std::vector<int> sel;
-    for (int i = 0; i < n_sel; ++i) if (!c->pk.pt_const[packed_of[pt_sel[i]]]) sel.push_back(i);
-    std::sort(sel.begin(), sel.end(), [&](int a, int b) { return packed_of[pt_sel[a]] < packed_of[pt_sel[b]]; });
-    const int n = (int)sel.size();
-    if (n == 0) { memcpy(cov, out.data(), out.size() * sizeof(double)); return XRSFM_BA_OK; }
-    std::vector<int> sel_pt((size_t)n);
-    for (int i = 0; i < n; ++i) sel_pt[i] = packed_of[pt_sel[sel[i]]];
-    CovPtRecords R;
-    if ((e = cov_point_records(c, ds, sel_pt, R))) return e;
-    const int n_rec = R.n_rec;
-    double* const d_blk = R.d_blk;
-    const std::vector<int2>& rec = R.rec;
-    const std::vector<int>& ro = R.ro;
-    const std::vector<int>& rptr = R.rptr;
-    int* d_selpt = nullptr;
-    std::vector<double> x;
+    CovPoints Q;
+    if ((e = cov_free_points(c, ds, S, Q))) return e;
+    const int n = (int)Q.sel.size();
+    std::vector<double> out((size_t)n_sel * 9, 0.0);      // staged (cov_publish)
+    if (n == 0) return cov_publish(out, cov);             // nothing but constant points
     if (f.fallback) {
-        // per point and column b: S x_b = w_b (column b of W_p Hinv_p) with the run path's factor-and-solve, Sigma_ab = Hinv_ab + w_a^T x_b
-        std::vector<double> blk((size_t)n_rec * 18), hs((size_t)n * 9), rhs((size_t)h.dev.n_pad);
-        double* d_hs = nullptr;
-        if ((e = ds.put(&d_selpt, sel_pt)) || (e = ds.get(&d_hs, (size_t)n * 9))) return e;
-        LAUNCH(c, K_SMALL, k_cov_pt_gather, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, d, (const int*)d_selpt, n, d_hs);
-        if (n_rec > 0) HIPCHK(hipMemcpyAsync(blk.data(), d_blk, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        static const int up[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+        // one group per free point: Sigma_ab = Hinv_ab + w_a^T x_b with S x_b = w_b (column b of W_p Hinv_p)
+        std::vector<CovCol> cols;
+        std::vector<int> gptr(1, 0);
         for (int i = 0; i < n; ++i) {
-            double M[3][3];
-            bool any = false;       // a point seen by constant cameras only: W_p = 0, nothing to solve
-            for (int q = rptr[i]; q < rptr[i + 1]; ++q) any = any || !(f.dof_const(rec[ro[q]].y, 0) && f.dof_const(rec[ro[q]].y, 3));
-            for (int b = 0; b < 3; ++b) {
-                if (any) {
-                    std::fill(rhs.begin(), rhs.end(), 0.0);
-                    for (int q = rptr[i]; q < rptr[i + 1]; ++q)
-                        for (int a = 0; a < 6; ++a) rhs[h.cam_off_host[rec[ro[q]].y] + a] = blk[18 * (size_t)ro[q] + 3 * a + b];
-                    if ((e = cov_factor(c, x, &rhs))) return e;
-                }
-                for (int a = 0; a < 3; ++a) {
-                    double s = 0.0;
-                    if (any)
-                        for (int q = rptr[i]; q < rptr[i + 1]; ++q)
-                            for (int r = 0; r < 6; ++r) s += blk[18 * (size_t)ro[q] + 3 * r + a] * x[6 * (size_t)rec[ro[q]].y + r];
-                    M[a][b] = hs[9 * (size_t)i + up[a][b]] + s;
-                }
-            }
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) out[9 * (size_t)sel[i] + 3 * a + b] = 0.5 * (M[a][b] + M[b][a]) * (hs[9 * (size_t)i + 6 + a] * hs[9 * (size_t)i + 6 + b]);
+            for (int a = 0; a < 3; ++a) cols.push_back(CovCol{i, 0, a});
+            gptr.push_back((int)cols.size());
         }
+        std::vector<double> blocks;
+        if ((e = cov_fallback(c, f, Q, cols, gptr, blocks))) return e;
+        for (int i = 0; i < n; ++i) memcpy(out.data() + 9 * (size_t)Q.sel[i], blocks.data() + 9 * (size_t)i, 9 * sizeof(double));
     } else {
+        std::vector<double> x;
         if ((e = cov_factor(c, x))) return e;
-        // chunks of 21 points whose cameras are close in elimination order: by the smallest tile column of a point's observers
-        // (then by packed index: the order of pt_sel has no say; chunking affects no value — ba_cov.h)
-        auto col_of = [&](int cam) { return h.cam_off_host[cam] / kNB; };
-        std::vector<int> kmin((size_t)n, h.T), po((size_t)n);
-        for (int r = 0; r < n_rec; ++r) kmin[rec[r].x] = std::min(kmin[rec[r].x], col_of(rec[r].y));
-        for (int i = 0; i < n; ++i) po[i] = i;
-        std::sort(po.begin(), po.end(), [&](int a, int b) { return kmin[a] != kmin[b] ? kmin[a] < kmin[b] : a < b; });
-        const int n_ch = cdiv(n, kCovPtsPerChunk);
-        std::vector<std::vector<int>> seeds((size_t)n_ch);
-        std::vector<int> chunk_pt((size_t)n_ch * kCovPtsPerChunk, 0);
-        for (int j = 0; j < n; ++j) {
-            const int i = po[j], ch = j / kCovPtsPerChunk;
-            chunk_pt[j] = sel_pt[i];
-            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
-                const int cam = rec[ro[q]].y;
-                if (!(f.dof_const(cam, 0) && f.dof_const(cam, 3))) seeds[ch].push_back(col_of(cam));      // (an all-constant camera: zero rows of W_p)
-            }
-        }
-        CovLists L;
-        cov_build_lists(h, seeds, L, true);
-        std::vector<int4> sc_ent; std::vector<int> sc_off((size_t)n_ch + 1, 0);
-        for (int j = 0; j < n; ++j) {
-            const int i = po[j], ch = j / kCovPtsPerChunk;
-            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
-                const int cam = rec[ro[q]].y, row = h.cam_off_host[cam];
-                const int sl = L.slot_of[(size_t)ch * h.T + row / kNB];
-                if (sl >= 0) sc_ent.push_back(make_int4(ro[q], sl, row % kNB, 3 * (j % kCovPtsPerChunk)));
-            }
-            sc_off[ch + 1] = (int)sc_ent.size();
-        }
-        int4 *d_ent = nullptr, *d_sc = nullptr; int2* d_lj = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
-        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, sc_ent)) || (e = ds.put(&d_selpt, chunk_pt)) ||
+        CovPlan P;
+        cov_plan_points(h, f, Q, P);
+        const CovLists& L = P.L;
+        int4 *d_ent = nullptr, *d_sc = nullptr; int2* d_lj = nullptr; int* d_selpt = nullptr; double *d_Z = nullptr, *d_cov = nullptr;
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, P.sc_ent)) || (e = ds.put(&d_selpt, P.chunk_pt)) ||
             (e = ds.get(&d_Z, (size_t)L.max_slots * kCovPanel)) || (e = ds.get(&d_cov, (size_t)n * 9))) return e;
         size_t li = 0;
-        for (int ch = 0, p0 = 0; ch < n_ch; ++ch, p0 += kCovPtsPerChunk) {
-            const int np = std::min(kCovPtsPerChunk, n - p0), ne = sc_off[ch + 1] - sc_off[ch];
+        for (int ch = 0, p0 = 0; ch < P.n_ch; ++ch, p0 += kCovPtsPerChunk) {
+            const int np = std::min(kCovPtsPerChunk, n - p0), ne = P.sc_off[ch + 1] - P.sc_off[ch];
+            // (the chunk's slots receive the scattered right-hand side: zero first)
             if (L.chunk_slots[ch] > 0) HIPCHK(hipMemsetAsync(d_Z, 0, sizeof(double) * (size_t)L.chunk_slots[ch] * kCovPanel, c->stream));
-            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + sc_off[ch]), ne, (const double*)d_blk, d_Z);
-            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li)
-                LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<true>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, d_Z,
-                       (const int*)nullptr, 0);
+            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + P.sc_off[ch]), ne, (const double*)Q.R.d_blk, d_Z);
+            cov_fwd_chunk(c, L, li, ch, d_ent, d_lj, d_Z, nullptr, 0);
             LAUNCH(c, K_SMALL, k_cov_pt_gram, dim3(cdiv(np, 4)), dim3(256), 0, d, (const double*)d_Z, L.chunk_slots[ch], (const int*)(d_selpt + p0), np, d_cov + 9 * (size_t)p0);
         }
         HIPCHK(hipGetLastError());
         std::vector<double> hc((size_t)n * 9);
         HIPCHK(hipMemcpyAsync(hc.data(), d_cov, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (int j = 0; j < n; ++j) memcpy(out.data() + 9 * (size_t)sel[po[j]], hc.data() + 9 * (size_t)j, 9 * sizeof(double));
+        for (int j = 0; j < n; ++j) memcpy(out.data() + 9 * (size_t)Q.sel[P.po[j]], hc.data() + 9 * (size_t)j, 9 * sizeof(double));
     }
-    for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
-    memcpy(cov, out.data(), out.size() * sizeof(double));
-    return XRSFM_BA_OK;
+    return cov_publish(out, cov);
 }
 
 // ---------------------------------------------------------------- joint covariance of selected cameras and points (ba_cov.h)
 int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel, const int32_t* cam_sel, int32_t n_pt_sel, const int32_t* pt_sel,
                           double* cov) {
-    if (!c) return XRSFM_BA_EINVAL;
-    if (c->poisoned) return XRSFM_BA_ESTATE;
-    if (c->wide || c->multi() || n_cam_sel < 0 || n_pt_sel < 0) return XRSFM_BA_EINVAL;
+    int e;
+    if ((e = cov_refusal(c))) return e;
+    if (n_cam_sel < 0 || n_pt_sel < 0) return XRSFM_BA_EINVAL;
     const long long N_ll = 6LL * n_cam_sel + 3LL * n_pt_sel;
     if (N_ll == 0) return XRSFM_BA_OK;
     if (N_ll > kCovJointMaxCols || (n_cam_sel > 0 && !cam_sel) || (n_pt_sel > 0 && !pt_sel) || !cov) return XRSFM_BA_EINVAL;
-    const int N = (int)N_ll, n_cs = n_cam_sel, n_ps = n_pt_sel;
+    const int N = (int)N_ll, n_cs = n_cam_sel;
     Dev& d = c->d;
     CholHost& h = c->chol;
-    const int Nc = d.n_cams, Np = c->n_points_caller;
-    std::vector<int> packed_of((size_t)std::max(Np, 1), -1);
-    {
-        std::vector<char> seen((size_t)std::max(Nc, 1), 0);
-        for (int i = 0; i < n_cs; ++i) {
-            const int s = cam_sel[i];
-            if (s < 0 || s >= Nc || seen[s]) return XRSFM_BA_EINVAL;
-            seen[s] = 1;
-        }
-        seen.assign((size_t)std::max(Np, 1), 0);
-        for (int i = 0; i < n_ps; ++i) {
-            const int s = pt_sel[i];
-            if (s < 0 || s >= Np || seen[s]) return XRSFM_BA_EINVAL;
-            seen[s] = 1;
-        }
-        for (size_t j = 0; j < c->pk.pt_orig.size(); ++j) packed_of[c->pk.pt_orig[j]] = (int)j;
-    }
-    int e;
+    CovSel S;
     CovFront f;
-    if ((e = cov_front(c, huber_a, f, [&] {
-            for (int i = 0; i < n_cs; ++i) if (!(f.act[cam_sel[i]] > 0.0)) return (int)XRSFM_BA_ESINGULAR;      // no observation: no information
-            for (int i = 0; i < n_ps; ++i) if (packed_of[pt_sel[i]] < 0) return (int)XRSFM_BA_ESINGULAR;
-            return 0;
-        }))) return e;
+    if ((e = cov_select(c, n_cs, cam_sel, n_pt_sel, pt_sel, S)) || (e = cov_front(c, huber_a, f, S))) return e;
     DevScratch ds;
-    std::vector<double> out((size_t)N * N, 0.0);      // staged: cov is written only when every value is finite
-    // the free points of the selection (a constant point keeps its all-zero rows and columns): sel[] = index in pt_sel, by ascending packed index
-    std::vector<int> sel;
-    for (int i = 0; i < n_ps; ++i) if (!c->pk.pt_const[packed_of[pt_sel[i]]]) sel.push_back(i);
-    std::sort(sel.begin(), sel.end(), [&](int a, int b) { return packed_of[pt_sel[a]] < packed_of[pt_sel[b]]; });
-    const int n = (int)sel.size();
-    if (n_cs == 0 && n == 0) { memcpy(cov, out.data(), out.size() * sizeof(double)); return XRSFM_BA_OK; }      // nothing but constant points
-    std::vector<int> sel_pt((size_t)n);
-    for (int i = 0; i < n; ++i) sel_pt[i] = packed_of[pt_sel[sel[i]]];
-    CovPtRecords R;
-    if (n > 0 && (e = cov_point_records(c, ds, sel_pt, R))) return e;
-    R.rptr.resize((size_t)n + 1, 0);
-    const std::vector<int2>& rec = R.rec;
-    const std::vector<int>& ro = R.ro;
-    const std::vector<int>& rptr = R.rptr;
-    auto cam_fixed = [&](int cam) { return f.dof_const(cam, 0) && f.dof_const(cam, 3); };      // (an all-constant camera: zero rows of W_p)
-    std::vector<double> x;
+    CovPoints Q;
+    if ((e = cov_free_points(c, ds, S, Q))) return e;
+    const int n = (int)Q.sel.size();
+    std::vector<double> out((size_t)N * N, 0.0);          // staged (cov_publish)
+    if (n_cs == 0 && n == 0) return cov_publish(out, cov);      // nothing but constant points
     if (f.fallback) {
-        // One factor-and-solve S x = rhs per free selected column (a unit vector; column b of W_p Hinv_p) with the run path's
-        // factor-and-solve: M = the selected rows of [E | -W Hinv]^T S^-1 [E | -W Hinv] (+ Hinv_p), symmetrised and unscaled.
-        std::vector<double> blk((size_t)R.n_rec * 18), hs((size_t)n * 9), sc((size_t)Nc * 6), rhs((size_t)h.dev.n_pad), M((size_t)N * N, 0.0), scl((size_t)N, 0.0);
-        int* d_selpt = nullptr; double* d_hs = nullptr;
-        if ((e = ds.put(&d_selpt, sel_pt)) || (e = ds.get(&d_hs, (size_t)n * 9))) return e;
-        if (n > 0) {
-            LAUNCH(c, K_SMALL, k_cov_pt_gather, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, d, (const int*)d_selpt, n, d_hs);
-            HIPCHK(hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (R.n_rec > 0) HIPCHK(hipMemcpyAsync(blk.data(), R.d_blk, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(sc.data(), d.scale_c, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        static const int up[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-        struct Col { int pt, blk, a; };      // pt: -1 camera, else index in sel[]; blk: camera / unused; a: degree of freedom
-        std::vector<Col> cols((size_t)N, Col{-1, 0, 0});
+        // one group of all N columns: the cameras as selected, then the points as selected (a constant point: nothing)
+        std::vector<CovCol> cols((size_t)N, CovCol{-2, 0, 0});
         for (int i = 0; i < n_cs; ++i)
-            for (int a = 0; a < 6; ++a) {
-                cols[6 * (size_t)i + a] = Col{-1, cam_sel[i], a};
-                scl[6 * (size_t)i + a] = f.dof_const(cam_sel[i], a) ? 0.0 : sc[6 * (size_t)cam_sel[i] + a];
-            }
+            for (int a = 0; a < 6; ++a) cols[6 * (size_t)i + a] = CovCol{-1, cam_sel[i], a};
         for (int i = 0; i < n; ++i)
-            for (int a = 0; a < 3; ++a) {
-                const size_t j = 6 * (size_t)n_cs + 3 * (size_t)sel[i] + a;
-                cols[j] = Col{i, 0, a};
-                scl[j] = hs[9 * (size_t)i + 6 + a];
-            }
-        for (int j = 0; j < N; ++j) {
-            if (scl[j] == 0.0) continue;
-            const Col cj = cols[j];
-            bool any = cj.pt < 0;       // a point seen by constant cameras only: W_p = 0, nothing to solve
-            std::fill(rhs.begin(), rhs.end(), 0.0);
-            if (cj.pt < 0) rhs[h.cam_off_host[cj.blk] + cj.a] = 1.0;
-            else
-                for (int q = rptr[cj.pt]; q < rptr[cj.pt + 1]; ++q) {
-                    any = any || !cam_fixed(rec[ro[q]].y);
-                    for (int r = 0; r < 6; ++r) rhs[h.cam_off_host[rec[ro[q]].y] + r] = blk[18 * (size_t)ro[q] + 3 * r + cj.a];
-                }
-            if (any) { if ((e = cov_factor(c, x, &rhs))) return e; }
-            else x.assign((size_t)Nc * 6, 0.0);
-            for (int i = 0; i < N; ++i) {
-                if (scl[i] == 0.0) continue;
-                const Col ci = cols[i];
-                double u = 0.0;
-                if (ci.pt < 0) u = x[6 * (size_t)ci.blk + ci.a];
-                else
-                    for (int q = rptr[ci.pt]; q < rptr[ci.pt + 1]; ++q)
-                        for (int r = 0; r < 6; ++r) u += blk[18 * (size_t)ro[q] + 3 * r + ci.a] * x[6 * (size_t)rec[ro[q]].y + r];
-                if ((ci.pt < 0) != (cj.pt < 0)) u = -u;
-                else if (ci.pt >= 0 && ci.pt == cj.pt) u += hs[9 * (size_t)ci.pt + up[ci.a][cj.a]];
-                M[(size_t)i * N + j] = u;
-            }
-        }
-        for (int i = 0; i < N; ++i)
-            for (int j = i; j < N; ++j) {
-                const double sij = scl[i] * scl[j];
-                const double v = sij == 0.0 ? 0.0 : 0.5 * (M[(size_t)i * N + j] + M[(size_t)j * N + i]) * sij;
-                out[(size_t)i * N + j] = v; out[(size_t)j * N + i] = v;
-            }
+            for (int a = 0; a < 3; ++a) cols[6 * (size_t)n_cs + 3 * (size_t)Q.sel[i] + a] = CovCol{i, 0, a};
+        if ((e = cov_fallback(c, f, Q, cols, {0, N}, out))) return e;
     } else {
+        std::vector<double> x;
         if ((e = cov_factor(c, x))) return e;
-        auto col_of = [&](int cam) { return h.cam_off_host[cam] / kNB; };
-        // chunks: the cameras by elimination row, 10 per chunk, then the free points by the smallest tile column of their observers
-        // (then by packed index), 21 per chunk: the order of cam_sel / pt_sel has no say, and chunking affects no value (ba_cov.h)
-        std::vector<int> co((size_t)n_cs);
-        for (int i = 0; i < n_cs; ++i) co[i] = i;
-        std::sort(co.begin(), co.end(), [&](int a, int b) { return h.cam_off_host[cam_sel[a]] < h.cam_off_host[cam_sel[b]]; });
-        std::vector<int> kmin((size_t)n, h.T), po((size_t)n);
-        for (int r = 0; r < R.n_rec; ++r) kmin[rec[r].x] = std::min(kmin[rec[r].x], col_of(rec[r].y));
-        for (int i = 0; i < n; ++i) po[i] = i;
-        std::sort(po.begin(), po.end(), [&](int a, int b) { return kmin[a] != kmin[b] ? kmin[a] < kmin[b] : a < b; });
-        const int n_cch = cdiv(n_cs, kCovCamsPerChunk), n_ch = n_cch + cdiv(n, kCovPtsPerChunk), T = h.T;
-        CovLists L;
-        std::vector<std::vector<int>> seeds((size_t)n_ch);
+        CovPlan P;
+        cov_plan_cameras(h, S, P);
+        cov_plan_points(h, f, Q, P);
+        const CovLists& L = P.L;
+        const int n_cch = P.n_cch, n_ch = P.n_ch, T = h.T;
+        // where k_cov_joint_finish finds a column: {column of the chunk panels, camera / packed point, degree of freedom, is a point}
         std::vector<int4> colv((size_t)N, make_int4(-1, 0, 0, 1));
-        L.sel_row.assign((size_t)n_cch * kCovCamsPerChunk, 0);
-        for (int j = 0; j < n_cs; ++j) {
-            const int i = co[j], cam = cam_sel[i], ch = j / kCovCamsPerChunk;
-            L.sel_row[j] = h.cam_off_host[cam];
-            seeds[ch].push_back(col_of(cam));
-            for (int a = 0; a < 6; ++a) colv[6 * (size_t)i + a] = make_int4(kNB * ch + 6 * (j % kCovCamsPerChunk) + a, cam, a, 0);
-        }
-        for (int j = 0; j < n; ++j) {
-            const int i = po[j], ch = n_cch + j / kCovPtsPerChunk;
-            for (int q = rptr[i]; q < rptr[i + 1]; ++q)
-                if (!cam_fixed(rec[ro[q]].y)) seeds[ch].push_back(col_of(rec[ro[q]].y));
+        for (int j = 0; j < n_cs; ++j)
+            for (int a = 0; a < 6; ++a)
+                colv[6 * (size_t)P.co[j] + a] = make_int4(kNB * (j / kCovCamsPerChunk) + 6 * (j % kCovCamsPerChunk) + a, cam_sel[P.co[j]], a, 0);
+        for (int j = 0; j < n; ++j)
             for (int a = 0; a < 3; ++a)
-                colv[6 * (size_t)n_cs + 3 * (size_t)sel[i] + a] = make_int4(kNB * ch + 3 * (j % kCovPtsPerChunk) + a, sel_pt[i], a, 1);
-        }
-        cov_build_lists(h, seeds, L, true);
+                colv[6 * (size_t)n_cs + 3 * (size_t)Q.sel[P.po[j]] + a] =
+                    make_int4(kNB * (n_cch + j / kCovPtsPerChunk) + 3 * (j % kCovPtsPerChunk) + a, Q.sel_pt[P.po[j]], a, 1);
         // every chunk keeps panel slots of its own: base[ch] .. base[ch + 1)
         std::vector<size_t> base((size_t)n_ch + 1, 0);
         for (int ch = 0; ch < n_ch; ++ch) base[ch + 1] = base[ch] + (size_t)L.chunk_slots[ch];
         if (base[n_ch] > (size_t)0x7fffffff) return XRSFM_BA_ENOMEM;
-        std::vector<int4> sc_ent; std::vector<int> sc_off((size_t)n_ch + 1, 0);
-        for (int j = 0; j < n; ++j) {
-            const int i = po[j], ch = n_cch + j / kCovPtsPerChunk;
-            for (int q = rptr[i]; q < rptr[i + 1]; ++q) {
-                const int row = h.cam_off_host[rec[ro[q]].y];
-                const int sl = L.slot_of[(size_t)ch * T + row / kNB];
-                if (sl >= 0) sc_ent.push_back(make_int4(ro[q], sl, row % kNB, 3 * (j % kCovPtsPerChunk)));
-            }
-            sc_off[ch + 1] = (int)sc_ent.size();
-        }
         // chunk pairs (A <= B), row by row (k_cov_joint_finish indexes them so), and the tile columns both reach, ascending
         std::vector<int2> g_ent, g_slots;
         for (int A = 0; A < n_ch; ++A)
@@ -2074,7 +2055,7 @@ int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel
             }
         int4 *d_ent = nullptr, *d_sc = nullptr, *d_col = nullptr; int2 *d_lj = nullptr, *d_gent = nullptr, *d_gsl = nullptr; int* d_row = nullptr;
         double *d_Z = nullptr, *d_G = nullptr, *d_cov = nullptr;
-        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, sc_ent)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_col, colv)) ||
+        if ((e = ds.put(&d_ent, L.ent)) || (e = ds.put(&d_lj, L.lj)) || (e = ds.put(&d_sc, P.sc_ent)) || (e = ds.put(&d_row, L.sel_row)) || (e = ds.put(&d_col, colv)) ||
             (e = ds.put(&d_gent, g_ent)) || (e = ds.put(&d_gsl, g_slots)) || (e = ds.get(&d_Z, base[n_ch] * kCovPanel)) ||
             (e = ds.get(&d_G, g_ent.size() * kCovPanel)) || (e = ds.get(&d_cov, (size_t)N * N))) return e;
         // (a camera chunk's kernel writes every element of its slots; a point chunk's slots receive the scattered right-hand side)
@@ -2082,16 +2063,10 @@ int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel
         size_t li = 0;
         for (int ch = 0; ch < n_ch; ++ch) {
             double* Zc = d_Z + base[ch] * kCovPanel;
-            const int ne = sc_off[ch + 1] - sc_off[ch];
-            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + sc_off[ch]), ne, (const double*)R.d_blk, Zc);
-            for (; li < L.launches.size() && L.launches[li].chunk == ch; ++li) {
-                if (ch < n_cch)
-                    LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<false>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, Zc,
-                           (const int*)(d_row + (size_t)ch * kCovCamsPerChunk), std::min(kCovCamsPerChunk, n_cs - ch * kCovCamsPerChunk));
-                else
-                    LAUNCH(c, K_TRISOLVE, k_lv_fwd_multi<true>, dim3(L.launches[li].n), dim3(256), 0, h.dev, (const int4*)(d_ent + L.launches[li].ent0), (const int2*)d_lj, Zc,
-                           (const int*)nullptr, 0);
-            }
+            const int ne = P.sc_off[ch + 1] - P.sc_off[ch], c0 = ch * kCovCamsPerChunk;
+            if (ne > 0) LAUNCH(c, K_SMALL, k_cov_pt_scatter, dim3(cdiv(18 * ne, 256)), dim3(256), 0, (const int4*)(d_sc + P.sc_off[ch]), ne, (const double*)Q.R.d_blk, Zc);
+            if (ch < n_cch) cov_fwd_chunk(c, L, li, ch, d_ent, d_lj, Zc, d_row + c0, std::min(kCovCamsPerChunk, n_cs - c0));
+            else cov_fwd_chunk(c, L, li, ch, d_ent, d_lj, Zc, nullptr, 0);
         }
         LAUNCH(c, K_TRISOLVE, k_cov_joint_gram, dim3((unsigned)g_ent.size()), dim3(256), 0, (const int2*)d_gent, (const int2*)d_gsl, (const double*)d_Z, d_G);
         LAUNCH(c, K_SMALL, k_cov_joint_finish, dim3(cdiv((long long)N * N, 256)), dim3(256), 0, d, (const int4*)d_col, N, n_ch, (const double*)d_G, d_cov);
@@ -2099,30 +2074,26 @@ int joint_covariance_impl(xrsfm_ba_context* c, double huber_a, int32_t n_cam_sel
         HIPCHK(hipMemcpyAsync(out.data(), d_cov, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    for (double v : out) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
-    memcpy(cov, out.data(), out.size() * sizeof(double));
-    return XRSFM_BA_OK;
+    return cov_publish(out, cov);
 }
 
 // ---------------------------------------------------------------- covariance of the whole map by selected inversion (ba_cov.h)
 int map_covariance_impl(xrsfm_ba_context* c, double huber_a, double* cam_cov, double* pt_cov, uint8_t* cam_status, uint8_t* pt_status) {
-    if (!c) return XRSFM_BA_EINVAL;
-    if (c->poisoned) return XRSFM_BA_ESTATE;
-    if (c->wide || c->multi()) return XRSFM_BA_EINVAL;
+    int e;
+    if ((e = cov_refusal(c))) return e;
     if (!cam_cov && !pt_cov && !cam_status && !pt_status) return XRSFM_BA_OK;
     Dev& d = c->d;
     CholHost& h = c->chol;
     const int Nc = d.n_cams, Np = c->n_points_caller;
     const auto t_begin = std::chrono::steady_clock::now();
-    int e;
     CovFront f;
-    if ((e = cov_front(c, huber_a, f, [] { return 0; }))) return e;
+    if ((e = cov_front(c, huber_a, f, CovSel()))) return e;
     // status of every camera and point, and the packed point of a caller's point (only points with an observation are packed)
     std::vector<uint8_t> cst((size_t)Nc), pst((size_t)Np, 2);
-    for (int i = 0; i < Nc; ++i) cst[i] = !(f.act[i] > 0.0) ? 2 : ((f.cc[i] & 3u) == 3u ? 1 : 0);
+    for (int i = 0; i < Nc; ++i) cst[i] = !(f.act[i] > 0.0) ? 2 : (f.cam_const(i) ? 1 : 0);
     const int n_pk = (int)c->pk.pt_orig.size();
     for (int j = 0; j < n_pk; ++j) pst[c->pk.pt_orig[j]] = c->pk.pt_const[j] ? 1 : 0;
-    // staged: the outputs are written only when every value is finite
+    // staged (cov_publish)
     std::vector<double> oc(cam_cov ? (size_t)Nc * 36 : 0, 0.0), op(pt_cov ? (size_t)Np * 9 : 0, 0.0);
     double ms_inv = 0.0, ms_pts = 0.0; size_t z_bytes = 0;
     if (f.fallback) {
@@ -2219,10 +2190,7 @@ int map_covariance_impl(xrsfm_ba_context* c, double huber_a, double* cam_cov, do
         HIPCHK(hipStreamSynchronize(c->stream));
         ms_pts = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pts).count();
     }
-    for (double v : oc) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
-    for (double v : op) if (!std::isfinite(v)) return XRSFM_BA_ESINGULAR;
-    if (cam_cov) memcpy(cam_cov, oc.data(), oc.size() * sizeof(double));
-    if (pt_cov) memcpy(pt_cov, op.data(), op.size() * sizeof(double));
+    if ((e = cov_publish(oc, cam_cov, op, pt_cov))) return e;
     if (cam_status) memcpy(cam_status, cst.data(), cst.size());
     if (pt_status) memcpy(pt_status, pst.data(), pst.size());
     if (std::getenv("XRSFM_BA_COV_TIMING"))       // (developer aid, tools/cov_timing.py: host clock around the phases of one call)
