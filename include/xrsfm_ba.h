@@ -517,6 +517,57 @@ int xrsfm_ba_filter_tracks(const xrsfm_ba_problem *problem, double max_reproj_er
                            uint8_t *obs_delete, uint8_t *track_outlier, double *track_error, double *track_angle,
                            int32_t *num_filtered);
 
+/* Batched robust triangulation of new tracks: the creation of a 3-D point from the observations of an untriangulated key point
+ * (CreatePoint3d1, /root/reference/src/geometry/track_processor.cc:109-161, called by Point3dProcessor::TriangulateFramePoint once
+ * per registered frame before the local BA and by run_triangulation over every frame of a map).  Restates
+ * colmap::EstimateTriangulation: LO-RANSAC over the pairs (i, j), i < j, of a track's observations in lexicographic order
+ * (CombinationSampler, deterministic), two-view DLT per pair, residual = squared angle between the observed ray and the ray to the
+ * model, multi-view refit of the inliers of every new best with more than two inliers.  One wave per track on the device, all
+ * tracks of a call in one launch; FP64 throughout.
+ *
+ * The observations of track j are trk_ptr[j] .. trk_ptr[j+1] in the caller's order (the order of `observations` in
+ * TriangulateFramePoint: it fixes the trial order).  obs_xy are NORMALISED image coordinates (GetPointNormalized of the key point:
+ * undistortion stays with the caller, as for xrsfm_tag_problem).  cam_q / cam_t are Tcw of the registered frames, q = x,y,z,w.
+ *
+ *   status[j]       0 no model (the reference's `return false`); 1 point created; 2 fewer than two observations (the `continue`
+ *                   at track_processor.cc:222); 3 more than XRSFM_BA_TRI_MAX_OBS observations: not attempted, the call still
+ *                   succeeds.  (128: C(128, 2) = 8128 pairs stay below the reference's cap of 10000 trials, which starts to bite
+ *                   at 142 observations, so the combination sampler never wraps.)
+ *   on status 1     points[j] the model; inlier_mask the reference's report.inlier_mask (AddTrack takes the observations it
+ *                   marks); num_inliers[j] the best support's count; num_trials[j] report.num_trials; best_trial[j] the 0-based
+ *                   trial whose sample model became the final best, plus bit 30 when the locally optimised model of that trial
+ *                   is the one returned
+ *   on 0, 2, 3      points[j] untouched, the track's mask entries 0, counts 0, best_trial -1
+ * On any negative return code no output is touched.  No output ever receives a NaN or an Inf: a status-1 model that is not
+ * finite becomes status 0.  A track's outputs are bit-identical whatever else is in the batch and in whatever order.
+ *
+ * Documented deviation (defined meaning where the reference has none): a sample model without a single inlier still beats the
+ * initial best support (0 == 0 inliers and 0.0 < DBL_MAX), after which the reference's ComputeNumTrials(0, ...) divides by
+ * log(1) = 0 and casts -inf to size_t.  An outlier pair whose rays are skew by more than max_error_rad reaches this.  The library
+ * takes zero inliers as "no information": the adaptive trial bound stays unbounded there.
+ *
+ * Errors: XRSFM_BA_EINVAL (checked on the host before the device is touched, one line on stderr) — NULL opt; NULL points, status
+ * or inlier_mask with n_tracks > 0; a negative count; trk_ptr not starting at 0 or decreasing; an obs_cam out of range; a
+ * non-finite pose, coordinate or option; max_error_rad <= 0; confidence or min_inlier_ratio outside [0, 1]; max_num_trials < 1;
+ * exhaustive_threshold < 0; min_tri_angle_rad < 0.  XRSFM_BA_ENODEV without a device (there is no CPU path); XRSFM_BA_ENOMEM when
+ * staging memory cannot be had.  n_tracks == 0 is success and needs no device. */
+typedef struct xrsfm_ba_tri_options {
+    double  min_tri_angle_rad;    /* DegToRad(1.5)   track_processor.cc:132 */
+    double  max_error_rad;        /* DegToRad(2): bound on the angular error; residual = angle^2  :135 */
+    double  confidence;           /* 0.9999          :136 */
+    double  min_inlier_ratio;     /* 0.02            :137 */
+    int32_t max_num_trials;       /* 10000           :138 */
+    int32_t exhaustive_threshold; /* 15: tracks of at most this many observations try every pair  :140-144 */
+} xrsfm_ba_tri_options;
+#define XRSFM_BA_TRI_MAX_OBS 128
+void xrsfm_ba_triangulate_options(xrsfm_ba_tri_options *opt);   /* the values above */
+int xrsfm_ba_triangulate_tracks(const xrsfm_ba_tri_options *opt, int32_t n_cams, const double *cam_q /* [n_cams][4] */,
+                                const double *cam_t /* [n_cams][3] */, int32_t n_tracks, const int32_t *trk_ptr /* [n_tracks+1] */,
+                                const int32_t *obs_cam /* [n_obs] */, const double *obs_xy /* [n_obs][2] */,
+                                double *points /* [n_tracks][3] */, uint8_t *status /* [n_tracks] */, uint8_t *inlier_mask /* [n_obs] */,
+                                int32_t *num_inliers /* [n_tracks], may be NULL */, int32_t *num_trials /* [n_tracks], may be NULL */,
+                                int32_t *best_trial /* [n_tracks], may be NULL */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

@@ -32,6 +32,7 @@ VARIANTS = {
     "poison": ["-DXBA_POISON", "-ffp-contract=off"],
     "strict": ["-ffp-contract=off"],
     "backsub_w5": ["-DXBA_BACKSUB_WAVES=5"],    # k_backsub register-allocated for 5 waves per SIMD (round-2 finding xi)
+    "tri_phases": ["-DXBA_TRI_PHASES"],         # k_tri_tracks counts the clock ticks of its blocks (tools/triangulate_timing.py)
 }
 
 

@@ -54,6 +54,11 @@ class CTagProblem(C.Structure):
                 ("points", _c_double_p), ("obs_frame", _c_int32_p), ("obs_pt", _c_int32_p), ("obs_xy", _c_double_p)]
 
 
+class CTriOptions(C.Structure):
+    _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
+                ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_uint64, C.c_int)
 
 
@@ -92,6 +97,7 @@ EXPORTS = [
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
     "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
+    "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -113,6 +119,8 @@ def _facts(v) -> dict:
 SOLVER_PCG, SOLVER_CHOLESKY, SOLVER_AUTO = 0, 1, 2
 SOLVER_RESIDENT = 3     # the whole LM loop in one kernel launch (local-BA-sized problems: include/xrsfm_ba.h)
 BATCH_MAX = 4096        # XRSFM_BA_BATCH_MAX: most contexts of one xrsfm_ba_run_batch
+TRI_MAX_OBS = 128       # XRSFM_BA_TRI_MAX_OBS: longest track xrsfm_ba_triangulate_tracks attempts
+TRI_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised model of that trial is the one returned
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -207,6 +215,11 @@ def load(path: str | None = None):
     lib.xrsfm_ba_run_batch.restype = C.c_int
     lib.xrsfm_ba_solve_batch.argtypes = [C.POINTER(COptions), C.c_int32, C.POINTER(CProblem), C.POINTER(CSummary), _c_int32_p]
     lib.xrsfm_ba_solve_batch.restype = C.c_int
+    lib.xrsfm_ba_triangulate_options.argtypes = [C.POINTER(CTriOptions)]
+    lib.xrsfm_ba_triangulate_options.restype = None
+    lib.xrsfm_ba_triangulate_tracks.argtypes = [C.POINTER(CTriOptions), C.c_int32, _c_double_p, _c_double_p, C.c_int32, _c_int32_p, _c_int32_p,
+                                                 _c_double_p, _c_double_p, _c_uint8_p, _c_uint8_p, _c_int32_p, _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_triangulate_tracks.restype = C.c_int
     _lib = lib
     return lib
 
@@ -612,6 +625,38 @@ def filter_tracks(problem: ProblemArrays, max_reproj_error: float, min_tri_angle
                                         out.ctypes.data_as(_c_uint8_p), _dp(err), _dp(ang), cnt.ctypes.data_as(_c_int32_p)),
           "xrsfm_ba_filter_tracks")
     return dict(obs_delete=obs_del, track_outlier=out, track_error=err, track_angle=ang, num_filtered=cnt)
+
+
+def triangulate_options(**overrides) -> CTriOptions:
+    """xrsfm_ba_triangulate_options: the settings of the reference's CreatePoint3d1."""
+    o = CTriOptions()
+    load().xrsfm_ba_triangulate_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def triangulate_tracks(cam_q, cam_t, trk_ptr, obs_cam, obs_xy, options: CTriOptions | None = None) -> dict:
+    """xrsfm_ba_triangulate_tracks: one robust triangulation per track (observations trk_ptr[j] .. trk_ptr[j+1], normalised image
+    coordinates, Tcw poses).  points of tracks whose status is not 1 stay 0 here (the C call leaves them untouched)."""
+    o = options if options is not None else triangulate_options()
+    cam_q = np.ascontiguousarray(cam_q, np.float64).reshape(-1, 4); cam_t = np.ascontiguousarray(cam_t, np.float64).reshape(-1, 3)
+    trk_ptr = np.ascontiguousarray(trk_ptr, np.int32); obs_cam = np.ascontiguousarray(obs_cam, np.int32)
+    obs_xy = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+    if len(cam_q) != len(cam_t) or trk_ptr.ndim != 1 or len(trk_ptr) < 1 or len(obs_cam) != len(obs_xy):
+        raise ValueError("triangulate_tracks: inconsistent array shapes")
+    nt, no = len(trk_ptr) - 1, len(obs_cam)
+    if nt > 0 and trk_ptr[-1] != no:
+        raise ValueError("triangulate_tracks: trk_ptr[-1] must be the number of observations")
+    points = np.zeros((nt, 3)); status = np.zeros(nt, np.uint8); mask = np.zeros(no, np.uint8)
+    ninl = np.zeros(nt, np.int32); ntr = np.zeros(nt, np.int32); best = np.full(nt, -1, np.int32)
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    check(load().xrsfm_ba_triangulate_tracks(C.byref(o), len(cam_q), _dp(cam_q), _dp(cam_t), nt, ip(trk_ptr), ip(obs_cam), _dp(obs_xy), _dp(points),
+                                             status.ctypes.data_as(_c_uint8_p), mask.ctypes.data_as(_c_uint8_p), ip(ninl), ip(ntr), ip(best)),
+          "xrsfm_ba_triangulate_tracks")
+    return dict(points=points, status=status, inlier_mask=mask, num_inliers=ninl, num_trials=ntr, best_trial=best)
 
 
 def debug_pack(problem: ProblemArrays) -> dict:

@@ -33,6 +33,7 @@
 #include "ba_pack.h"
 #include "ba_plan.h"
 #include "ba_refine.h"
+#include "ba_tri.h"
 #include "ba_trust_region.h"
 #include "ba_wide.h"
 #include "ba_pack_dev.h"
@@ -3415,6 +3416,166 @@ static int filter_tracks_impl(const xrsfm_ba_problem* p, double max_reproj_error
 int xrsfm_ba_filter_tracks(const xrsfm_ba_problem* p, double max_reproj_error, double min_tri_angle_rad, uint8_t* obs_delete,
                            uint8_t* track_outlier, double* track_error, double* track_angle, int32_t* num_filtered) {
     return no_throw([&] { return filter_tracks_impl(p, max_reproj_error, min_tri_angle_rad, obs_delete, track_outlier, track_error, track_angle, num_filtered); });
+}
+
+// ---------------------------------------------------------------- batched robust triangulation of new tracks (ba_tri.h)
+void xrsfm_ba_triangulate_options(xrsfm_ba_tri_options* opt) {
+    if (!opt) return;
+    const double deg = 3.14159265358979323846 / 180.0;
+    opt->min_tri_angle_rad = 1.5 * deg;       // track_processor.cc:132
+    opt->max_error_rad = 2.0 * deg;           // :135
+    opt->confidence = 0.9999;                 // :136
+    opt->min_inlier_ratio = 0.02;             // :137
+    opt->max_num_trials = 10000;              // :138
+    opt->exhaustive_threshold = 15;           // :140
+}
+
+// dyn(k, n) of ba_tri_scan.h for k <= n <= XRSFM_BA_TRI_MAX_OBS, row n at n * (kMaxObs + 1): depends on the confidence only, so it is
+// tabulated once per confidence (with the host's log) and kept
+static const int32_t* tri_dyn_table(double confidence) {
+    static std::mutex mu;
+    static std::vector<int32_t> tab;
+    static double have = -1.0;
+    std::lock_guard<std::mutex> g(mu);
+    if (tab.empty() || have != confidence) {
+        const int W = xtri::kMaxObs + 1;
+        tab.assign((size_t)W * W, xtri::kUnbounded);
+        for (int n = 1; n < W; ++n)
+            for (int k = 0; k <= n; ++k) tab[(size_t)n * W + k] = xtri::tri_dyn_trials(k, n, confidence);
+        have = confidence;
+    }
+    return tab.data();
+}
+
+static int triangulate_tracks_impl(const xrsfm_ba_tri_options* opt, int32_t n_cams, const double* cam_q, const double* cam_t, int32_t n_tracks,
+                                   const int32_t* trk_ptr, const int32_t* obs_cam, const double* obs_xy, double* points, uint8_t* status,
+                                   uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_triangulate_tracks: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_cams < 0 || n_tracks < 0) return bad("negative count");
+    if (!std::isfinite(opt->min_tri_angle_rad) || !std::isfinite(opt->max_error_rad) || !std::isfinite(opt->confidence) ||
+        !std::isfinite(opt->min_inlier_ratio)) return bad("non-finite option");
+    if (opt->max_error_rad <= 0.0) return bad("max_error_rad <= 0");
+    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
+    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
+    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
+    if (opt->exhaustive_threshold < 0) return bad("exhaustive_threshold < 0");
+    if (opt->min_tri_angle_rad < 0.0) return bad("min_tri_angle_rad < 0");
+    if (n_tracks == 0) return XRSFM_BA_OK;
+    if (!points || !status || !inlier_mask) return bad("NULL points, status or inlier_mask");
+    if (!trk_ptr) return bad("NULL trk_ptr");
+    if (trk_ptr[0] != 0) return bad("trk_ptr does not start at 0");
+    for (int j = 0; j < n_tracks; ++j)
+        if (trk_ptr[j + 1] < trk_ptr[j]) return bad("trk_ptr decreases");
+    const int No = trk_ptr[n_tracks], Nc = n_cams, Nt = n_tracks;
+    if (No > 0 && (!obs_cam || !obs_xy)) return bad("NULL obs_cam or obs_xy");
+    if (Nc > 0 && (!cam_q || !cam_t)) return bad("NULL cam_q or cam_t");
+    for (int i = 0; i < No; ++i) {
+        if (obs_cam[i] < 0 || obs_cam[i] >= Nc) return bad("obs_cam out of range");
+        if (!std::isfinite(obs_xy[2 * (size_t)i]) || !std::isfinite(obs_xy[2 * (size_t)i + 1])) return bad("non-finite coordinate");
+    }
+    for (size_t i = 0; i < 4 * (size_t)Nc; ++i) if (!std::isfinite(cam_q[i])) return bad("non-finite pose");
+    for (size_t i = 0; i < 3 * (size_t)Nc; ++i) if (!std::isfinite(cam_t[i])) return bad("non-finite pose");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the triangulation has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    TriParams prm;
+    prm.min_angle = opt->min_tri_angle_rad;
+    prm.max_residual = opt->max_error_rad * opt->max_error_rad;
+    prm.trial_cap = std::min(opt->max_num_trials, xtri::tri_ratio_trials(opt->min_inlier_ratio, opt->confidence));
+    prm.exhaustive_threshold = opt->exhaustive_threshold;
+    const int32_t* dyn = tri_dyn_table(opt->confidence);
+    const size_t dyn_bytes = sizeof(int32_t) * (size_t)(xtri::kMaxObs + 1) * (xtri::kMaxObs + 1);
+    HIPCHK(hipSetDevice(0));
+    // one block from the allocation cache, one upload, two launches, one read-back (the layout of filter_tracks_impl)
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    const size_t o_cam = take(sizeof(CamRec) * (size_t)Nc), o_ptr = take(sizeof(int) * ((size_t)Nt + 1)), o_ocam = take(sizeof(int) * (size_t)No),
+                 o_oxy = take(sizeof(double) * 2 * (size_t)No), o_dyn = take(dyn_bytes);
+    const size_t in_bytes = off;
+    const size_t o_centre = take(sizeof(double) * 3 * (size_t)Nc);
+    const size_t out0 = off;
+    const size_t o_pts = take(sizeof(double) * 3 * (size_t)Nt), o_ninl = take(sizeof(int) * (size_t)Nt), o_ntr = take(sizeof(int) * (size_t)Nt),
+                 o_best = take(sizeof(int) * (size_t)Nt), o_stat = take((size_t)Nt), o_mask = take((size_t)No);
+    const size_t out_bytes = off - out0;
+    // developer aid (tools/triangulate_timing.py): HIP events around the kernel and, in the "tri_phases" build, its phase ticks
+    const bool timing = std::getenv("XRSFM_BA_TRI_TIMING") != nullptr;
+    const size_t o_phase = take(4 * sizeof(unsigned long long));
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    size_t cls = 0;
+    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
+    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    int e = 0;
+    {
+        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
+        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
+        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        CamRec* cams = (CamRec*)(stage.data() + o_cam);
+        for (int i = 0; i < Nc; ++i) {
+            for (int k2 = 0; k2 < 4; ++k2) cams[i].q[k2] = cam_q[4 * (size_t)i + k2];
+            for (int k2 = 0; k2 < 3; ++k2) cams[i].t[k2] = cam_t[3 * (size_t)i + k2];
+            cams[i].pad = 0.0;
+            for (int k2 = 0; k2 < 8; ++k2) cams[i].intr[k2] = 0.0;
+        }
+        memcpy(stage.data() + o_ptr, trk_ptr, sizeof(int) * ((size_t)Nt + 1));
+        if (No) { memcpy(stage.data() + o_ocam, obs_cam, sizeof(int) * (size_t)No); memcpy(stage.data() + o_oxy, obs_xy, sizeof(double) * 2 * (size_t)No); }
+        memcpy(stage.data() + o_dyn, dyn, dyn_bytes);
+        hipStream_t st = hb.stream;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (timing && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) e = XRSFM_BA_ENODEV;
+        if (!e && hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e && timing && hipMemsetAsync(base + o_phase, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            if (Nc > 0) hipLaunchKernelGGL(k_cam_centres, dim3(cdiv(Nc, 256)), dim3(256), 0, st, (const CamRec*)(base + o_cam), Nc, (double*)(base + o_centre));
+            if (timing) hipEventRecord(ev0, st);
+            hipLaunchKernelGGL(k_tri_tracks, dim3(cdiv(Nt, kTriWaves)), dim3(kTriWave * kTriWaves), 0, st, (const CamRec*)(base + o_cam),
+                               (const double*)(base + o_centre), (const int*)(base + o_ptr), (const int*)(base + o_ocam), (const double*)(base + o_oxy), Nt, prm,
+                               (const int32_t*)(base + o_dyn), (double*)(base + o_pts), (unsigned char*)(base + o_stat), (unsigned char*)(base + o_mask),
+                               (int*)(base + o_ninl), (int*)(base + o_ntr), (int*)(base + o_best),
+                               timing ? (unsigned long long*)(base + o_phase) : (unsigned long long*)nullptr);
+            if (timing) hipEventRecord(ev1, st);
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+        }
+        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        unsigned long long ticks[4] = {0, 0, 0, 0};
+        if (!e && timing && hipMemcpyAsync(ticks, base + o_phase, sizeof(ticks), hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (timing) {
+            float ms = 0.0f;
+            if (!e && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
+                fprintf(stderr, "[xrsfm_ba] triangulate: kernel_ms %.4f ticks_a %llu ticks_b %llu ticks_c %llu ticks_d %llu\n", ms, ticks[0], ticks[1],
+                        ticks[2], ticks[3]);
+            if (ev0) hipEventDestroy(ev0);
+            if (ev1) hipEventDestroy(ev1);
+        }
+        if (!e) {
+            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
+            const double* pts = (const double*)(o + o_pts);
+            const unsigned char* stat = o + o_stat;
+            for (int j = 0; j < Nt; ++j) {
+                status[j] = stat[j];
+                if (stat[j] == 1) for (int k2 = 0; k2 < 3; ++k2) points[3 * (size_t)j + k2] = pts[3 * (size_t)j + k2];
+            }
+            if (No) memcpy(inlier_mask, o + o_mask, (size_t)No);
+            if (num_inliers) memcpy(num_inliers, o + o_ninl, sizeof(int) * (size_t)Nt);
+            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Nt);
+            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Nt);
+        }
+    }
+    g_cache.put(0, base, cls);
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int xrsfm_ba_triangulate_tracks(const xrsfm_ba_tri_options* opt, int32_t n_cams, const double* cam_q, const double* cam_t, int32_t n_tracks,
+                                const int32_t* trk_ptr, const int32_t* obs_cam, const double* obs_xy, double* points, uint8_t* status,
+                                uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
+    return no_throw([&] { return triangulate_tracks_impl(opt, n_cams, cam_q, cam_t, n_tracks, trk_ptr, obs_cam, obs_xy, points, status, inlier_mask,
+                                                         num_inliers, num_trials, best_trial); });
 }
 
 // ---------------------------------------------------------------- diagnostics
