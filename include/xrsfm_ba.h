@@ -681,6 +681,13 @@ int xrsfm_ba_debug_backsub_layout(xrsfm_ba_context *ctx, int32_t *pt_orig, int32
  * consumers (0, the J-free linearisation of the Cholesky path): after xrsfm_ba_run, the mode its last iterations used. */
 int xrsfm_ba_debug_stored_j(xrsfm_ba_context *ctx, int32_t *stored);
 
+/* TEST ENTRY.  The scalars the LM controller decides on, of the context's current linearisation (after xrsfm_ba_debug_linearize
+ * or xrsfm_ba_debug_wide; XRSFM_BA_ESTATE without one): out = {sum of rho (twice the cost), |x_points|^2 over the variable points
+ * that have an observation, the gradient max-norm over the points, the gradient max-norm over the cameras}.  Fetched the way
+ * xrsfm_ba_run fetches them after iteration 0: a fused context reads what the tail of the linearisation left, an unfused or
+ * bal9 context launches the camera gradient kernel. */
+int xrsfm_ba_debug_lin_scalars(xrsfm_ba_context *ctx, double out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,7 @@ EXPORTS = [
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
     "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
-    "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks",
+    "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -435,6 +435,14 @@ class Context:
         v = C.c_int32(0)
         check(self.lib.xrsfm_ba_debug_stored_j(self._h, C.byref(v)), "debug_stored_j")
         return bool(v.value)
+
+    def debug_lin_scalars(self) -> dict:
+        """After debug_linearize / debug_wide: the scalars of the current linearisation as a run reads them (gradient_max)."""
+        out = np.zeros(4)
+        self.lib.xrsfm_ba_debug_lin_scalars.argtypes = [C.c_void_p, _c_double_p]
+        self.lib.xrsfm_ba_debug_lin_scalars.restype = C.c_int
+        check(self.lib.xrsfm_ba_debug_lin_scalars(self._h, _dp(out)), "xrsfm_ba_debug_lin_scalars")
+        return dict(sum_rho=float(out[0]), xnorm2_pts=float(out[1]), gradmax_pts=float(out[2]), gradmax_cams=float(out[3]))
 
     def debug_cholesky_solve(self, radius: float, want_S: bool = False):
         n = 6 * self.problem.n_cams

@@ -3722,6 +3722,20 @@ int xrsfm_ba_debug_stored_j(xrsfm_ba_context* c, int32_t* stored) {
     return 0;
 }
 
+// The scalars the LM controller reads of the context's current linearisation, fetched the way ba_run_impl fetches them after
+// iteration 0 (gradient_max): a fused context reads what k_lin_tail left, an unfused or bal9 context launches k_gradmax_cams /
+// k9_gradmax_cams.  out = {sum rho, |x_points|^2, gradient max-norm over the points, over the cameras}.
+int xrsfm_ba_debug_lin_scalars(xrsfm_ba_context* c, double* out) {
+    if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
+    if (!c || !out) return XRSFM_BA_EINVAL;
+    if (!c->linearized) return XRSFM_BA_ESTATE;
+    HIPCHK(hipSetDevice(c->device));
+    double gmax = 0.0;
+    if (int e = gradient_max(c, &gmax)) return e;
+    out[0] = c->h_scal[S_COST]; out[1] = c->h_scal[S_XNORM2_PTS]; out[2] = c->h_scal[S_GRADMAX_PTS]; out[3] = c->h_scal[S_GRADMAX_CAMS];
+    return 0;
+}
+
 int xrsfm_ba_debug_schur_product(xrsfm_ba_context* c, double radius, const double* x, double* y, double* b) {
     if (c && c->poisoned) return XRSFM_BA_ESTATE;       // the watchdog gave up on this context's stream: nothing may wait for it again
     if (c && c->wide) return XRSFM_BA_EINVAL;
