@@ -211,6 +211,28 @@ def shape_problems(groups_per_problem=6, seed=0):
     return out
 
 
+def tiles_of(arr):
+    """(C, T, ragged, passes, klass) of every tile of the packed problem; klass = 'gram' | 'pair' (the catalogue has no long items)."""
+    prod = to_product(arr)
+    pk = capi.debug_pack(prod)
+    g = capi.debug_pack_gram(prod)
+    out = []
+    so, ncam = pk["slot_obs"], g["tile_ncam"]
+    for t in range(pk["tiles"]):
+        o = so[64 * t:64 * t + 64]; o = o[o >= 0]
+        if o.size == 0:
+            continue
+        cams, pts = arr["obs_cam"][o], arr["obs_pt"][o]
+        C, T = len(set(cams.tolist())), len(set(pts.tolist()))
+        ragged = not all(int((pts == p).sum()) == C for p in set(pts.tolist()))
+        passes = 1
+        if ncam[t] > 0:            # ba_pack.h: gram_lds_need — the smallest number of staging passes that fits the 10 KB LDS class
+            while 6 * C * (((3 * -(-T // passes) + 3) & ~3) + 1) * 8 + 11 * 11 * 4 + 48 > 10240 and -(-T // passes) > 1:
+                passes += 1
+        out.append((C, T, ragged, passes, "gram" if ncam[t] > 0 else "pair"))
+    return out, g
+
+
 def reduced_system_oracle(arr, radius, use_scaling=True):
     """Dense reduced camera matrix S(radius) and right-hand side b of the oracle's linearisation at the state `arr` (Jacobi
     scaling from the column norms like iteration 0 of a solve): S = Hcc + Dc^2 - sum_tracks W Hpp^-1 W^T."""

@@ -63,11 +63,8 @@ def test_bal9_gram_tiles_of_every_camera_count(lib, k_cams, ragged):
     take the per-pair path: the step of the FIRST linearisation against the oracle's exact solve, and three LM iterations
     against the oracle (same decisions, cost, cameras, intrinsics)."""
     from xrsfm_amd import capi
-    kw = dict(mode="unordered", min_tri_angle_deg=0.5)
-    n_cams = k_cams + (3 if ragged else 0)
-    if ragged:
-        kw["dropout"] = 0.3
-    arr = H.make_bal9(n_cams, 260, min(k_cams + (2 if ragged else 0), n_cams), seed=300 + 10 * k_cams + int(ragged), **kw)
+    from tests.schur_yardstick import bal9_gram_tiles      # (the builder moved there: tests/test_gpu_schur.py uses it too)
+    arr = bal9_gram_tiles(k_cams, ragged)
     g = capi.debug_pack_gram(H.to_product(arr))
     if not ragged:
         assert (g["gram_tiles"] > 0) == (k_cams <= 7) and (k_cams > 7 or g["max_cams"] == k_cams), g

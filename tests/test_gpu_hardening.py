@@ -22,27 +22,7 @@ from tests import helpers as H
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _tiles_of(arr):
-    """(C, T, ragged, passes, klass) of every tile of the packed problem; klass = 'gram' | 'pair' (the catalogue has no long items)."""
-    from xrsfm_amd import capi
-    prod = H.to_product(arr)
-    pk = capi.debug_pack(prod)
-    g = capi.debug_pack_gram(prod)
-    out = []
-    so, ncam = pk["slot_obs"], g["tile_ncam"]
-    for t in range(pk["tiles"]):
-        o = so[64 * t:64 * t + 64]; o = o[o >= 0]
-        if o.size == 0:
-            continue
-        cams, pts = arr["obs_cam"][o], arr["obs_pt"][o]
-        C, T = len(set(cams.tolist())), len(set(pts.tolist()))
-        ragged = not all(int((pts == p).sum()) == C for p in set(pts.tolist()))
-        passes = 1
-        if ncam[t] > 0:            # ba_pack.h: gram_lds_need — the smallest number of staging passes that fits the 10 KB LDS class
-            while 6 * C * (((3 * -(-T // passes) + 3) & ~3) + 1) * 8 + 11 * 11 * 4 + 48 > 10240 and -(-T // passes) > 1:
-                passes += 1
-        out.append((C, T, ragged, passes, "gram" if ncam[t] > 0 else "pair"))
-    return out, g
+_tiles_of = H.tiles_of      # (moved to tests/helpers.py: tests/test_schur_cpu.py uses it too)
 
 
 def test_shape_catalogue_covers_every_cell(lib):
