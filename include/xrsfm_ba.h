@@ -568,6 +568,64 @@ int xrsfm_ba_triangulate_tracks(const xrsfm_ba_tri_options *opt, int32_t n_cams,
                                 int32_t *num_inliers /* [n_tracks], may be NULL */, int32_t *num_trials /* [n_tracks], may be NULL */,
                                 int32_t *best_trial /* [n_tracks], may be NULL */);
 
+/* Batched absolute pose of frames from 2D-3D correspondences: the "pose estimate [init]" of RegisterImage, that is
+ * SolvePnP_colmap -> EstimateAbsolutePose -> colmap::LORANSAC<P3PEstimator, EPNPEstimator> (reference src/geometry/pnp.cc:29-36,
+ * 253-316), for all frames of a call in one launch: one workgroup per frame, FP64 throughout.  The result is the pose that
+ * xrsfm_ba_refine_pose(s) starts from.  Restates LORANSAC::Estimate (optim/loransac.h:92-239) with InlierSupportMeasurer and
+ * ComputeSquaredReprojectionError (residual DBL_MAX at depth <= DBL_EPSILON): P3P sample models from three correspondences, an
+ * EPnP model from the inliers of every new best with more than 3 inliers, the adaptive trial bound.
+ *
+ * The correspondences of frame f are corr_ptr[f] .. corr_ptr[f+1] in the caller's order (what SearchCorrespondences hands to
+ * SolvePnP_colmap).  xy are NORMALISED image coordinates: undistortion stays with the caller, as for xrsfm_ba_triangulate_tracks.
+ *
+ *   status[f]       0 no model (the reference's `return false`: !report.success || num_inliers == 0); 1 pose found; 2 fewer than
+ *                   3 correspondences; 3 more than XRSFM_BA_POSE_MAX_CORR correspondences: not attempted, the call still succeeds
+ *   on status 1     q[f] (unit quaternion x,y,z,w with w >= 0, from the 3x3 matrix by the usual four-branch rule) and t[f] the
+ *                   model (Tcw); inlier_mask the reference's report.inlier_mask, recomputed from the returned model;
+ *                   num_inliers[f] its sum; num_trials[f] report.num_trials; best_trial[f] the 0-based trial of the final best,
+ *                   plus bit 30 when the locally optimised model is the one returned (the convention of best_trial above)
+ *   on 0, 2, 3      q[f], t[f] untouched, the frame's mask entries 0, counts 0, best_trial -1
+ * On any negative return code no output is touched.  No output ever receives a NaN or an Inf: a non-finite sample or local model
+ * is discarded.  A frame's outputs are bit-identical whatever else is in the batch, in whatever order, and across calls.
+ *
+ * Documented deviations (defined meaning where the reference has no portable one):
+ *   1. Sampler.  The reference draws from one process-wide std::mt19937 that is never re-seeded between calls, through
+ *      std::uniform_int_distribution.  Here every frame gets a fresh MT19937 (init_genrand(seed), seed from frame_seed or
+ *      opt->seed) and replays RandomSampler: the index array persists across the trials of a frame, three Fisher-Yates steps per
+ *      trial; bounded draw for m = last - i + 1: s = 0xFFFFFFFF / m, draw 32-bit words until x < m s, j = i + x / s.
+ *   2. Root order and acceptance.  The quartic's roots are found as complex numbers by a bounded iteration; a root is taken when
+ *      |Im| <= 1e-10 and Re >= 0; the models of one trial are offered in ascending Re.  A vanishing leading coefficient gives no
+ *      model.  The rigid fit is Umeyama without scale with the sign from det(U) det(V).
+ *   3. EPnP's sign step negates iff the first inlier's depth is negative (the published rule), not whenever it is non-zero.
+ *   As for the triangulation, a model without a single inlier leaves the adaptive trial bound unbounded.
+ *
+ * Errors: XRSFM_BA_EINVAL (checked on the host before the device is touched, one line on stderr) — NULL opt; NULL q, t, status or
+ * inlier_mask with n_frames > 0; a negative count; corr_ptr not starting at 0 or decreasing; a non-finite coordinate, max_error or
+ * option; max_error <= 0 (option or per frame); confidence or min_inlier_ratio outside [0, 1]; min_num_trials < 0;
+ * max_num_trials < 1 or above XRSFM_BA_POSE_MAX_TRIALS; min_num_trials > max_num_trials.  XRSFM_BA_ENODEV without a device (there
+ * is no CPU path); XRSFM_BA_ENOMEM when staging memory cannot be had.  n_frames == 0 is success and needs no device. */
+typedef struct xrsfm_ba_pose_options {
+    double  max_error;         /* normalised image units: 8 / fx (RegisterImage, pnp.cc:30), 16 / fx (RegisterNextImageLocal); default 8 / 800 */
+    double  confidence;        /* 0.9999  pnp.cc:265 */
+    double  min_inlier_ratio;  /* 0.25    pnp.cc:261 */
+    int32_t min_num_trials;    /* 100     pnp.cc:264 */
+    int32_t max_num_trials;    /* XRSFM_BA_POSE_MAX_TRIALS; the effective cap is min(this, the constructor's bound from
+                                  min_inlier_ratio: 585 at the defaults) */
+    uint32_t seed;             /* 0 */
+} xrsfm_ba_pose_options;
+#define XRSFM_BA_POSE_MAX_CORR   8192
+#define XRSFM_BA_POSE_MAX_TRIALS 16384
+void xrsfm_ba_absolute_pose_options(xrsfm_ba_pose_options *opt);   /* the values above */
+int xrsfm_ba_absolute_pose(const xrsfm_ba_pose_options *opt, int32_t n_frames, const int32_t *corr_ptr /* [n_frames+1] */,
+                           const double *xy /* [n][2] normalised */, const double *points3d /* [n][3] */,
+                           const double *frame_max_error /* [n_frames] or NULL = opt->max_error */,
+                           const uint32_t *frame_seed /* [n_frames] or NULL = opt->seed */, double *q /* [n_frames][4] x,y,z,w */,
+                           double *t /* [n_frames][3] */, uint8_t *status /* [n_frames] */, uint8_t *inlier_mask /* [n] */,
+                           int32_t *num_inliers /* [n_frames], may be NULL */, int32_t *num_trials /* [n_frames], may be NULL */,
+                           int32_t *best_trial /* [n_frames], may be NULL */);
+/* TEST ENTRY, no GPU: the sample triples of the first n_trials trials for n correspondences and one seed (deviation 1). */
+int xrsfm_ba_debug_pose_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *triples /* [n_trials][3] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

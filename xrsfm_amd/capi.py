@@ -54,6 +54,11 @@ class CTagProblem(C.Structure):
                 ("points", _c_double_p), ("obs_frame", _c_int32_p), ("obs_pt", _c_int32_p), ("obs_xy", _c_double_p)]
 
 
+class CPoseOptions(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("confidence", C.c_double), ("min_inlier_ratio", C.c_double),
+                ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32), ("seed", C.c_uint32)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -98,6 +103,7 @@ EXPORTS = [
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
     "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
     "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars",
+    "xrsfm_ba_absolute_pose_options", "xrsfm_ba_absolute_pose", "xrsfm_ba_debug_pose_samples",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -121,6 +127,9 @@ SOLVER_RESIDENT = 3     # the whole LM loop in one kernel launch (local-BA-sized
 BATCH_MAX = 4096        # XRSFM_BA_BATCH_MAX: most contexts of one xrsfm_ba_run_batch
 TRI_MAX_OBS = 128       # XRSFM_BA_TRI_MAX_OBS: longest track xrsfm_ba_triangulate_tracks attempts
 TRI_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised model of that trial is the one returned
+POSE_MAX_CORR = 8192    # XRSFM_BA_POSE_MAX_CORR: most correspondences of a frame xrsfm_ba_absolute_pose attempts
+POSE_MAX_TRIALS = 16384  # XRSFM_BA_POSE_MAX_TRIALS
+POSE_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised (EPnP) model of that trial is the one returned
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -220,6 +229,14 @@ def load(path: str | None = None):
     lib.xrsfm_ba_triangulate_tracks.argtypes = [C.POINTER(CTriOptions), C.c_int32, _c_double_p, _c_double_p, C.c_int32, _c_int32_p, _c_int32_p,
                                                  _c_double_p, _c_double_p, _c_uint8_p, _c_uint8_p, _c_int32_p, _c_int32_p, _c_int32_p]
     lib.xrsfm_ba_triangulate_tracks.restype = C.c_int
+    lib.xrsfm_ba_absolute_pose_options.argtypes = [C.POINTER(CPoseOptions)]
+    lib.xrsfm_ba_absolute_pose_options.restype = None
+    lib.xrsfm_ba_absolute_pose.argtypes = [C.POINTER(CPoseOptions), C.c_int32, _c_int32_p, _c_double_p, _c_double_p, _c_double_p,
+                                            C.POINTER(C.c_uint32), _c_double_p, _c_double_p, _c_uint8_p, _c_uint8_p, _c_int32_p, _c_int32_p,
+                                            _c_int32_p]
+    lib.xrsfm_ba_absolute_pose.restype = C.c_int
+    lib.xrsfm_ba_debug_pose_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
+    lib.xrsfm_ba_debug_pose_samples.restype = C.c_int
     _lib = lib
     return lib
 
@@ -665,6 +682,54 @@ def triangulate_tracks(cam_q, cam_t, trk_ptr, obs_cam, obs_xy, options: CTriOpti
                                              status.ctypes.data_as(_c_uint8_p), mask.ctypes.data_as(_c_uint8_p), ip(ninl), ip(ntr), ip(best)),
           "xrsfm_ba_triangulate_tracks")
     return dict(points=points, status=status, inlier_mask=mask, num_inliers=ninl, num_trials=ntr, best_trial=best)
+
+
+def absolute_pose_options(**overrides) -> CPoseOptions:
+    """xrsfm_ba_absolute_pose_options: the settings of the reference's SolvePnP_colmap (max_error for 8 px at a focal length of 800)."""
+    o = CPoseOptions()
+    load().xrsfm_ba_absolute_pose_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def absolute_pose(corr_ptr, xy, points3d, options: CPoseOptions | None = None, frame_max_error=None, frame_seed=None) -> dict:
+    """xrsfm_ba_absolute_pose: one P3P LO-RANSAC per frame (correspondences corr_ptr[f] .. corr_ptr[f+1]: normalised image
+    coordinates and world points).  q and t of frames whose status is not 1 stay 0 here (the C call leaves them untouched)."""
+    o = options if options is not None else absolute_pose_options()
+    corr_ptr = np.ascontiguousarray(corr_ptr, np.int32)
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2); points3d = np.ascontiguousarray(points3d, np.float64).reshape(-1, 3)
+    if corr_ptr.ndim != 1 or len(corr_ptr) < 1 or len(xy) != len(points3d):
+        raise ValueError("absolute_pose: inconsistent array shapes")
+    nf, n = len(corr_ptr) - 1, len(xy)
+    if nf > 0 and corr_ptr[-1] != n:
+        raise ValueError("absolute_pose: corr_ptr[-1] must be the number of correspondences")
+    fme = fsd = None
+    if frame_max_error is not None:
+        fme = np.ascontiguousarray(frame_max_error, np.float64)
+        if fme.shape != (nf,):
+            raise ValueError("absolute_pose: frame_max_error must have one entry per frame")
+    if frame_seed is not None:
+        fsd = np.ascontiguousarray(frame_seed, np.uint32)
+        if fsd.shape != (nf,):
+            raise ValueError("absolute_pose: frame_seed must have one entry per frame")
+    q = np.zeros((nf, 4)); t = np.zeros((nf, 3)); status = np.zeros(nf, np.uint8); mask = np.zeros(n, np.uint8)
+    ninl = np.zeros(nf, np.int32); ntr = np.zeros(nf, np.int32); best = np.full(nf, -1, np.int32)
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    check(load().xrsfm_ba_absolute_pose(C.byref(o), nf, ip(corr_ptr), _dp(xy), _dp(points3d), _dp(fme) if fme is not None else None,
+                                        fsd.ctypes.data_as(C.POINTER(C.c_uint32)) if fsd is not None else None, _dp(q), _dp(t),
+                                        status.ctypes.data_as(_c_uint8_p), mask.ctypes.data_as(_c_uint8_p), ip(ninl), ip(ntr), ip(best)),
+          "xrsfm_ba_absolute_pose")
+    return dict(q=q, t=t, status=status, inlier_mask=mask, num_inliers=ninl, num_trials=ntr, best_trial=best)
+
+
+def debug_pose_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
+    """xrsfm_ba_debug_pose_samples: the sample triples [n_trials][3] of a frame of n correspondences (no GPU)."""
+    out = np.zeros((n_trials, 3), np.int32)
+    check(load().xrsfm_ba_debug_pose_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_pose_samples")
+    return out
 
 
 def debug_pack(problem: ProblemArrays) -> dict:

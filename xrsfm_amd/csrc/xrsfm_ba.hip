@@ -32,6 +32,7 @@
 #include "ba_lba.h"
 #include "ba_pack.h"
 #include "ba_plan.h"
+#include "ba_pnp.h"
 #include "ba_refine.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
@@ -3576,6 +3577,149 @@ int xrsfm_ba_triangulate_tracks(const xrsfm_ba_tri_options* opt, int32_t n_cams,
                                 uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
     return no_throw([&] { return triangulate_tracks_impl(opt, n_cams, cam_q, cam_t, n_tracks, trk_ptr, obs_cam, obs_xy, points, status, inlier_mask,
                                                          num_inliers, num_trials, best_trial); });
+}
+
+// ---------------------------------------------------------------- batched absolute pose of frames (ba_pnp.h)
+void xrsfm_ba_absolute_pose_options(xrsfm_ba_pose_options* opt) {
+    if (!opt) return;
+    opt->max_error = 8.0 / 800.0;             // 8 px at a focal length of 800: the caller sets 8 / fx (pnp.cc:30)
+    opt->confidence = 0.9999;                 // pnp.cc:265
+    opt->min_inlier_ratio = 0.25;             // :261
+    opt->min_num_trials = 100;                // :264
+    opt->max_num_trials = XRSFM_BA_POSE_MAX_TRIALS;
+    opt->seed = 0;
+}
+
+int xrsfm_ba_debug_pose_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t* triples) {
+    if (n < 3 || n > XRSFM_BA_POSE_MAX_CORR || n_trials < 0 || n_trials > XRSFM_BA_POSE_MAX_TRIALS || (n_trials > 0 && !triples)) return XRSFM_BA_EINVAL;
+    return no_throw([&] {
+        std::vector<int32_t> idx((size_t)n);
+        xpnp::pnp_sample_triples(seed, n, n_trials, idx.data(), triples);
+        return XRSFM_BA_OK;
+    });
+}
+
+static int absolute_pose_impl(const xrsfm_ba_pose_options* opt, int32_t n_frames, const int32_t* corr_ptr, const double* xy, const double* points3d,
+                              const double* frame_max_error, const uint32_t* frame_seed, double* q, double* t, uint8_t* status,
+                              uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_absolute_pose: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_frames < 0) return bad("negative count");
+    if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio)) return bad("non-finite option");
+    if (opt->max_error <= 0.0) return bad("max_error <= 0");
+    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
+    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
+    if (opt->min_num_trials < 0) return bad("min_num_trials < 0");
+    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
+    if (opt->max_num_trials > XRSFM_BA_POSE_MAX_TRIALS) return bad("max_num_trials above XRSFM_BA_POSE_MAX_TRIALS");
+    if (opt->min_num_trials > opt->max_num_trials) return bad("min_num_trials > max_num_trials");
+    if (n_frames == 0) return XRSFM_BA_OK;
+    if (!q || !t || !status || !inlier_mask) return bad("NULL q, t, status or inlier_mask");
+    if (!corr_ptr) return bad("NULL corr_ptr");
+    if (corr_ptr[0] != 0) return bad("corr_ptr does not start at 0");
+    for (int j = 0; j < n_frames; ++j)
+        if (corr_ptr[j + 1] < corr_ptr[j]) return bad("corr_ptr decreases");
+    const int Nc = corr_ptr[n_frames], Nf = n_frames;
+    if (Nc > 0 && (!xy || !points3d)) return bad("NULL xy or points3d");
+    for (size_t i = 0; i < 2 * (size_t)Nc; ++i) if (!std::isfinite(xy[i])) return bad("non-finite coordinate");
+    for (size_t i = 0; i < 3 * (size_t)Nc; ++i) if (!std::isfinite(points3d[i])) return bad("non-finite coordinate");
+    if (frame_max_error)
+        for (int j = 0; j < Nf; ++j) {
+            if (!std::isfinite(frame_max_error[j])) return bad("non-finite max_error");
+            if (frame_max_error[j] <= 0.0) return bad("max_error <= 0");
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the absolute pose has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    PnpParams prm;
+    prm.trial_cap = std::min(opt->max_num_trials, xpnp::pnp_ratio_trials(opt->min_inlier_ratio, opt->confidence));
+    prm.min_trials = opt->min_num_trials;
+    // per frame: the row dyn(k, n) (shared by the frames of one n) and the sample triples of the effective trial cap (deviation 1)
+    std::vector<PnpFrame> frames((size_t)Nf);
+    std::vector<int32_t> dyn, triples, idx;
+    std::map<int, int> dyn_of;
+    for (int j = 0; j < Nf; ++j) {
+        PnpFrame& fr = frames[(size_t)j];
+        fr.beg = corr_ptr[j]; fr.n = corr_ptr[j + 1] - corr_ptr[j];
+        const double me = frame_max_error ? frame_max_error[j] : opt->max_error;
+        fr.max_residual = me * me; fr.tri_off = -1; fr.dyn_off = 0;
+        if (fr.n < 3 || fr.n > XRSFM_BA_POSE_MAX_CORR) continue;
+        auto it = dyn_of.find(fr.n);
+        if (it == dyn_of.end()) {
+            it = dyn_of.emplace(fr.n, (int)dyn.size()).first;
+            for (int k = 0; k <= fr.n; ++k) dyn.push_back(xpnp::pnp_dyn_trials(k, fr.n, opt->confidence));
+        }
+        fr.dyn_off = it->second;
+        fr.tri_off = (int32_t)(triples.size() / 3);
+        triples.resize(triples.size() + 3 * (size_t)prm.trial_cap);
+        idx.resize((size_t)fr.n);
+        xpnp::pnp_sample_triples(frame_seed ? frame_seed[j] : opt->seed, fr.n, prm.trial_cap, idx.data(), triples.data() + 3 * (size_t)fr.tri_off);
+    }
+    HIPCHK(hipSetDevice(0));
+    // one block from the allocation cache, one upload, one launch, one read-back (the layout of triangulate_tracks_impl)
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    const size_t o_fr = take(sizeof(PnpFrame) * (size_t)Nf), o_xy = take(sizeof(double) * 2 * (size_t)Nc), o_X = take(sizeof(double) * 3 * (size_t)Nc),
+                 o_tri = take(sizeof(int32_t) * triples.size()), o_dyn = take(sizeof(int32_t) * dyn.size());
+    const size_t in_bytes = off, out0 = off;
+    const size_t o_q = take(sizeof(double) * 4 * (size_t)Nf), o_t = take(sizeof(double) * 3 * (size_t)Nf), o_ninl = take(sizeof(int) * (size_t)Nf),
+                 o_ntr = take(sizeof(int) * (size_t)Nf), o_best = take(sizeof(int) * (size_t)Nf), o_stat = take((size_t)Nf), o_mask = take((size_t)Nc);
+    const size_t out_bytes = off - out0;
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    size_t cls = 0;
+    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
+    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    int e = 0;
+    {
+        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
+        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
+        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        memcpy(stage.data() + o_fr, frames.data(), sizeof(PnpFrame) * (size_t)Nf);
+        if (Nc) { memcpy(stage.data() + o_xy, xy, sizeof(double) * 2 * (size_t)Nc); memcpy(stage.data() + o_X, points3d, sizeof(double) * 3 * (size_t)Nc); }
+        if (!triples.empty()) memcpy(stage.data() + o_tri, triples.data(), sizeof(int32_t) * triples.size());
+        if (!dyn.empty()) memcpy(stage.data() + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
+        hipStream_t st = hb.stream;
+        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            hipLaunchKernelGGL(k_pnp_frames, dim3(Nf), dim3(kPnpThreads), 0, st, (const PnpFrame*)(base + o_fr), Nf, prm, (const double*)(base + o_xy),
+                               (const double*)(base + o_X), (const int32_t*)(base + o_tri), (const int32_t*)(base + o_dyn), (double*)(base + o_q),
+                               (double*)(base + o_t), (unsigned char*)(base + o_stat), (unsigned char*)(base + o_mask), (int*)(base + o_ninl),
+                               (int*)(base + o_ntr), (int*)(base + o_best));
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+        }
+        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
+            const double* qs = (const double*)(o + o_q);
+            const double* ts = (const double*)(o + o_t);
+            const unsigned char* stat = o + o_stat;
+            for (int j = 0; j < Nf; ++j) {
+                status[j] = stat[j];
+                if (stat[j] != 1) continue;
+                for (int k2 = 0; k2 < 4; ++k2) q[4 * (size_t)j + k2] = qs[4 * (size_t)j + k2];
+                for (int k2 = 0; k2 < 3; ++k2) t[3 * (size_t)j + k2] = ts[3 * (size_t)j + k2];
+            }
+            if (Nc) memcpy(inlier_mask, o + o_mask, (size_t)Nc);
+            if (num_inliers) memcpy(num_inliers, o + o_ninl, sizeof(int) * (size_t)Nf);
+            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Nf);
+            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Nf);
+        }
+    }
+    g_cache.put(0, base, cls);
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int xrsfm_ba_absolute_pose(const xrsfm_ba_pose_options* opt, int32_t n_frames, const int32_t* corr_ptr, const double* xy, const double* points3d,
+                           const double* frame_max_error, const uint32_t* frame_seed, double* q, double* t, uint8_t* status, uint8_t* inlier_mask,
+                           int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
+    return no_throw([&] { return absolute_pose_impl(opt, n_frames, corr_ptr, xy, points3d, frame_max_error, frame_seed, q, t, status, inlier_mask,
+                                                    num_inliers, num_trials, best_trial); });
 }
 
 // ---------------------------------------------------------------- diagnostics
