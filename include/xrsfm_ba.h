@@ -626,6 +626,79 @@ int xrsfm_ba_absolute_pose(const xrsfm_ba_pose_options *opt, int32_t n_frames, c
 /* TEST ENTRY, no GPU: the sample triples of the first n_trials trials for n correspondences and one seed (deviation 1). */
 int xrsfm_ba_debug_pose_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *triples /* [n_trials][3] */);
 
+/* Batched two-view initialisation: what FindInitFramePair computes for every candidate pair and InitializeMap for the chosen one,
+ * that is CheckInitFramePair -> solve_essential (a 5-point RANSAC) -> decompose_rt (four-way decomposition, triangulation of
+ * every match) -> the triangulation-angle counts (reference src/geometry/map_initializer.cc:13-65, 141-206; essential.cc:283-487),
+ * for all pairs of a call in one launch: one workgroup per pair, FP64 throughout.
+ *
+ * The matches of pair p are match_ptr[p] .. match_ptr[p+1]: the matches the reference keeps (frame_pair.inlier_mask), in its
+ * order.  xy_a, xy_b are NORMALISED image coordinates in frame 1 and frame 2; pair_threshold[p] is 10 / fx of frame 1
+ * (map_initializer.cc:32).  Restated literally: the inlier test is sampson_error < 2 th^2 (the error is already squared); the score
+ * is the sum over all matches of log(1 + se^2 / (2 th^2)); a model wins with more inliers, or with as many (and best_inlier > 0)
+ * and a strictly smaller score; after a new best of k of n the trial bound becomes ceil(log(1 - confidence) / log(1 - (k / n)^5))
+ * if that is smaller; decompose_rt runs over ALL matches and picks the candidate with strictly more points in front, in the order
+ * (R1,+T), (R1,-T), (R2,+T), (R2,-T); a point is in front when both depths are positive and below max_depth.
+ *
+ *   status[p]     0 no E (best_E stayed NaN) or no candidate with a point in front (the reference then takes k = 0 of an
+ *                 arbitrary order; the pair is rejected either way); 1 geometry found, accepted[p] says whether it qualifies;
+ *                 2 fewer than min_matches matches; 3 more than XRSFM_BA_INIT_MAX_MATCHES: not attempted, the call still succeeds
+ *   on status 1   E[p] the best essential matrix scaled to unit Frobenius norm (x_b' E x_a = 0); q[p] (x,y,z,w, w >= 0) and t[p]
+ *                 the pose of frame 2 (frame 1 is the identity); points[i] the triangulated point of every match with
+ *                 front_mask[i] (written only there); essential_mask[i] the reference's solve_essential mask;
+ *                 counts[p] = {essential inliers, num_p3d, winning candidate k, 0, num_p3d_valid at min_angle_rad[0..3]};
+ *                 accepted[p] bit a: num_p3d >= min_front_ratio n && num_p3d_valid[a] >= min_angle_ratio num_p3d &&
+ *                 num_p3d_valid[a] > min_num_valid; num_trials[p] the trials executed; best_trial[p] = trial * 16 + model slot
+ *   on status 0   q, t, points untouched, front_mask 0, accepted 0; E, essential_mask, counts[0], num_trials and best_trial are
+ *                 those of the best E if there is one, otherwise E is untouched, the masks and counts are 0 and best_trial is -1
+ *   on 2, 3       E, q, t, points untouched, masks and counts 0, num_trials 0, best_trial -1
+ * On any negative return code no output is touched.  No output ever receives a NaN or an Inf: a non-finite model is never
+ * offered.  A pair's outputs are bit-identical whatever else is in the batch, in whatever order, and across calls.
+ *
+ * Documented deviations (defined meaning where the reference has no portable one):
+ *   1. Sampler.  LotBox draws through std::default_random_engine and std::uniform_int_distribution<size_t>, both chosen by the
+ *      standard library.  Here every pair gets a fresh MT19937 (init_genrand(seed), seed from pair_seed or opt->seed) and the
+ *      sampler of xrsfm_ba_absolute_pose with five draws: the index array persists across the trials of a pair, five
+ *      Fisher-Yates steps per trial, the same bounded draw.
+ *   2. Model order.  The up to ten models of one trial are offered in ascending real eigenvalue of the action matrix (found by a
+ *      bounded Hessenberg / shifted-QR iteration; a root is taken when |Im| < 1e-10).  The order decides exact ties only.
+ *   3. Decomposition.  SVD branch only.  The third singular vectors are u3 = u1 x u2 and v3 = v1 x v2, so both determinants are
+ *      +1 and nothing depends on how a library signs a null vector; T = u3, R1 = U W V', R2 = U W' V'.
+ *   A trial bound that is NaN or -inf in the reference (confidence 1; a ratio whose fifth power underflows) counts as unbounded.
+ *
+ * Errors: XRSFM_BA_EINVAL (checked on the host before the device is touched, one line on stderr) — NULL opt; a negative count;
+ * NULL status, E, q, t, points, essential_mask, front_mask or counts with n_pairs > 0; NULL match_ptr or pair_threshold;
+ * match_ptr not starting at 0 or decreasing; NULL xy_a or xy_b with matches; a non-finite coordinate, threshold or option; a
+ * threshold <= 0; confidence outside [0, 1]; max_iterations < 1 or above XRSFM_BA_INIT_MAX_TRIALS; min_matches < 5;
+ * max_depth <= 0; n_angles outside [1, 4]; a negative min_angle_rad, min_front_ratio or min_angle_ratio; min_num_valid < 0.
+ * XRSFM_BA_ENODEV without a device (there is no CPU path); XRSFM_BA_ENOMEM when staging memory cannot be had.  n_pairs == 0 is
+ * success and needs no device. */
+typedef struct xrsfm_ba_two_view_options {
+    double  confidence;          /* 0.9   essential.cc:393 */
+    int32_t max_iterations;      /* 50    :393; at most XRSFM_BA_INIT_MAX_TRIALS (64) */
+    uint32_t seed;               /* 0     :393 */
+    int32_t min_matches;         /* 10    map_initializer.cc:30; at least 5 */
+    double  max_depth;           /* 100   essential.cc:424 */
+    int32_t n_angles;            /* 2, at most 4 */
+    double  min_angle_rad[4];    /* DegToRad(16), DegToRad(8)  map_initializer.cc:119,132 */
+    double  min_front_ratio;     /* 0.5   :58 num_p3d >= ratio * n */
+    double  min_angle_ratio;     /* 0.5   :58 */
+    int32_t min_num_valid;       /* 200   :59, strict > */
+} xrsfm_ba_two_view_options;
+#define XRSFM_BA_INIT_MAX_MATCHES 8192
+#define XRSFM_BA_INIT_MAX_TRIALS  64
+void xrsfm_ba_two_view_options_default(xrsfm_ba_two_view_options *opt);   /* the values above */
+int xrsfm_ba_two_view_init(const xrsfm_ba_two_view_options *opt, int32_t n_pairs, const int32_t *match_ptr /* [n_pairs+1] */,
+                           const double *xy_a /* [n][2] normalised, frame 1 */, const double *xy_b /* [n][2] normalised, frame 2 */,
+                           const double *pair_threshold /* [n_pairs]: 10 / fx of frame 1 */,
+                           const uint32_t *pair_seed /* [n_pairs] or NULL = opt->seed */, uint8_t *status /* [n_pairs] */,
+                           double *E /* [n_pairs][9] row-major, unit Frobenius norm */, double *q /* [n_pairs][4] x,y,z,w, w >= 0 */,
+                           double *t /* [n_pairs][3] */, double *points /* [n][3] */, uint8_t *essential_mask /* [n] */,
+                           uint8_t *front_mask /* [n]: result_status of decompose_rt */, int32_t *counts /* [n_pairs][4 + 4] */,
+                           uint8_t *accepted /* [n_pairs]: bit a = CheckInitFramePair true at min_angle_rad[a]; may be NULL */,
+                           int32_t *num_trials /* [n_pairs], may be NULL */, int32_t *best_trial /* [n_pairs], may be NULL */);
+/* TEST ENTRY, no GPU: the sample quintuples of the first n_trials trials for n matches and one seed (deviation 1). */
+int xrsfm_ba_debug_two_view_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *quintuples /* [n_trials][5] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

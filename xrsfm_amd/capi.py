@@ -59,6 +59,12 @@ class CPoseOptions(C.Structure):
                 ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32), ("seed", C.c_uint32)]
 
 
+class CTwoViewOptions(C.Structure):
+    _fields_ = [("confidence", C.c_double), ("max_iterations", C.c_int32), ("seed", C.c_uint32), ("min_matches", C.c_int32),
+                ("max_depth", C.c_double), ("n_angles", C.c_int32), ("min_angle_rad", C.c_double * 4), ("min_front_ratio", C.c_double),
+                ("min_angle_ratio", C.c_double), ("min_num_valid", C.c_int32)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -104,6 +110,7 @@ EXPORTS = [
     "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
     "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars",
     "xrsfm_ba_absolute_pose_options", "xrsfm_ba_absolute_pose", "xrsfm_ba_debug_pose_samples",
+    "xrsfm_ba_two_view_options_default", "xrsfm_ba_two_view_init", "xrsfm_ba_debug_two_view_samples",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -130,6 +137,9 @@ TRI_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised model of that trial
 POSE_MAX_CORR = 8192    # XRSFM_BA_POSE_MAX_CORR: most correspondences of a frame xrsfm_ba_absolute_pose attempts
 POSE_MAX_TRIALS = 16384  # XRSFM_BA_POSE_MAX_TRIALS
 POSE_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised (EPnP) model of that trial is the one returned
+INIT_MAX_MATCHES = 8192  # XRSFM_BA_INIT_MAX_MATCHES: most matches of a pair xrsfm_ba_two_view_init attempts
+INIT_MAX_TRIALS = 64     # XRSFM_BA_INIT_MAX_TRIALS
+INIT_SLOT_STRIDE = 16    # best_trial of xrsfm_ba_two_view_init: trial * 16 + model slot
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -237,6 +247,14 @@ def load(path: str | None = None):
     lib.xrsfm_ba_absolute_pose.restype = C.c_int
     lib.xrsfm_ba_debug_pose_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
     lib.xrsfm_ba_debug_pose_samples.restype = C.c_int
+    lib.xrsfm_ba_two_view_options_default.argtypes = [C.POINTER(CTwoViewOptions)]
+    lib.xrsfm_ba_two_view_options_default.restype = None
+    lib.xrsfm_ba_two_view_init.argtypes = [C.POINTER(CTwoViewOptions), C.c_int32, _c_int32_p, _c_double_p, _c_double_p, _c_double_p,
+                                            C.POINTER(C.c_uint32), _c_uint8_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_uint8_p,
+                                            _c_uint8_p, _c_int32_p, _c_uint8_p, _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_two_view_init.restype = C.c_int
+    lib.xrsfm_ba_debug_two_view_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
+    lib.xrsfm_ba_debug_two_view_samples.restype = C.c_int
     _lib = lib
     return lib
 
@@ -729,6 +747,89 @@ def debug_pose_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
     """xrsfm_ba_debug_pose_samples: the sample triples [n_trials][3] of a frame of n correspondences (no GPU)."""
     out = np.zeros((n_trials, 3), np.int32)
     check(load().xrsfm_ba_debug_pose_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_pose_samples")
+    return out
+
+
+def two_view_options(**overrides) -> CTwoViewOptions:
+    """xrsfm_ba_two_view_options_default: the settings of the reference's CheckInitFramePair / solve_essential.  min_angle_rad may
+    be given as a sequence of up to four angles; n_angles follows it."""
+    o = CTwoViewOptions()
+    load().xrsfm_ba_two_view_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        if k == "min_angle_rad":
+            v = [float(x) for x in v]
+            o.n_angles = len(v)
+            v = (C.c_double * 4)(*(v + [0.0] * (4 - len(v))))
+        setattr(o, k, v)
+    return o
+
+
+class TwoViewResult:
+    """The outputs of xrsfm_ba_two_view_init, one entry per pair (status, E [9], q, t, counts [8], accepted, num_trials, best_trial)
+    or per match (points, essential_mask, front_mask).  q, t, E and points the call leaves untouched are 0 here."""
+    FIELDS = ("status", "E", "q", "t", "points", "essential_mask", "front_mask", "counts", "accepted", "num_trials", "best_trial")
+
+    def __init__(self, match_ptr, **arrays):
+        self.match_ptr = match_ptr
+        for k in self.FIELDS:
+            setattr(self, k, arrays[k])
+
+    def pair(self, p: int) -> dict:
+        """the outputs of pair p, the per-match ones cut to its matches"""
+        a, b = int(self.match_ptr[p]), int(self.match_ptr[p + 1])
+        per_match = ("points", "essential_mask", "front_mask")
+        return {k: (getattr(self, k)[a:b] if k in per_match else getattr(self, k)[p]) for k in self.FIELDS}
+
+
+def two_view_init(match_ptr, xy_a, xy_b, pair_threshold, options: CTwoViewOptions | None = None, pair_seed=None) -> TwoViewResult:
+    """xrsfm_ba_two_view_init: one 5-point RANSAC, decomposition and triangulation per candidate pair (matches match_ptr[p] ..
+    match_ptr[p+1]: normalised image coordinates in frame 1 and frame 2; pair_threshold[p] = 10 / fx of frame 1)."""
+    o = options if options is not None else two_view_options()
+    match_ptr = np.ascontiguousarray(match_ptr, np.int32)
+    xy_a = np.ascontiguousarray(xy_a, np.float64).reshape(-1, 2); xy_b = np.ascontiguousarray(xy_b, np.float64).reshape(-1, 2)
+    if match_ptr.ndim != 1 or len(match_ptr) < 1 or len(xy_a) != len(xy_b):
+        raise ValueError("two_view_init: inconsistent array shapes")
+    npair, n = len(match_ptr) - 1, len(xy_a)
+    if npair > 0 and match_ptr[-1] != n:
+        raise ValueError("two_view_init: match_ptr[-1] must be the number of matches")
+    th = np.ascontiguousarray(pair_threshold, np.float64)
+    if th.shape != (npair,):
+        raise ValueError("two_view_init: pair_threshold must have one entry per pair")
+    sd = None
+    if pair_seed is not None:
+        sd = np.ascontiguousarray(pair_seed, np.uint32)
+        if sd.shape != (npair,):
+            raise ValueError("two_view_init: pair_seed must have one entry per pair")
+    r = dict(status=np.zeros(npair, np.uint8), E=np.zeros((npair, 9)), q=np.zeros((npair, 4)), t=np.zeros((npair, 3)), points=np.zeros((n, 3)),
+             essential_mask=np.zeros(n, np.uint8), front_mask=np.zeros(n, np.uint8), counts=np.zeros((npair, 8), np.int32),
+             accepted=np.zeros(npair, np.uint8), num_trials=np.zeros(npair, np.int32), best_trial=np.full(npair, -1, np.int32))
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    up = lambda a: a.ctypes.data_as(_c_uint8_p)
+    check(load().xrsfm_ba_two_view_init(C.byref(o), npair, ip(match_ptr), _dp(xy_a), _dp(xy_b), _dp(th),
+                                        sd.ctypes.data_as(C.POINTER(C.c_uint32)) if sd is not None else None, up(r["status"]), _dp(r["E"]), _dp(r["q"]),
+                                        _dp(r["t"]), _dp(r["points"]), up(r["essential_mask"]), up(r["front_mask"]), ip(r["counts"]), up(r["accepted"]),
+                                        ip(r["num_trials"]), ip(r["best_trial"])), "xrsfm_ba_two_view_init")
+    return TwoViewResult(match_ptr, **r)
+
+
+def first_accepted(order, accepted) -> tuple:
+    """FindInitFramePair's two passes (map_initializer.cc:112-136) over the candidates `order` (indices of pairs, best first): all
+    candidates at angle 0, then all at angle 1, ...  Returns (pair, angle index), or (-1, -1) when none qualifies."""
+    accepted = np.asarray(accepted)
+    n_angles = 4
+    for a in range(n_angles):
+        for p in order:
+            if (int(accepted[int(p)]) >> a) & 1:
+                return int(p), a
+    return -1, -1
+
+
+def debug_two_view_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
+    """xrsfm_ba_debug_two_view_samples: the sample quintuples [n_trials][5] of a pair of n matches (no GPU)."""
+    out = np.zeros((n_trials, 5), np.int32)
+    check(load().xrsfm_ba_debug_two_view_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_two_view_samples")
     return out
 
 

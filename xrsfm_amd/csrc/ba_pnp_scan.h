@@ -83,21 +83,25 @@ struct Mt19937 {
     }
 };
 
-// deviation 1: the sample triples of the first n_trials trials of a frame of n >= 3 correspondences; idx is scratch of n entries
-inline void pnp_sample_triples(uint32_t seed, int n, int n_trials, int32_t* idx, int32_t* triples) {
+// deviation 1: the samples of m distinct indices of the first n_trials trials of a set of n >= m entries; idx is scratch of n
+// entries.  m = 3 here; the two-view initialisation (ba_init_scan.h) draws m = 5 from the same generator and bounded draw.
+inline void pnp_sample_tuples(uint32_t seed, int n, int n_trials, int m_draws, int32_t* idx, int32_t* tuples) {
     Mt19937 g(seed);
     for (int i = 0; i < n; ++i) idx[i] = i;
     const uint32_t last = (uint32_t)(n - 1);
     for (int t = 0; t < n_trials; ++t) {
-        for (uint32_t i = 0; i < 3; ++i) {
+        for (uint32_t i = 0; i < (uint32_t)m_draws; ++i) {
             const uint32_t m = last - i + 1, s = 0xFFFFFFFFu / m;
             uint32_t x;
             do x = g.next(); while (x >= m * s);              // (m s <= 0xFFFFFFFF: no overflow)
             const uint32_t j = i + x / s;
             const int32_t tmp = idx[i]; idx[i] = idx[j]; idx[j] = tmp;
         }
-        triples[3 * t] = idx[0]; triples[3 * t + 1] = idx[1]; triples[3 * t + 2] = idx[2];
+        for (int i = 0; i < m_draws; ++i) tuples[(size_t)m_draws * t + i] = idx[i];
     }
+}
+inline void pnp_sample_triples(uint32_t seed, int n, int n_trials, int32_t* idx, int32_t* triples) {
+    pnp_sample_tuples(seed, n, n_trials, 3, idx, triples);
 }
 
 enum Offer { kIgnored = 0, kNewBest = 1, kNewBestLocal = 2 };

@@ -33,6 +33,7 @@
 #include "ba_pack.h"
 #include "ba_plan.h"
 #include "ba_pnp.h"
+#include "ba_init.h"
 #include "ba_refine.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
@@ -3720,6 +3721,174 @@ int xrsfm_ba_absolute_pose(const xrsfm_ba_pose_options* opt, int32_t n_frames, c
                            int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
     return no_throw([&] { return absolute_pose_impl(opt, n_frames, corr_ptr, xy, points3d, frame_max_error, frame_seed, q, t, status, inlier_mask,
                                                     num_inliers, num_trials, best_trial); });
+}
+
+// ---------------------------------------------------------------- batched two-view initialisation (ba_init.h)
+void xrsfm_ba_two_view_options_default(xrsfm_ba_two_view_options* opt) {
+    if (!opt) return;
+    opt->confidence = 0.9;                    // essential.cc:393
+    opt->max_iterations = 50;
+    opt->seed = 0;
+    opt->min_matches = 10;                    // map_initializer.cc:30
+    opt->max_depth = 100.0;                   // essential.cc:424
+    opt->n_angles = 2;
+    opt->min_angle_rad[0] = 16.0 * 0.0174532925199432954743716805978692718781530857086181640625;      // DegToRad (util/math.h), :119
+    opt->min_angle_rad[1] = 8.0 * 0.0174532925199432954743716805978692718781530857086181640625;       // :132
+    opt->min_angle_rad[2] = opt->min_angle_rad[3] = 0.0;
+    opt->min_front_ratio = 0.5;               // :58
+    opt->min_angle_ratio = 0.5;
+    opt->min_num_valid = 200;                 // :59
+}
+
+int xrsfm_ba_debug_two_view_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t* quintuples) {
+    if (n < 5 || n > XRSFM_BA_INIT_MAX_MATCHES || n_trials < 0 || n_trials > XRSFM_BA_INIT_MAX_TRIALS || (n_trials > 0 && !quintuples)) return XRSFM_BA_EINVAL;
+    return no_throw([&] {
+        std::vector<int32_t> idx((size_t)n);
+        xinit::init_sample_quintuples(seed, n, n_trials, idx.data(), quintuples);
+        return XRSFM_BA_OK;
+    });
+}
+
+static int two_view_init_impl(const xrsfm_ba_two_view_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
+                              const double* pair_threshold, const uint32_t* pair_seed, uint8_t* status, double* E, double* q, double* t, double* points,
+                              uint8_t* essential_mask, uint8_t* front_mask, int32_t* counts, uint8_t* accepted, int32_t* num_trials, int32_t* best_trial) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_two_view_init: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_pairs < 0) return bad("negative count");
+    if (!std::isfinite(opt->confidence) || !std::isfinite(opt->max_depth) || !std::isfinite(opt->min_front_ratio) || !std::isfinite(opt->min_angle_ratio))
+        return bad("non-finite option");
+    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
+    if (opt->max_iterations < 1) return bad("max_iterations < 1");
+    if (opt->max_iterations > XRSFM_BA_INIT_MAX_TRIALS) return bad("max_iterations above XRSFM_BA_INIT_MAX_TRIALS");
+    if (opt->min_matches < 5) return bad("min_matches < 5");
+    if (opt->max_depth <= 0.0) return bad("max_depth <= 0");
+    if (opt->n_angles < 1 || opt->n_angles > 4) return bad("n_angles outside [1, 4]");
+    for (int a = 0; a < opt->n_angles; ++a) {
+        if (!std::isfinite(opt->min_angle_rad[a])) return bad("non-finite option");
+        if (opt->min_angle_rad[a] < 0.0) return bad("negative min_angle_rad");
+    }
+    if (opt->min_front_ratio < 0.0 || opt->min_angle_ratio < 0.0) return bad("negative min_front_ratio or min_angle_ratio");
+    if (opt->min_num_valid < 0) return bad("min_num_valid < 0");
+    if (n_pairs == 0) return XRSFM_BA_OK;
+    if (!status || !E || !q || !t || !points || !essential_mask || !front_mask || !counts) return bad("NULL status, E, q, t, points, essential_mask, front_mask or counts");
+    if (!match_ptr || !pair_threshold) return bad("NULL match_ptr or pair_threshold");
+    if (match_ptr[0] != 0) return bad("match_ptr does not start at 0");
+    for (int j = 0; j < n_pairs; ++j)
+        if (match_ptr[j + 1] < match_ptr[j]) return bad("match_ptr decreases");
+    const int Nm = match_ptr[n_pairs], Np = n_pairs;
+    if (Nm > 0 && (!xy_a || !xy_b)) return bad("NULL xy_a or xy_b");
+    for (size_t i = 0; i < 2 * (size_t)Nm; ++i) if (!std::isfinite(xy_a[i]) || !std::isfinite(xy_b[i])) return bad("non-finite coordinate");
+    for (int j = 0; j < Np; ++j) {
+        if (!std::isfinite(pair_threshold[j])) return bad("non-finite threshold");
+        if (pair_threshold[j] <= 0.0) return bad("threshold <= 0");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the two-view initialisation has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    InitParams prm;
+    prm.max_depth = opt->max_depth; prm.min_front_ratio = opt->min_front_ratio; prm.min_angle_ratio = opt->min_angle_ratio;
+    for (int a = 0; a < 4; ++a) prm.min_angle[a] = a < opt->n_angles ? opt->min_angle_rad[a] : 0.0;
+    prm.max_iterations = opt->max_iterations; prm.n_angles = opt->n_angles; prm.min_num_valid = opt->min_num_valid;
+    // per pair: the row of the trial bound (shared by the pairs of one n) and the sample quintuples (deviation 1)
+    std::vector<InitPair> pairs((size_t)Np);
+    std::vector<int32_t> rows, quint, idx;
+    std::map<int, int> row_of;
+    for (int j = 0; j < Np; ++j) {
+        InitPair& pr = pairs[(size_t)j];
+        pr.beg = match_ptr[j]; pr.n = match_ptr[j + 1] - match_ptr[j];
+        pr.th2 = 2.0 * pair_threshold[j] * pair_threshold[j];
+        pr.quint_off = -1; pr.row_off = 0; pr.pad = 0;
+        pr.skip_status = pr.n < opt->min_matches ? 2 : 3;
+        if (pr.n < opt->min_matches || pr.n > XRSFM_BA_INIT_MAX_MATCHES) continue;
+        auto it = row_of.find(pr.n);
+        if (it == row_of.end()) {
+            it = row_of.emplace(pr.n, (int)rows.size()).first;
+            rows.resize(rows.size() + (size_t)pr.n + 1);
+            xinit::init_bound_row(pr.n, opt->confidence, rows.data() + it->second);
+        }
+        pr.row_off = it->second;
+        pr.quint_off = (int32_t)(quint.size() / 5);
+        quint.resize(quint.size() + 5 * (size_t)prm.max_iterations);
+        idx.resize((size_t)pr.n);
+        xinit::init_sample_quintuples(pair_seed ? pair_seed[j] : opt->seed, pr.n, prm.max_iterations, idx.data(), quint.data() + 5 * (size_t)pr.quint_off);
+    }
+    HIPCHK(hipSetDevice(0));
+    static std::once_flag lds_once;
+    std::call_once(lds_once, [] { (void)hipFuncSetAttribute((const void*)k_init_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InitShared)); });
+    // one block from the allocation cache, one upload, one launch, one read-back (the layout of absolute_pose_impl)
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    const size_t o_pr = take(sizeof(InitPair) * (size_t)Np), o_m = take(sizeof(double) * 4 * (size_t)Nm), o_qt = take(sizeof(int32_t) * quint.size()),
+                 o_row = take(sizeof(int32_t) * rows.size());
+    const size_t in_bytes = off, out0 = off;
+    const size_t o_E = take(sizeof(double) * 9 * (size_t)Np), o_q = take(sizeof(double) * 4 * (size_t)Np), o_t = take(sizeof(double) * 3 * (size_t)Np),
+                 o_pts = take(sizeof(double) * 3 * (size_t)Nm), o_cnt = take(sizeof(int) * 8 * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
+                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_acc = take((size_t)Np), o_em = take((size_t)Nm), o_fm = take((size_t)Nm);
+    const size_t out_bytes = off - out0;
+    const size_t o_models = take(sizeof(double) * 9 * xinit::kMaxModels * xinit::kMaxTrials * (size_t)Np);       // device only
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    size_t cls = 0;
+    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
+    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    int e = 0;
+    {
+        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
+        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
+        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        memcpy(stage.data() + o_pr, pairs.data(), sizeof(InitPair) * (size_t)Np);
+        double* mm = (double*)(stage.data() + o_m);
+        for (size_t i = 0; i < (size_t)Nm; ++i) { mm[4 * i] = xy_a[2 * i]; mm[4 * i + 1] = xy_a[2 * i + 1]; mm[4 * i + 2] = xy_b[2 * i]; mm[4 * i + 3] = xy_b[2 * i + 1]; }
+        if (!quint.empty()) memcpy(stage.data() + o_qt, quint.data(), sizeof(int32_t) * quint.size());
+        if (!rows.empty()) memcpy(stage.data() + o_row, rows.data(), sizeof(int32_t) * rows.size());
+        hipStream_t st = hb.stream;
+        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            hipLaunchKernelGGL(k_init_pairs, dim3(Np), dim3(kInitThreads), sizeof(InitShared), st, (const InitPair*)(base + o_pr), Np, prm,
+                               (const double*)(base + o_m), (const int32_t*)(base + o_qt), (const int32_t*)(base + o_row), (double*)(base + o_models),
+                               (unsigned char*)(base + o_stat), (double*)(base + o_E), (double*)(base + o_q), (double*)(base + o_t), (double*)(base + o_pts),
+                               (unsigned char*)(base + o_em), (unsigned char*)(base + o_fm), (int*)(base + o_cnt), (unsigned char*)(base + o_acc),
+                               (int*)(base + o_ntr), (int*)(base + o_best));
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+        }
+        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
+            const double *Es = (const double*)(o + o_E), *qs = (const double*)(o + o_q), *ts = (const double*)(o + o_t), *ps = (const double*)(o + o_pts);
+            const unsigned char *stat = o + o_stat, *fm = o + o_fm;
+            const int* bt = (const int*)(o + o_best);
+            for (int j = 0; j < Np; ++j) {
+                status[j] = stat[j];
+                bool have_E = false;                                    // (the kernel hands back zeros when there is no E)
+                if (stat[j] <= 1) for (int k2 = 0; k2 < 9; ++k2) have_E = have_E || Es[9 * (size_t)j + k2] != 0.0;
+                if (have_E) for (int k2 = 0; k2 < 9; ++k2) E[9 * (size_t)j + k2] = Es[9 * (size_t)j + k2];
+                if (stat[j] != 1) continue;
+                for (int k2 = 0; k2 < 4; ++k2) q[4 * (size_t)j + k2] = qs[4 * (size_t)j + k2];
+                for (int k2 = 0; k2 < 3; ++k2) t[3 * (size_t)j + k2] = ts[3 * (size_t)j + k2];
+            }
+            for (size_t i = 0; i < (size_t)Nm; ++i)
+                if (fm[i]) for (int k2 = 0; k2 < 3; ++k2) points[3 * i + k2] = ps[3 * i + k2];
+            if (Nm) { memcpy(essential_mask, o + o_em, (size_t)Nm); memcpy(front_mask, fm, (size_t)Nm); }
+            memcpy(counts, o + o_cnt, sizeof(int) * 8 * (size_t)Np);
+            if (accepted) memcpy(accepted, o + o_acc, (size_t)Np);
+            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Np);
+            if (best_trial) memcpy(best_trial, bt, sizeof(int) * (size_t)Np);
+        }
+    }
+    g_cache.put(0, base, cls);
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int xrsfm_ba_two_view_init(const xrsfm_ba_two_view_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
+                           const double* pair_threshold, const uint32_t* pair_seed, uint8_t* status, double* E, double* q, double* t, double* points,
+                           uint8_t* essential_mask, uint8_t* front_mask, int32_t* counts, uint8_t* accepted, int32_t* num_trials, int32_t* best_trial) {
+    return no_throw([&] { return two_view_init_impl(opt, n_pairs, match_ptr, xy_a, xy_b, pair_threshold, pair_seed, status, E, q, t, points, essential_mask,
+                                                    front_mask, counts, accepted, num_trials, best_trial); });
 }
 
 // ---------------------------------------------------------------- diagnostics
