@@ -699,6 +699,74 @@ int xrsfm_ba_two_view_init(const xrsfm_ba_two_view_options *opt, int32_t n_pairs
 /* TEST ENTRY, no GPU: the sample quintuples of the first n_trials trials for n matches and one seed (deviation 1). */
 int xrsfm_ba_debug_two_view_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *quintuples /* [n_trials][5] */);
 
+/* Batched fundamental-matrix verification of matched image pairs: what FeatureMatching computes for every candidate pair, that is
+ * SolveFundamnetalCOLMAP -> colmap::LORANSAC<FundamentalMatrixSevenPointEstimator, FundamentalMatrixEightPointEstimator>
+ * (reference src/geometry/epipolar_geometry.hpp:10-27; src/feature/feature_processing.cc:256-296; run_triangulation.cc:91), for
+ * all pairs of a call in one launch: one workgroup per pair, FP64 throughout.  Its inlier masks are the matches that
+ * xrsfm_ba_two_view_init expects.  Restates LORANSAC::Estimate (optim/loransac.h:92-239) with InlierSupportMeasurer and
+ * ComputeSquaredSampsonError: 7-point sample models (up to three per trial), an 8-point model from the inliers of every new best
+ * with at least 8 inliers, the adaptive trial bound with exponent 7.
+ *
+ * The matches of pair p are match_ptr[p] .. match_ptr[p+1] in the caller's order.  xy_a, xy_b are PIXEL coordinates in the first
+ * and second image (frame.points; max_error is in pixels).
+ *
+ *   status[p]       0 no model (!report.success); 1 model found; 2 fewer than min_matches matches; 3 more than
+ *                   XRSFM_BA_FUND_MAX_MATCHES matches: not attempted, the call still succeeds
+ *   on status 1     F[p] row-major with x_b' F x_a = 0, scaled to unit Frobenius norm, the entry of largest magnitude positive
+ *                   (the reference returns the 7-point model with F(2,2) = 1 and the 8-point model at the scale and sign of its
+ *                   SVD); inlier_mask the reference's report.inlier_mask (residual <= max_error^2, from the model before that
+ *                   scaling); num_inliers[p] its sum; num_trials[p] report.num_trials; best_trial[p] the 0-based trial of the
+ *                   final best, plus bit 30 when the 8-point local model is the one returned; accepted[p] whether
+ *                   num_inliers >= max(min_num_inliers, (int)(min_accept_ratio n)) (feature_processing.cc:284-290)
+ *   on 0, 2, 3      F[p] untouched, the pair's mask entries 0, counts 0, best_trial -1, accepted 0
+ * On any negative return code no output is touched.  No output ever receives a NaN or an Inf: a non-finite sample or local model
+ * is discarded.  A pair's outputs are bit-identical whatever else is in the batch, in whatever order, and across calls.
+ *
+ * Documented deviations (defined meaning where the reference has no portable one):
+ *   1. Sampler.  That of xrsfm_ba_absolute_pose with seven draws: a fresh MT19937 per pair (init_genrand(seed), seed from
+ *      pair_seed or opt->seed), an index array that persists across the trials of the pair, seven Fisher-Yates steps per trial,
+ *      the same bounded draw (with a cap of 16 rejected words per draw, never reached, so that the device loop is bounded).
+ *      The septuples are drawn on the device.
+ *   2. Null space, roots and model order.  The null space of the 7 x 9 system is spanned by Q e7, Q e8 of the Householder QR of
+ *      its transpose (the reference takes two columns of an SVD; the models are the same, the cubic's variable is not).  The
+ *      cubic is solved by bisection for one real root, the closed form for the remaining quadratic and two Newton steps per
+ *      root; a complex pair is taken when |Im| <= 1e-10; leading zero coefficients lower the degree.  The models of one trial
+ *      are offered in ascending root on that basis.  The order decides ties and what is seen at the aborting trial.
+ *   3. 8-point model.  The null vector is the eigenvector of smallest eigenvalue of the 9 x 9 Gram matrix of the normalised
+ *      constraint rows (cyclic Jacobi); the rank-2 projection keeps the two largest terms of a one-sided Jacobi SVD of the 3 x 3
+ *      matrix and forms no third singular vector, so nothing depends on how a library signs one.
+ *   As for the pose, a model without a single inlier leaves the adaptive trial bound unbounded.
+ *
+ * Errors: XRSFM_BA_EINVAL (checked on the host before the device is touched, one line on stderr) — NULL opt; NULL status, F or
+ * inlier_mask with n_pairs > 0; a negative count; NULL match_ptr, or one not starting at 0 or decreasing; NULL xy_a or xy_b with
+ * matches; a non-finite coordinate, max_error or option; max_error <= 0 (option or per pair); confidence or min_inlier_ratio
+ * outside [0, 1]; min_num_trials < 0; max_num_trials < 1 or above XRSFM_BA_FUND_MAX_TRIALS; min_num_trials > max_num_trials;
+ * min_matches < 7; min_num_inliers < 0; min_accept_ratio < 0.  XRSFM_BA_ENODEV without a device (there is no CPU path);
+ * XRSFM_BA_ENOMEM when staging memory cannot be had.  n_pairs == 0 is success and needs no device. */
+typedef struct xrsfm_ba_fund_options {
+    double  max_error;         /* 4.0 pixels   epipolar_geometry.hpp:14 */
+    double  confidence;        /* 0.999        :17 */
+    double  min_inlier_ratio;  /* 0.25         :18; its constructor bound (113174 trials) is above max_num_trials */
+    int32_t min_num_trials;    /* 100          :16 */
+    int32_t max_num_trials;    /* 10000        :15; at most XRSFM_BA_FUND_MAX_TRIALS */
+    uint32_t seed;             /* 0 */
+    int32_t min_matches;       /* 15           feature_processing.cc:226; at least 7 */
+    int32_t min_num_inliers;   /* 15           :227 */
+    double  min_accept_ratio;  /* 0.25         :228 */
+} xrsfm_ba_fund_options;
+#define XRSFM_BA_FUND_MAX_MATCHES 8192
+#define XRSFM_BA_FUND_MAX_TRIALS  16384
+void xrsfm_ba_verify_pairs_options(xrsfm_ba_fund_options *opt);   /* the values above */
+int xrsfm_ba_verify_pairs(const xrsfm_ba_fund_options *opt, int32_t n_pairs, const int32_t *match_ptr /* [n_pairs+1] */,
+                          const double *xy_a /* [n][2] pixels, first image */, const double *xy_b /* [n][2] pixels, second image */,
+                          const double *pair_max_error /* [n_pairs] or NULL = opt->max_error */,
+                          const uint32_t *pair_seed /* [n_pairs] or NULL = opt->seed */, uint8_t *status /* [n_pairs] */,
+                          double *F /* [n_pairs][9] row-major */, uint8_t *inlier_mask /* [n] */,
+                          int32_t *num_inliers /* [n_pairs], may be NULL */, int32_t *num_trials /* [n_pairs], may be NULL */,
+                          int32_t *best_trial /* [n_pairs], may be NULL */, uint8_t *accepted /* [n_pairs], may be NULL */);
+/* TEST ENTRY, no GPU: the sample septuples of the first n_trials trials for n matches and one seed (deviation 1). */
+int xrsfm_ba_debug_fund_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *tuples /* [n_trials][7] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

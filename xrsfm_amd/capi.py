@@ -65,6 +65,12 @@ class CTwoViewOptions(C.Structure):
                 ("min_angle_ratio", C.c_double), ("min_num_valid", C.c_int32)]
 
 
+class CFundOptions(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("confidence", C.c_double), ("min_inlier_ratio", C.c_double),
+                ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32), ("seed", C.c_uint32), ("min_matches", C.c_int32),
+                ("min_num_inliers", C.c_int32), ("min_accept_ratio", C.c_double)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -111,6 +117,7 @@ EXPORTS = [
     "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars",
     "xrsfm_ba_absolute_pose_options", "xrsfm_ba_absolute_pose", "xrsfm_ba_debug_pose_samples",
     "xrsfm_ba_two_view_options_default", "xrsfm_ba_two_view_init", "xrsfm_ba_debug_two_view_samples",
+    "xrsfm_ba_verify_pairs_options", "xrsfm_ba_verify_pairs", "xrsfm_ba_debug_fund_samples",
 ]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
@@ -140,6 +147,9 @@ POSE_LOCAL_BIT = 1 << 30  # best_trial: the locally optimised (EPnP) model of th
 INIT_MAX_MATCHES = 8192  # XRSFM_BA_INIT_MAX_MATCHES: most matches of a pair xrsfm_ba_two_view_init attempts
 INIT_MAX_TRIALS = 64     # XRSFM_BA_INIT_MAX_TRIALS
 INIT_SLOT_STRIDE = 16    # best_trial of xrsfm_ba_two_view_init: trial * 16 + model slot
+FUND_MAX_MATCHES = 8192  # XRSFM_BA_FUND_MAX_MATCHES: most matches of a pair xrsfm_ba_verify_pairs attempts
+FUND_MAX_TRIALS = 16384  # XRSFM_BA_FUND_MAX_TRIALS
+FUND_LOCAL_BIT = 1 << 30  # best_trial: the 8-point local model of that trial is the one returned
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -255,6 +265,14 @@ def load(path: str | None = None):
     lib.xrsfm_ba_two_view_init.restype = C.c_int
     lib.xrsfm_ba_debug_two_view_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
     lib.xrsfm_ba_debug_two_view_samples.restype = C.c_int
+    lib.xrsfm_ba_verify_pairs_options.argtypes = [C.POINTER(CFundOptions)]
+    lib.xrsfm_ba_verify_pairs_options.restype = None
+    lib.xrsfm_ba_verify_pairs.argtypes = [C.POINTER(CFundOptions), C.c_int32, _c_int32_p, _c_double_p, _c_double_p, _c_double_p,
+                                           C.POINTER(C.c_uint32), _c_uint8_p, _c_double_p, _c_uint8_p, _c_int32_p, _c_int32_p, _c_int32_p,
+                                           _c_uint8_p]
+    lib.xrsfm_ba_verify_pairs.restype = C.c_int
+    lib.xrsfm_ba_debug_fund_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
+    lib.xrsfm_ba_debug_fund_samples.restype = C.c_int
     _lib = lib
     return lib
 
@@ -830,6 +848,73 @@ def debug_two_view_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
     """xrsfm_ba_debug_two_view_samples: the sample quintuples [n_trials][5] of a pair of n matches (no GPU)."""
     out = np.zeros((n_trials, 5), np.int32)
     check(load().xrsfm_ba_debug_two_view_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_two_view_samples")
+    return out
+
+
+def verify_pairs_options(**overrides) -> CFundOptions:
+    """xrsfm_ba_verify_pairs_options: the settings of the reference's SolveFundamnetalCOLMAP and FeatureMatching."""
+    o = CFundOptions()
+    load().xrsfm_ba_verify_pairs_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def verify_pairs(match_ptr, xy_a, xy_b, options: CFundOptions | None = None, pair_max_error=None, pair_seed=None) -> dict:
+    """xrsfm_ba_verify_pairs: one 7-point / 8-point LO-RANSAC per matched pair (matches match_ptr[p] .. match_ptr[p+1]: PIXEL
+    coordinates in the first and second image).  F of pairs whose status is not 1 stays 0 here (the C call leaves it untouched)."""
+    o = options if options is not None else verify_pairs_options()
+    match_ptr = np.ascontiguousarray(match_ptr, np.int32)
+    xy_a = np.ascontiguousarray(xy_a, np.float64).reshape(-1, 2); xy_b = np.ascontiguousarray(xy_b, np.float64).reshape(-1, 2)
+    if match_ptr.ndim != 1 or len(match_ptr) < 1 or len(xy_a) != len(xy_b):
+        raise ValueError("verify_pairs: inconsistent array shapes")
+    npair, n = len(match_ptr) - 1, len(xy_a)
+    if npair > 0 and match_ptr[-1] != n:
+        raise ValueError("verify_pairs: match_ptr[-1] must be the number of matches")
+    pme = psd = None
+    if pair_max_error is not None:
+        pme = np.ascontiguousarray(pair_max_error, np.float64)
+        if pme.shape != (npair,):
+            raise ValueError("verify_pairs: pair_max_error must have one entry per pair")
+    if pair_seed is not None:
+        psd = np.ascontiguousarray(pair_seed, np.uint32)
+        if psd.shape != (npair,):
+            raise ValueError("verify_pairs: pair_seed must have one entry per pair")
+    r = dict(status=np.zeros(npair, np.uint8), F=np.zeros((npair, 9)), inlier_mask=np.zeros(n, np.uint8), num_inliers=np.zeros(npair, np.int32),
+             num_trials=np.zeros(npair, np.int32), best_trial=np.full(npair, -1, np.int32), accepted=np.zeros(npair, np.uint8))
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    up = lambda a: a.ctypes.data_as(_c_uint8_p)
+    check(load().xrsfm_ba_verify_pairs(C.byref(o), npair, ip(match_ptr), _dp(xy_a), _dp(xy_b), _dp(pme) if pme is not None else None,
+                                       psd.ctypes.data_as(C.POINTER(C.c_uint32)) if psd is not None else None, up(r["status"]), _dp(r["F"]),
+                                       up(r["inlier_mask"]), ip(r["num_inliers"]), ip(r["num_trials"]), ip(r["best_trial"]), up(r["accepted"])),
+          "xrsfm_ba_verify_pairs")
+    return r
+
+
+def verified_matches(result: dict, match_ptr, matches) -> tuple:
+    """FeatureMatching after the verification (feature_processing.cc:291-305): the pairs with accepted != 0 keep their inlier
+    matches (ExtractInlierMatches), every other pair is dropped.  `matches` has one row per match (any columns: feature indices,
+    coordinates).  Returns (kept pair indices, the kept rows, their match_ptr): what two_view_init takes."""
+    match_ptr = np.asarray(match_ptr, np.int64)
+    matches = np.asarray(matches)
+    mask = np.asarray(result["inlier_mask"], bool)
+    if len(matches) != len(mask) or len(match_ptr) != len(result["accepted"]) + 1:
+        raise ValueError("verified_matches: inconsistent array shapes")
+    kept = np.flatnonzero(np.asarray(result["accepted"]) != 0)
+    rows = [np.arange(match_ptr[p], match_ptr[p + 1])[mask[match_ptr[p]:match_ptr[p + 1]]] for p in kept]
+    new_ptr = np.zeros(len(kept) + 1, np.int32)
+    if len(kept):
+        new_ptr[1:] = np.cumsum([len(r) for r in rows])
+    sel = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    return kept, matches[sel], new_ptr
+
+
+def debug_fund_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
+    """xrsfm_ba_debug_fund_samples: the sample septuples [n_trials][7] of a pair of n matches (no GPU)."""
+    out = np.zeros((n_trials, 7), np.int32)
+    check(load().xrsfm_ba_debug_fund_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_fund_samples")
     return out
 
 

@@ -34,6 +34,7 @@
 #include "ba_plan.h"
 #include "ba_pnp.h"
 #include "ba_init.h"
+#include "ba_fund.h"
 #include "ba_refine.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
@@ -3889,6 +3890,157 @@ int xrsfm_ba_two_view_init(const xrsfm_ba_two_view_options* opt, int32_t n_pairs
                            uint8_t* essential_mask, uint8_t* front_mask, int32_t* counts, uint8_t* accepted, int32_t* num_trials, int32_t* best_trial) {
     return no_throw([&] { return two_view_init_impl(opt, n_pairs, match_ptr, xy_a, xy_b, pair_threshold, pair_seed, status, E, q, t, points, essential_mask,
                                                     front_mask, counts, accepted, num_trials, best_trial); });
+}
+
+// ---------------------------------------------------------------- batched fundamental-matrix verification of pairs (ba_fund.h)
+void xrsfm_ba_verify_pairs_options(xrsfm_ba_fund_options* opt) {
+    if (!opt) return;
+    opt->max_error = 4.0;                     // epipolar_geometry.hpp:14
+    opt->confidence = 0.999;                  // :17
+    opt->min_inlier_ratio = 0.25;             // :18
+    opt->min_num_trials = 100;                // :16
+    opt->max_num_trials = 10000;              // :15
+    opt->seed = 0;
+    opt->min_matches = 15;                    // feature_processing.cc:226
+    opt->min_num_inliers = 15;                // :227
+    opt->min_accept_ratio = 0.25;             // :228
+}
+
+int xrsfm_ba_debug_fund_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t* tuples) {
+    if (n < xfund::kSample || n > XRSFM_BA_FUND_MAX_MATCHES || n_trials < 0 || n_trials > XRSFM_BA_FUND_MAX_TRIALS || (n_trials > 0 && !tuples))
+        return XRSFM_BA_EINVAL;
+    return no_throw([&] {
+        std::vector<int32_t> idx((size_t)n);
+        std::vector<uint32_t> mt(624);
+        xfund::fund_sample_tuples(seed, n, n_trials, mt.data(), idx.data(), tuples);
+        return XRSFM_BA_OK;
+    });
+}
+
+static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
+                             const double* pair_max_error, const uint32_t* pair_seed, uint8_t* status, double* F, uint8_t* inlier_mask,
+                             int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_verify_pairs: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_pairs < 0) return bad("negative count");
+    if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio) || !std::isfinite(opt->min_accept_ratio))
+        return bad("non-finite option");
+    if (opt->max_error <= 0.0) return bad("max_error <= 0");
+    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
+    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
+    if (opt->min_num_trials < 0) return bad("min_num_trials < 0");
+    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
+    if (opt->max_num_trials > XRSFM_BA_FUND_MAX_TRIALS) return bad("max_num_trials above XRSFM_BA_FUND_MAX_TRIALS");
+    if (opt->min_num_trials > opt->max_num_trials) return bad("min_num_trials > max_num_trials");
+    if (opt->min_matches < xfund::kSample) return bad("min_matches < 7");
+    if (opt->min_num_inliers < 0) return bad("min_num_inliers < 0");
+    if (opt->min_accept_ratio < 0.0) return bad("min_accept_ratio < 0");
+    if (n_pairs == 0) return XRSFM_BA_OK;
+    if (!status || !F || !inlier_mask) return bad("NULL status, F or inlier_mask");
+    if (!match_ptr) return bad("NULL match_ptr");
+    if (match_ptr[0] != 0) return bad("match_ptr does not start at 0");
+    for (int j = 0; j < n_pairs; ++j)
+        if (match_ptr[j + 1] < match_ptr[j]) return bad("match_ptr decreases");
+    const int Nm = match_ptr[n_pairs], Np = n_pairs;
+    if (Nm > 0 && (!xy_a || !xy_b)) return bad("NULL xy_a or xy_b");
+    for (size_t i = 0; i < 2 * (size_t)Nm; ++i) if (!std::isfinite(xy_a[i]) || !std::isfinite(xy_b[i])) return bad("non-finite coordinate");
+    if (pair_max_error)
+        for (int j = 0; j < Np; ++j) {
+            if (!std::isfinite(pair_max_error[j])) return bad("non-finite max_error");
+            if (pair_max_error[j] <= 0.0) return bad("max_error <= 0");
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the pair verification has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    FundParams prm;
+    prm.trial_cap = std::min(opt->max_num_trials, xfund::fund_ratio_trials(opt->min_inlier_ratio, opt->confidence));
+    prm.min_trials = opt->min_num_trials;
+    // per pair: the row dyn(k, n), shared by the pairs of one n; the septuples are drawn on the device
+    std::vector<FundPair> pairs((size_t)Np);
+    std::vector<int32_t> dyn;
+    std::map<int, int> dyn_of;
+    for (int j = 0; j < Np; ++j) {
+        FundPair& pr = pairs[(size_t)j];
+        pr.beg = match_ptr[j]; pr.n = match_ptr[j + 1] - match_ptr[j];
+        const double me = pair_max_error ? pair_max_error[j] : opt->max_error;
+        pr.max_residual = me * me; pr.dyn_off = 0; pr.pad = 0;
+        pr.seed = pair_seed ? pair_seed[j] : opt->seed;
+        pr.skip_status = pr.n < opt->min_matches ? 2 : (pr.n > XRSFM_BA_FUND_MAX_MATCHES ? 3 : 0);
+        if (pr.skip_status) continue;
+        auto it = dyn_of.find(pr.n);
+        if (it == dyn_of.end()) {
+            it = dyn_of.emplace(pr.n, (int)dyn.size()).first;
+            for (int k = 0; k <= pr.n; ++k) dyn.push_back(xfund::fund_dyn_trials(k, pr.n, opt->confidence));
+        }
+        pr.dyn_off = it->second;
+    }
+    HIPCHK(hipSetDevice(0));
+    static std::once_flag lds_once;
+    std::call_once(lds_once, [] { (void)hipFuncSetAttribute((const void*)k_verify_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FundShared)); });
+    // one block from the allocation cache, one upload, one launch, one read-back (the layout of absolute_pose_impl)
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    const size_t o_pr = take(sizeof(FundPair) * (size_t)Np), o_m = take(sizeof(double) * 4 * (size_t)Nm), o_dyn = take(sizeof(int32_t) * dyn.size());
+    const size_t in_bytes = off, out0 = off;
+    const size_t o_F = take(sizeof(double) * 9 * (size_t)Np), o_ninl = take(sizeof(int) * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
+                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_mask = take((size_t)Nm);
+    const size_t out_bytes = off - out0;
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    size_t cls = 0;
+    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
+    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    int e = 0;
+    {
+        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
+        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
+        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        memcpy(stage.data() + o_pr, pairs.data(), sizeof(FundPair) * (size_t)Np);
+        double* mm = (double*)(stage.data() + o_m);
+        for (size_t i = 0; i < (size_t)Nm; ++i) { mm[4 * i] = xy_a[2 * i]; mm[4 * i + 1] = xy_a[2 * i + 1]; mm[4 * i + 2] = xy_b[2 * i]; mm[4 * i + 3] = xy_b[2 * i + 1]; }
+        if (!dyn.empty()) memcpy(stage.data() + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
+        hipStream_t st = hb.stream;
+        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            hipLaunchKernelGGL(k_verify_pairs, dim3(Np), dim3(kFundThreads), sizeof(FundShared), st, (const FundPair*)(base + o_pr), Np, prm,
+                               (const double*)(base + o_m), (const int32_t*)(base + o_dyn), (double*)(base + o_F), (unsigned char*)(base + o_stat),
+                               (unsigned char*)(base + o_mask), (int*)(base + o_ninl), (int*)(base + o_ntr), (int*)(base + o_best));
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+        }
+        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
+            const double* Fs = (const double*)(o + o_F);
+            const unsigned char* stat = o + o_stat;
+            const int* ninl = (const int*)(o + o_ninl);
+            for (int j = 0; j < Np; ++j) {
+                status[j] = stat[j];
+                if (stat[j] == 1) for (int k2 = 0; k2 < 9; ++k2) F[9 * (size_t)j + k2] = Fs[9 * (size_t)j + k2];
+                if (accepted) {                                        // feature_processing.cc:284-290
+                    const int thr = std::max(opt->min_num_inliers, (int)(opt->min_accept_ratio * (double)pairs[(size_t)j].n));
+                    accepted[j] = (stat[j] == 1 && ninl[j] >= thr) ? 1 : 0;
+                }
+            }
+            if (Nm) memcpy(inlier_mask, o + o_mask, (size_t)Nm);
+            if (num_inliers) memcpy(num_inliers, ninl, sizeof(int) * (size_t)Np);
+            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Np);
+            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Np);
+        }
+    }
+    g_cache.put(0, base, cls);
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int xrsfm_ba_verify_pairs(const xrsfm_ba_fund_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
+                          const double* pair_max_error, const uint32_t* pair_seed, uint8_t* status, double* F, uint8_t* inlier_mask,
+                          int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
+    return no_throw([&] { return verify_pairs_impl(opt, n_pairs, match_ptr, xy_a, xy_b, pair_max_error, pair_seed, status, F, inlier_mask, num_inliers,
+                                                   num_trials, best_trial, accepted); });
 }
 
 // ---------------------------------------------------------------- diagnostics
