@@ -767,6 +767,67 @@ int xrsfm_ba_verify_pairs(const xrsfm_ba_fund_options *opt, int32_t n_pairs, con
 /* TEST ENTRY, no GPU: the sample septuples of the first n_trials trials for n matches and one seed (deviation 1). */
 int xrsfm_ba_debug_fund_samples(uint32_t seed, int32_t n, int32_t n_trials, int32_t *tuples /* [n_trials][7] */);
 
+/* Batched SIFT descriptor matching: what FeatureMatching computes for every candidate pair before the verification above, that is
+ * SiftMatchGPU::GetSiftMatch (reference src/feature/feature_processing.cc:118-154, 240-255; the kernels MultiplyDescriptor_Kernel,
+ * RowMatch_Kernel and ColMatch_Kernel of 3rdparty/SiftGPU/ProgramCU.cu:1491-1884 and the host loop of SiftMatchCU::GetBestMatch,
+ * SiftMatchCU.cpp:186-215), for all pairs of a call, with the 128-byte products on the int8 matrix cores.  Every output is an
+ * integer and is exactly defined:
+ *
+ *   dot(i, j)       sum_k a[i][k] b[j][k] over the 128 uint8 components: at most 8 323 200
+ *   (best, idx, next) of a row over all columns, and of a column over all rows, from (0, -1, 0): best = max(0, max dot), next the
+ *                   second largest value counted with multiplicity and floored at 0, idx the lowest position holding best, -1 when
+ *                   no dot is positive (ProgramCU.cu:1804-1826, 1861-1863)
+ *   dist(d)         (float) acos(min((double) ((float) d * 2^-18f), 1.0)) (:1830), from a table over d = 0 .. 2^18
+ *   row_match[i]    idx when dist(best) < max_distance && dist(best) < dist(next) * max_ratio (all float, :1833), else -1;
+ *                   col_match[j] likewise
+ *   matches         (i, row_match[i]) in ascending i where row_match[i] >= 0 and, with mutual_best, col_match[row_match[i]] == i
+ *                   (SiftMatchCU.cpp:199-213)
+ *
+ * Frame f holds the descriptors desc_ptr[f] .. desc_ptr[f+1]; only its first max_features take part (SetDescriptors:113-114).  Pair
+ * p matches frame pair_a[p] (rows, i) against pair_b[p] (columns, j); a pair may name one frame twice; a frame without descriptors
+ * gives its pairs no matches.  The matches of pair p are rows match_ptr[p] .. match_ptr[p+1] of `matches`: as int32, the
+ * match_ptr that xrsfm_ba_verify_pairs takes.  A capacity of sum_p min(n_a(p), max_features) always suffices.  num_row[p] / num_col[p]: the rows /
+ * columns that pass their own test.  On any negative return code no output is touched.  A pair's outputs are bit-identical whatever
+ * else is in the batch, in whatever order, and across calls.
+ *
+ * Documented deviations:
+ *   1. The distance table is built on the host with its acos, once per process (the reference calls the device's acos per row).
+ *      No transcendental runs on the device and none sits in a decision.
+ *   2. Of several positions holding the best, idx is the lowest (the reference's depends on its 32-lane walk).  With max_ratio <= 1
+ *      a tied best always fails dist < dist_next * max_ratio, so the index of a tied best is never returned in a match; a
+ *      max_ratio outside (0, 1] is refused.
+ *   3. All pairs of a call go in one submission and every frame is prepared once (the reference uploads both descriptor sets for
+ *      every pair).  The call is split into several launches when its workspace would exceed 1 GiB (environment
+ *      XRSFM_BA_MATCH_WORKSPACE_MB: another bound); the results do not depend on the split.
+ *   The reference's cap on the number of matches (max_match = 16384 = the most rows) never binds and is not restated.
+ *
+ * Errors: XRSFM_BA_EINVAL (checked on the host before the device is touched, one line on stderr) — NULL opt; a negative count;
+ * non-finite or non-positive max_distance; max_ratio outside (0, 1]; max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES; with
+ * n_pairs > 0: NULL match_ptr, pair_a, pair_b or desc_ptr, a desc_ptr that does not start at 0 or decreases, NULL desc with
+ * descriptors, NULL matches with a capacity, a frame index out of range.  XRSFM_BA_EINVAL after the computation, with one line on
+ * stderr that names the needed size, when the matches do not fit matches_capacity.  XRSFM_BA_ENODEV without a device (there is no
+ * CPU path); XRSFM_BA_ENOMEM when descriptors plus workspace cannot be had.  n_pairs == 0 is success and needs no device. */
+typedef struct xrsfm_ba_match_options {
+    float   max_distance;   /* 0.7    feature_processing.cc:122 */
+    float   max_ratio;      /* 0.8    :123; in (0, 1] */
+    int32_t mutual_best;    /* 1      :146 */
+    int32_t max_features;   /* 16384  :23; 1 .. XRSFM_BA_MATCH_MAX_FEATURES */
+} xrsfm_ba_match_options;
+#define XRSFM_BA_MATCH_MAX_FEATURES 16384
+#define XRSFM_BA_MATCH_DIM 128
+void xrsfm_ba_match_options_default(xrsfm_ba_match_options *opt);   /* the values above */
+int xrsfm_ba_match_descriptors(const xrsfm_ba_match_options *opt, int32_t n_frames, const int64_t *desc_ptr /* [n_frames+1] */,
+                               const uint8_t *desc /* [n][128] */, int32_t n_pairs, const int32_t *pair_a,
+                               const int32_t *pair_b /* [n_pairs] frame indices */, int64_t matches_capacity,
+                               int64_t *match_ptr /* [n_pairs+1] */, int32_t *matches /* [capacity][2]: (i, j) */,
+                               int32_t *num_row /* [n_pairs], may be NULL */, int32_t *num_col /* [n_pairs], may be NULL */);
+/* TEST ENTRY, no GPU: dist(0 .. 2^18), the table of the test. */
+int xrsfm_ba_debug_match_table(float *table /* [262145] */);
+/* TEST ENTRY: one pair through the kernels of xrsfm_ba_match_descriptors; the triples (best, idx, next) of its rows and columns.
+ * n_a, n_b in 0 .. XRSFM_BA_MATCH_MAX_FEATURES. */
+int xrsfm_ba_debug_match_top2(int32_t n_a, const uint8_t *desc_a, int32_t n_b, const uint8_t *desc_b,
+                              int32_t *row_top /* [n_a][3] */, int32_t *col_top /* [n_b][3] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

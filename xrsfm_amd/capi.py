@@ -71,6 +71,10 @@ class CFundOptions(C.Structure):
                 ("min_num_inliers", C.c_int32), ("min_accept_ratio", C.c_double)]
 
 
+class CMatchOptions(C.Structure):
+    _fields_ = [("max_distance", C.c_float), ("max_ratio", C.c_float), ("mutual_best", C.c_int32), ("max_features", C.c_int32)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -118,7 +122,10 @@ EXPORTS = [
     "xrsfm_ba_absolute_pose_options", "xrsfm_ba_absolute_pose", "xrsfm_ba_debug_pose_samples",
     "xrsfm_ba_two_view_options_default", "xrsfm_ba_two_view_init", "xrsfm_ba_debug_two_view_samples",
     "xrsfm_ba_verify_pairs_options", "xrsfm_ba_verify_pairs", "xrsfm_ba_debug_fund_samples",
+    "xrsfm_ba_match_options_default", "xrsfm_ba_match_descriptors", "xrsfm_ba_debug_match_table",
 ]
+# declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
+EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
 
 # xrsfm_ba_debug_reduced_system / debug_chol_plan: the schedule facts, in order (include/xrsfm_ba.h)
 CHOL_FACTS = ("T", "levels", "ordering", "schedule", "macro_levels", "split_levels", "la_depth", "fill_rest", "rest_apart", "packed",
@@ -150,6 +157,9 @@ INIT_SLOT_STRIDE = 16    # best_trial of xrsfm_ba_two_view_init: trial * 16 + mo
 FUND_MAX_MATCHES = 8192  # XRSFM_BA_FUND_MAX_MATCHES: most matches of a pair xrsfm_ba_verify_pairs attempts
 FUND_MAX_TRIALS = 16384  # XRSFM_BA_FUND_MAX_TRIALS
 FUND_LOCAL_BIT = 1 << 30  # best_trial: the 8-point local model of that trial is the one returned
+MATCH_MAX_FEATURES = 16384  # XRSFM_BA_MATCH_MAX_FEATURES: most descriptors of a frame xrsfm_ba_match_descriptors takes
+MATCH_DIM = 128          # XRSFM_BA_MATCH_DIM
+MATCH_TABLE_SIZE = (1 << 18) + 1  # entries of xrsfm_ba_debug_match_table
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -273,6 +283,15 @@ def load(path: str | None = None):
     lib.xrsfm_ba_verify_pairs.restype = C.c_int
     lib.xrsfm_ba_debug_fund_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, _c_int32_p]
     lib.xrsfm_ba_debug_fund_samples.restype = C.c_int
+    lib.xrsfm_ba_match_options_default.argtypes = [C.POINTER(CMatchOptions)]
+    lib.xrsfm_ba_match_options_default.restype = None
+    lib.xrsfm_ba_match_descriptors.argtypes = [C.POINTER(CMatchOptions), C.c_int32, C.POINTER(C.c_int64), _c_uint8_p, C.c_int32, _c_int32_p, _c_int32_p,
+                                                C.c_int64, C.POINTER(C.c_int64), _c_int32_p, _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_match_descriptors.restype = C.c_int
+    lib.xrsfm_ba_debug_match_table.argtypes = [C.POINTER(C.c_float)]
+    lib.xrsfm_ba_debug_match_table.restype = C.c_int
+    lib.xrsfm_ba_debug_match_top2.argtypes = [C.c_int32, _c_uint8_p, C.c_int32, _c_uint8_p, _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_debug_match_top2.restype = C.c_int
     _lib = lib
     return lib
 
@@ -916,6 +935,88 @@ def debug_fund_samples(seed: int, n: int, n_trials: int) -> np.ndarray:
     out = np.zeros((n_trials, 7), np.int32)
     check(load().xrsfm_ba_debug_fund_samples(int(seed), int(n), int(n_trials), out.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_fund_samples")
     return out
+
+
+def match_options(**overrides) -> CMatchOptions:
+    """xrsfm_ba_match_options_default: the settings of the reference's FeatureMatching."""
+    o = CMatchOptions()
+    load().xrsfm_ba_match_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def _desc2d(desc) -> np.ndarray:
+    d = np.ascontiguousarray(desc, np.uint8)
+    return d.reshape(d.size // MATCH_DIM if d.size % MATCH_DIM == 0 else -1, MATCH_DIM)
+
+
+def match_descriptors(desc_ptr, desc, pair_a, pair_b, options: CMatchOptions | None = None) -> dict:
+    """xrsfm_ba_match_descriptors: the SIFT matches of every pair (frame pair_a[p] against frame pair_b[p]; the descriptors of frame f
+    are rows desc_ptr[f] .. desc_ptr[f+1] of the uint8 array desc [n][128]).  Returns match_ptr [n_pairs+1] (int64), matches
+    [match_ptr[-1]][2] (feature index in a, in b), num_row and num_col [n_pairs]."""
+    o = options if options is not None else match_options()
+    desc_ptr = np.ascontiguousarray(desc_ptr, np.int64)
+    desc = _desc2d(desc)
+    pair_a = np.ascontiguousarray(pair_a, np.int32); pair_b = np.ascontiguousarray(pair_b, np.int32)
+    if desc_ptr.ndim != 1 or len(desc_ptr) < 1 or pair_a.ndim != 1 or pair_a.shape != pair_b.shape:
+        raise ValueError("match_descriptors: inconsistent array shapes")
+    if desc_ptr[-1] != len(desc):
+        raise ValueError("match_descriptors: desc_ptr[-1] must be the number of descriptors")
+    nf, npair = len(desc_ptr) - 1, len(pair_a)
+    n = np.minimum(np.diff(desc_ptr), max(int(o.max_features), 0))
+    ok = npair > 0 and nf > 0 and pair_a.min() >= 0 and pair_a.max() < nf
+    cap = int(n[pair_a].sum()) if ok else 0                  # (an index out of range is the library's to refuse)
+    mp = np.zeros(npair + 1, np.int64); m = np.zeros((cap, 2), np.int32)
+    r = dict(num_row=np.zeros(npair, np.int32), num_col=np.zeros(npair, np.int32))
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    check(load().xrsfm_ba_match_descriptors(C.byref(o), nf, lp(desc_ptr), desc.ctypes.data_as(_c_uint8_p), npair, ip(pair_a), ip(pair_b), cap, lp(mp), ip(m),
+                                            ip(r["num_row"]), ip(r["num_col"])), "xrsfm_ba_match_descriptors")
+    r["match_ptr"] = mp
+    r["matches"] = m[:int(mp[-1])].copy()
+    return r
+
+
+def matched_points(result: dict, kp_ptr, keypoints_xy, pair_a, pair_b) -> tuple:
+    """The coordinates of the matches of match_descriptors: keypoints_xy [n][2] holds the keypoints of frame f at rows kp_ptr[f] ..
+    kp_ptr[f+1], in the order of its descriptors.  Returns (xy_a, xy_b), one row per match: what verify_pairs takes together with
+    result["match_ptr"]."""
+    kp_ptr = np.asarray(kp_ptr, np.int64)
+    xy = np.ascontiguousarray(keypoints_xy, np.float64).reshape(-1, 2)
+    mp, m = np.asarray(result["match_ptr"], np.int64), np.asarray(result["matches"], np.int64).reshape(-1, 2)
+    pair_a, pair_b = np.asarray(pair_a, np.int64), np.asarray(pair_b, np.int64)
+    if len(mp) != len(pair_a) + 1 or len(pair_a) != len(pair_b) or (len(mp) and mp[-1] != len(m)):
+        raise ValueError("matched_points: inconsistent array shapes")
+    per = np.diff(mp)
+    return xy[np.repeat(kp_ptr[pair_a], per) + m[:, 0]], xy[np.repeat(kp_ptr[pair_b], per) + m[:, 1]]
+
+
+def quantize_descriptors(float_desc) -> np.ndarray:
+    """SetDescriptors(float) of the reference (SiftMatchCU.cpp:131-135): unit-norm float descriptors to uint8 by int(512 d + 0.5).
+    The reference stores the int into an unsigned char; values that do not fit are refused here."""
+    q = (512.0 * np.asarray(float_desc, np.float32) + np.float32(0.5)).astype(np.int32)
+    if q.size and (q.min() < 0 or q.max() > 255):
+        raise ValueError("quantize_descriptors: a component outside [0, 255 / 512]")
+    return q.astype(np.uint8)
+
+
+def debug_match_table() -> np.ndarray:
+    """xrsfm_ba_debug_match_table: dist(0 .. 2^18) as the library builds it (no GPU)."""
+    out = np.zeros(MATCH_TABLE_SIZE, np.float32)
+    check(load().xrsfm_ba_debug_match_table(out.ctypes.data_as(C.POINTER(C.c_float))), "xrsfm_ba_debug_match_table")
+    return out
+
+
+def debug_match_top2(desc_a, desc_b) -> tuple:
+    """xrsfm_ba_debug_match_top2: (row_top [n_a][3], col_top [n_b][3]), the triples (best, idx, next) of one pair."""
+    a, b = _desc2d(desc_a), _desc2d(desc_b)
+    rt, ct = np.zeros((len(a), 3), np.int32), np.zeros((len(b), 3), np.int32)
+    check(load().xrsfm_ba_debug_match_top2(len(a), a.ctypes.data_as(_c_uint8_p), len(b), b.ctypes.data_as(_c_uint8_p), rt.ctypes.data_as(_c_int32_p),
+                                           ct.ctypes.data_as(_c_int32_p)), "xrsfm_ba_debug_match_top2")
+    return rt, ct
 
 
 def debug_pack(problem: ProblemArrays) -> dict:

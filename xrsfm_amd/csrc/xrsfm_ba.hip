@@ -35,6 +35,7 @@
 #include "ba_pnp.h"
 #include "ba_init.h"
 #include "ba_fund.h"
+#include "ba_match.h"
 #include "ba_refine.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
@@ -4041,6 +4042,276 @@ int xrsfm_ba_verify_pairs(const xrsfm_ba_fund_options* opt, int32_t n_pairs, con
                           int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
     return no_throw([&] { return verify_pairs_impl(opt, n_pairs, match_ptr, xy_a, xy_b, pair_max_error, pair_seed, status, F, inlier_mask, num_inliers,
                                                    num_trials, best_trial, accepted); });
+}
+
+// ---------------------------------------------------------------- batched SIFT descriptor matching (ba_match.h)
+void xrsfm_ba_match_options_default(xrsfm_ba_match_options* opt) {
+    if (!opt) return;
+    opt->max_distance = 0.7f;                 // feature_processing.cc:122
+    opt->max_ratio = 0.8f;                    // :123
+    opt->mutual_best = 1;                     // :146
+    opt->max_features = 16384;                // :23
+}
+
+int xrsfm_ba_debug_match_table(float* table) {
+    if (!table) return XRSFM_BA_EINVAL;
+    xmatch::match_build_table(table);
+    return XRSFM_BA_OK;
+}
+
+namespace {
+// dist(0 .. 2^18): built once per process, uploaded once per device (device 0: the batched entries run there)
+const float* match_table_host() {
+    static std::vector<float> tab;
+    static std::once_flag once;
+    std::call_once(once, [] { tab.resize(xmatch::kTabSize); xmatch::match_build_table(tab.data()); });
+    return tab.data();
+}
+const float* match_table_device() {
+    static float* dev = nullptr;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> g(mu);
+    if (!dev) {
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, sizeof(float) * xmatch::kTabSize) != hipSuccess) return nullptr;
+        if (hipMemcpy(p, match_table_host(), sizeof(float) * xmatch::kTabSize, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return nullptr; }
+        dev = p;
+    }
+    return dev;
+}
+
+struct MatchResult {                          // of the whole call, held back until nothing can fail any more
+    std::vector<int32_t> count, num_row, num_col;       // [n_pairs]
+    std::vector<std::vector<int32_t>> rows;             // per pair: its matches (i, j)
+    std::vector<int32_t> row_top, col_top;              // debug: of pair 0
+};
+
+// Everything after the argument checks.  clip[f]: descriptors of frame f that take part.
+int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, const std::vector<int32_t>& clip,
+              int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, bool debug, MatchResult* R) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    R->count.assign((size_t)n_pairs, 0); R->num_row.assign((size_t)n_pairs, 0); R->num_col.assign((size_t)n_pairs, 0);
+    R->rows.assign((size_t)n_pairs, std::vector<int32_t>());
+    // the frames that occur in a pair with work, each once
+    std::vector<int64_t> dev_off((size_t)n_frames, -1);
+    std::vector<int32_t> live;                           // pairs with rows and columns
+    for (int p = 0; p < n_pairs; ++p)
+        if (clip[(size_t)pair_a[p]] > 0 && clip[(size_t)pair_b[p]] > 0) { live.push_back(p); dev_off[(size_t)pair_a[p]] = dev_off[(size_t)pair_b[p]] = 0; }
+    if (live.empty()) return XRSFM_BA_OK;
+    int64_t D = 0;
+    for (int f = 0; f < n_frames; ++f) if (dev_off[(size_t)f] == 0) { dev_off[(size_t)f] = D; D += clip[(size_t)f]; }
+    const size_t o_off = al((size_t)D * xmatch::kDim), desc_bytes = o_off + al(sizeof(int32_t) * (size_t)D);
+    // sub-batches of pairs under the workspace budget
+    size_t budget = (size_t)1024 << 20;
+    if (const char* s = getenv("XRSFM_BA_MATCH_WORKSPACE_MB")) { const long long mb = atoll(s); if (mb >= 0) budget = (size_t)mb << 20; }
+    budget = budget > desc_bytes ? budget - desc_bytes : 0;
+    struct Layout { size_t o_pr, o_it, in_bytes, o_cnt, o_m, o_rt, o_ct, back_bytes, o_cm, o_part, total; int64_t rows, cols, parts, items; };
+    auto layout = [&](int64_t np, int64_t rows, int64_t cols, int64_t parts, int64_t items) {
+        Layout L{};
+        size_t off = 0;
+        auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+        L.o_pr = take(sizeof(MatchPair) * (size_t)np); L.o_it = take(sizeof(MatchItem) * (size_t)items); L.in_bytes = off;
+        L.o_cnt = take(sizeof(int32_t) * 4 * (size_t)np); L.o_m = take(sizeof(int32_t) * 2 * (size_t)rows);
+        if (!debug) L.back_bytes = off - L.o_cnt;
+        L.o_rt = take(sizeof(int32_t) * 3 * (size_t)rows); L.o_ct = take(sizeof(int32_t) * 3 * (size_t)cols);
+        if (debug) L.back_bytes = off - L.o_cnt;
+        L.o_cm = take(sizeof(int32_t) * (size_t)cols); L.o_part = take(sizeof(int32_t) * 3 * (size_t)parts);
+        L.total = off; L.rows = rows; L.cols = cols; L.parts = parts; L.items = items;
+        return L;
+    };
+    struct Batch { size_t first, last; Layout L; };
+    std::vector<Batch> batches;
+    {
+        size_t first = 0;
+        int64_t rows = 0, cols = 0, parts = 0, items = 0;
+        for (size_t k = 0; k < live.size(); ++k) {
+            const int64_t na = clip[(size_t)pair_a[live[k]]], nb = clip[(size_t)pair_b[live[k]]], strips = (na + kMatchStrip - 1) / kMatchStrip;
+            if (k > first && layout((int64_t)(k - first) + 1, rows + na, cols + nb, parts + strips * nb, items + strips).total > budget) {
+                batches.push_back({first, k, layout((int64_t)(k - first), rows, cols, parts, items)});
+                first = k; rows = cols = parts = items = 0;
+            }
+            rows += na; cols += nb; parts += strips * nb; items += strips;
+        }
+        batches.push_back({first, live.size(), layout((int64_t)(live.size() - first), rows, cols, parts, items)});
+    }
+    size_t ws_bytes = 0, in_max = 0, back_max = 0;
+    for (const Batch& b : batches) { ws_bytes = std::max(ws_bytes, b.L.total); in_max = std::max(in_max, b.L.in_bytes); back_max = std::max(back_max, b.L.back_bytes); }
+
+    HIPCHK(hipSetDevice(0));
+    const float* tab = match_table_device();
+    if (!tab) return XRSFM_BA_ENOMEM;
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    size_t cls_d = 0, cls_w = 0;
+    unsigned char* dbase = (unsigned char*)g_cache.get(0, desc_bytes, &cls_d);
+    unsigned char* base = dbase ? (unsigned char*)g_cache.get(0, ws_bytes, &cls_w) : nullptr;
+    if (!base) { if (dbase) g_cache.put(0, dbase, cls_d); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    int e = 0;
+    {
+        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } dstage, stage, back;
+        dstage.p = (unsigned char*)g_pinned.get((size_t)D * xmatch::kDim, &dstage.cap);
+        stage.p = (unsigned char*)g_pinned.get(in_max, &stage.cap); back.p = (unsigned char*)g_pinned.get(back_max, &back.cap);
+        if (!dstage.p || !stage.p || !back.p) { g_cache.put(0, base, cls_w); g_cache.put(0, dbase, cls_d); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        for (int f = 0; f < n_frames; ++f)
+            if (dev_off[(size_t)f] >= 0 && clip[(size_t)f] > 0)
+                memcpy(dstage.data() + (size_t)dev_off[(size_t)f] * xmatch::kDim, desc + (size_t)desc_ptr[f] * xmatch::kDim, (size_t)clip[(size_t)f] * xmatch::kDim);
+        hipStream_t st = hb.stream;
+        // XRSFM_BA_MATCH_TIMING: the kernels' times from events on the stream, one line on stderr (tools/descriptor_match_timing.py)
+        struct Events { hipEvent_t ev[5] = {}; bool on = false; ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); } } tm;
+        if (getenv("XRSFM_BA_MATCH_TIMING")) { tm.on = true; for (hipEvent_t& x : tm.ev) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; tm.on = false; } }
+        float ms_prep = 0.f, ms_dots = 0.f, ms_select = 0.f;
+        if (hipMemcpyAsync(dbase, dstage.data(), (size_t)D * xmatch::kDim, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+        if (!e) {
+            if (tm.on) (void)hipEventRecord(tm.ev[0], st);
+            hipLaunchKernelGGL(k_match_prep, dim3((unsigned)((D * 8 + kMatchThreads - 1) / kMatchThreads)), dim3(kMatchThreads), 0, st, dbase, (int32_t*)(dbase + o_off), D);
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+            if (tm.on) (void)hipEventRecord(tm.ev[1], st);
+        }
+        const MatchParams prm{opt->max_distance, opt->max_ratio, opt->mutual_best ? 1 : 0};
+        for (size_t bi = 0; bi < batches.size() && !e; ++bi) {
+            const Batch& b = batches[bi];
+            const Layout& L = b.L;
+            const int np = (int)(b.last - b.first);
+            MatchPair* prs = (MatchPair*)(stage.data() + L.o_pr);
+            MatchItem* its = (MatchItem*)(stage.data() + L.o_it);
+            int64_t rows = 0, cols = 0, parts = 0, items = 0;
+            for (int q = 0; q < np; ++q) {
+                const int p = live[b.first + (size_t)q];
+                MatchPair& pr = prs[q];
+                pr.a_off = dev_off[(size_t)pair_a[p]]; pr.b_off = dev_off[(size_t)pair_b[p]];
+                pr.n_a = clip[(size_t)pair_a[p]]; pr.n_b = clip[(size_t)pair_b[p]];
+                pr.strips = (pr.n_a + kMatchStrip - 1) / kMatchStrip; pr.pad = 0;
+                pr.part_off = parts; pr.row_off = rows; pr.col_off = cols;
+                for (int s = 0; s < pr.strips; ++s) its[items++] = MatchItem{q, s};
+                rows += pr.n_a; cols += pr.n_b; parts += (int64_t)pr.strips * pr.n_b;
+            }
+            if (hipMemcpyAsync(base, stage.data(), L.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (tm.on) (void)hipEventRecord(tm.ev[2], st);
+            hipLaunchKernelGGL(k_match_dots, dim3((unsigned)L.items), dim3(kMatchThreads), 0, st, (const MatchItem*)(base + L.o_it), (const MatchPair*)(base + L.o_pr),
+                               (const uint8_t*)dbase, (const int32_t*)(dbase + o_off), (int32_t*)(base + L.o_part), (int32_t*)(base + L.o_rt));
+            if (hipGetLastError() != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (tm.on) (void)hipEventRecord(tm.ev[3], st);
+            hipLaunchKernelGGL(k_match_select, dim3((unsigned)np), dim3(kMatchThreads), 0, st, (const MatchPair*)(base + L.o_pr), prm, tab, (const int32_t*)(base + L.o_part),
+                               (const int32_t*)(base + L.o_rt), (int32_t*)(base + L.o_ct), (int32_t*)(base + L.o_cm), (int32_t*)(base + L.o_m), (int32_t*)(base + L.o_cnt));
+            if (hipGetLastError() != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (tm.on) (void)hipEventRecord(tm.ev[4], st);
+            if (hipMemcpyAsync(back.data(), base + L.o_cnt, L.back_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (tm.on) {
+                float a = 0.f;
+                if (bi == 0 && hipEventElapsedTime(&a, tm.ev[0], tm.ev[1]) == hipSuccess) ms_prep = a;
+                if (hipEventElapsedTime(&a, tm.ev[2], tm.ev[3]) == hipSuccess) ms_dots += a;
+                if (hipEventElapsedTime(&a, tm.ev[3], tm.ev[4]) == hipSuccess) ms_select += a;
+            }
+            const unsigned char* o = back.data() - L.o_cnt;          // (offsets above are relative to the block)
+            const int32_t* cnt = (const int32_t*)(o + L.o_cnt);
+            const int32_t* mm = (const int32_t*)(o + L.o_m);
+            for (int q = 0; q < np; ++q) {
+                const int p = live[b.first + (size_t)q];
+                const int32_t c = cnt[4 * q];
+                if (c < 0 || c > prs[q].n_a) { e = XRSFM_BA_EINTERNAL; break; }
+                R->count[(size_t)p] = c; R->num_row[(size_t)p] = cnt[4 * q + 1]; R->num_col[(size_t)p] = cnt[4 * q + 2];
+                R->rows[(size_t)p].assign(mm + 2 * prs[q].row_off, mm + 2 * (prs[q].row_off + c));
+            }
+            if (debug && !e) {
+                R->row_top.assign((const int32_t*)(o + L.o_rt), (const int32_t*)(o + L.o_rt) + 3 * (size_t)prs[0].n_a);
+                R->col_top.assign((const int32_t*)(o + L.o_ct), (const int32_t*)(o + L.o_ct) + 3 * (size_t)prs[0].n_b);
+            }
+        }
+        if (e) (void)hipStreamSynchronize(st);
+        if (tm.on && !e) fprintf(stderr, "[xrsfm_ba] match timing: prep %.4f ms, dots %.4f ms, select %.4f ms, launches %zu\n", ms_prep, ms_dots, ms_select, batches.size());
+    }
+    g_cache.put(0, base, cls_w);
+    g_cache.put(0, dbase, cls_d);
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int match_no_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the descriptor matching has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    return 0;
+}
+
+int match_descriptors_impl(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, int32_t n_pairs,
+                           const int32_t* pair_a, const int32_t* pair_b, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
+                           int32_t* num_row, int32_t* num_col) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_match_descriptors: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_pairs < 0 || n_frames < 0 || matches_capacity < 0) return bad("negative count");
+    if (!std::isfinite(opt->max_distance) || !std::isfinite(opt->max_ratio)) return bad("non-finite option");
+    if (opt->max_distance <= 0.0f) return bad("max_distance <= 0");
+    if (!(opt->max_ratio > 0.0f && opt->max_ratio <= 1.0f)) return bad("max_ratio outside (0, 1]");
+    if (opt->max_features < 1 || opt->max_features > XRSFM_BA_MATCH_MAX_FEATURES) return bad("max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES");
+    if (n_pairs == 0) return XRSFM_BA_OK;
+    if (!match_ptr) return bad("NULL match_ptr");
+    if (!pair_a || !pair_b) return bad("NULL pair_a or pair_b");
+    if (!desc_ptr) return bad("NULL desc_ptr");
+    if (desc_ptr[0] != 0) return bad("desc_ptr does not start at 0");
+    for (int f = 0; f < n_frames; ++f)
+        if (desc_ptr[f + 1] < desc_ptr[f]) return bad("desc_ptr decreases");
+    if (desc_ptr[n_frames] > 0 && !desc) return bad("NULL desc");
+    for (int p = 0; p < n_pairs; ++p)
+        if (pair_a[p] < 0 || pair_a[p] >= n_frames || pair_b[p] < 0 || pair_b[p] >= n_frames) return bad("frame index out of range");
+    if (matches_capacity > 0 && !matches) return bad("NULL matches");
+    if (int e = match_no_device()) return e;
+    std::vector<int32_t> clip((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) clip[(size_t)f] = (int32_t)std::min<int64_t>(desc_ptr[f + 1] - desc_ptr[f], opt->max_features);
+    MatchResult R;
+    if (int e = match_run(opt, n_frames, desc_ptr, desc, clip, n_pairs, pair_a, pair_b, false, &R)) return e;
+    int64_t need = 0;
+    for (int p = 0; p < n_pairs; ++p) need += R.count[(size_t)p];
+    if (need > matches_capacity) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_match_descriptors: matches_capacity %lld is below the %lld matches of the call\n", (long long)matches_capacity, (long long)need);
+        return XRSFM_BA_EINVAL;
+    }
+    match_ptr[0] = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const std::vector<int32_t>& r = R.rows[(size_t)p];
+        if (!r.empty()) memcpy(matches + 2 * match_ptr[p], r.data(), sizeof(int32_t) * r.size());
+        match_ptr[p + 1] = match_ptr[p] + R.count[(size_t)p];
+    }
+    if (num_row) memcpy(num_row, R.num_row.data(), sizeof(int32_t) * (size_t)n_pairs);
+    if (num_col) memcpy(num_col, R.num_col.data(), sizeof(int32_t) * (size_t)n_pairs);
+    return XRSFM_BA_OK;
+}
+
+int debug_match_top2_impl(int32_t n_a, const uint8_t* desc_a, int32_t n_b, const uint8_t* desc_b, int32_t* row_top, int32_t* col_top) {
+    if (n_a < 0 || n_b < 0 || n_a > XRSFM_BA_MATCH_MAX_FEATURES || n_b > XRSFM_BA_MATCH_MAX_FEATURES) return XRSFM_BA_EINVAL;
+    if ((n_a > 0 && (!desc_a || !row_top)) || (n_b > 0 && (!desc_b || !col_top))) return XRSFM_BA_EINVAL;
+    if (int e = match_no_device()) return e;
+    MatchResult R;
+    if (n_a > 0 && n_b > 0) {
+        xrsfm_ba_match_options opt;
+        xrsfm_ba_match_options_default(&opt);
+        std::vector<uint8_t> d((size_t)(n_a + n_b) * xmatch::kDim);
+        memcpy(d.data(), desc_a, (size_t)n_a * xmatch::kDim);
+        memcpy(d.data() + (size_t)n_a * xmatch::kDim, desc_b, (size_t)n_b * xmatch::kDim);
+        const int64_t ptr[3] = {0, n_a, (int64_t)n_a + n_b};
+        const int32_t pa = 0, pb = 1;
+        if (int e = match_run(&opt, 2, ptr, d.data(), std::vector<int32_t>{n_a, n_b}, 1, &pa, &pb, true, &R)) return e;
+        memcpy(row_top, R.row_top.data(), sizeof(int32_t) * 3 * (size_t)n_a);
+        memcpy(col_top, R.col_top.data(), sizeof(int32_t) * 3 * (size_t)n_b);
+    } else {                                   // nothing to multiply: every triple is the initial one
+        for (int i = 0; i < n_a; ++i) { row_top[3 * i] = 0; row_top[3 * i + 1] = -1; row_top[3 * i + 2] = 0; }
+        for (int j = 0; j < n_b; ++j) { col_top[3 * j] = 0; col_top[3 * j + 1] = -1; col_top[3 * j + 2] = 0; }
+    }
+    return XRSFM_BA_OK;
+}
+}  // namespace
+
+int xrsfm_ba_match_descriptors(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, int32_t n_pairs,
+                               const int32_t* pair_a, const int32_t* pair_b, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
+                               int32_t* num_row, int32_t* num_col) {
+    return no_throw([&] { return match_descriptors_impl(opt, n_frames, desc_ptr, desc, n_pairs, pair_a, pair_b, matches_capacity, match_ptr, matches,
+                                                        num_row, num_col); });
+}
+
+int xrsfm_ba_debug_match_top2(int32_t n_a, const uint8_t* desc_a, int32_t n_b, const uint8_t* desc_b, int32_t* row_top, int32_t* col_top) {
+    return no_throw([&] { return debug_match_top2_impl(n_a, desc_a, n_b, desc_b, row_top, col_top); });
 }
 
 // ---------------------------------------------------------------- diagnostics
