@@ -1439,13 +1439,17 @@ __device__ __forceinline__ void cam_update_one(const Dev& d, int c, const double
 // Workgroups >= n_item_blocks: candidate cameras from the camera part of the solution (thread = camera; cam_update_one).
 // PREP = true: the damped point block is factored here from Hpp and the radius (point_factor(), u = C (C^T a)); false: read
 // Hinv as k_point_prep stored it (PCG path, XRSFM_BA_PREP_FUSED=0).
+// k_backsub_parent: the body as it was before the 5-wave kernels below (XRSFM_BA_BACKSUB_LEAN=0, the A/B reference of
+// tests/test_gpu_backsub_lean.py): 4 waves per SIMD, head-only operands held in registers, long tracks in the same function, yp always stored.
+// Its text stays as it was, the long-track sweeps included (backsub_long_item below repeats them for k_backsub_long): the compiler is free
+// to contract a sum of two products around either one, and does so differently when the body moves into a function of its own.
 template <bool PREP>
 #if XBA_BACKSUB_WAVES > 0
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(XBA_BACKSUB_WAVES, XBA_BACKSUB_WAVES)))
 #else
 __global__ __launch_bounds__(kBlock)
 #endif
-void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, double radius) {
+void k_backsub_parent(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, double radius) {
     if ((int)blockIdx.x >= n_item_blocks) {
         const int c = (blockIdx.x - n_item_blocks) * kBlock + threadIdx.x;
         if (c < d.n_cams) cam_update_one(d, c, d.px + 6 * (size_t)c, camrec_cand);
@@ -1589,6 +1593,261 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
             }
         }
     }
+    model = wave_sum(model);
+    step2 = wave_sum(step2);
+    if (lane == 0) { d.part[2 * d.n_items + item] = model; d.part[3 * d.n_items + item] = step2; }
+}
+
+// One track of more than 64 observations (a run of whole tiles, one wave): two sweeps over its tiles around the point solve.
+// model: per-lane terms of the model decrease, step2: lane 0's squared point step (the caller sums both over the wave).
+// store_yp: also keep the scaled point step in d.yp (the debug entry's point_step).
+template <bool PREP>
+__device__ __forceinline__ void backsub_long_item(const Dev& d, const Item it, int lane, double radius, bool store_yp, double& model, double& step2) {
+    {
+        double wsum[3] = {0, 0, 0};
+        int pt0 = -1;
+        for (int tl = 0; tl < it.n_tiles; ++tl) {
+            const int slot = (it.first_tile + tl) * kWave + lane;
+            const int cam = d.slot_cam[slot];
+            if (cam >= 0) {
+                pt0 = d.slot_pt[slot];
+                const double* y = d.px + 6 * (size_t)cam;
+                double F[12], E[6], r0, r1;
+                load_FE_rc(d, slot, cam, pt0, F, E, r0, r1);
+                double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { v0 += F[k] * y[k]; v1 += F[6 + k] * y[k]; }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) wsum[k] += E[k] * v0 + E[3 + k] * v1;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { wsum[k] = wave_sum(wsum[k]); wsum[k] = __shfl(wsum[k], 0, kWave); }
+        pt0 = __shfl(pt0, 0, kWave);
+        const double* h = (PREP ? d.Hpp : d.Hinv) + 6 * (size_t)pt0;
+        const double* g = d.gp + 3 * (size_t)pt0;
+        const double a0 = g[0] - wsum[0], a1 = g[1] - wsum[1], a2 = g[2] - wsum[2];
+        double u[3];
+        if (PREP) {
+            const double hv[6] = {h[0], h[1], h[2], h[3], h[4], h[5]};
+            double cf[6];
+            point_factor(hv, radius, cf);
+            const double s0 = cf[0] * a0, s1 = cf[1] * a0 + cf[3] * a1, s2 = cf[2] * a0 + cf[4] * a1 + cf[5] * a2;
+            u[0] = cf[0] * s0 + cf[1] * s1 + cf[2] * s2;
+            u[1] = cf[3] * s1 + cf[4] * s2;
+            u[2] = cf[5] * s2;
+        } else {
+            u[0] = h[0] * a0 + h[1] * a1 + h[2] * a2;
+            u[1] = h[1] * a0 + h[3] * a1 + h[4] * a2;
+            u[2] = h[2] * a0 + h[4] * a1 + h[5] * a2;
+        }
+        if (lane == 0) {
+            const double* sp = d.scale_p + 3 * (size_t)pt0;
+            const double* P = d.P + 3 * (size_t)pt0;
+            double* Pc = d.P_cand + 3 * (size_t)pt0;
+            double* yo = d.yp + 3 * (size_t)pt0;
+            const bool var = !d.pt_const[pt0];
+            for (int k = 0; k < 3; ++k) {
+                const double dl = var ? -u[k] * sp[k] : 0.0;
+                const double pn = P[k] + dl;
+                Pc[k] = pn;
+                if (store_yp) yo[k] = u[k];
+                const double df = pn - P[k];
+                step2 += df * df;
+            }
+        }
+        for (int tl = 0; tl < it.n_tiles; ++tl) {
+            const int slot = (it.first_tile + tl) * kWave + lane;
+            const int cam = d.slot_cam[slot];
+            if (cam >= 0) {
+                const double* y = d.px + 6 * (size_t)cam;
+                double F[12], E[6], r0, r1;
+                load_FE_rc(d, slot, cam, pt0, F, E, r0, r1);
+                double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { v0 += F[k] * y[k]; v1 += F[6 + k] * y[k]; }
+                const double m0 = v0 + E[0] * u[0] + E[1] * u[1] + E[2] * u[2];
+                const double m1 = v1 + E[3] * u[0] + E[4] * u[1] + E[5] * u[2];
+                model += m0 * (r0 - 0.5 * m0) + m1 * (r1 - 0.5 * m1);
+            }
+        }
+    }
+}
+
+// ---- back-substitution, the default kernels (XRSFM_BA_BACKSUB_LEAN=0: k_backsub_parent above)
+// The same arithmetic as k_backsub_parent, expression tree for expression tree (tests/test_gpu_backsub_lean.py: bit for bit), laid
+// out for 5 waves per SIMD (96 VGPRs) instead of 4:
+//  - k_backsub handles the items of one tile; tracks longer than a tile go through k_backsub_long, a launch over the long
+//    items only (their list is made once per context), so their two sweeps are not in the function the common path is allocated for;
+//  - what only the head lane of a track needs after the segmented sum — Hpp (or Hinv) and g_p of its point, 9 doubles — is
+//    requested at the top by the head lanes with direct-to-LDS loads (72 B per lane, lane-linear) and read back after the
+//    reduction, instead of living in 18 VGPRs of every lane across the recomputation: no register, and no third round trip.
+//    (16- and 4-byte loads: the destination of the 12-byte form is lane x 16, not lane x 12, on an MI355X);
+//  - scale_p and P are loaded once, for the recomputation and the head lane's update alike; F y is summed as F is produced;
+//  - YP: d.yp (the scaled point step) is stored only for the debug entry that hands it out — nothing else reads it.
+#if XBA_BACKSUB_WAVES > 0
+#define XBA_BACKSUB_LEAN_WAVES XBA_BACKSUB_WAVES
+#else
+#define XBA_BACKSUB_LEAN_WAVES 5
+#endif
+constexpr int kBsLdsH = 16 * kWave, kBsLdsW = 4 * kWave;              // one direct-to-LDS load of the wave: 16 / 4 bytes per lane
+constexpr int kBsLdsWave = 4 * kBsLdsH + 2 * kBsLdsW;                 // 4608 bytes per wave
+
+// A sum of two products can be contracted around either product, and which one the compiler rounds first depends on the code
+// around it.  k_backsub rounds the product that went through rounded() first and fuses the other, which is what the compiler makes
+// of the same sums in k_backsub_parent (read from its code object; tests/test_gpu_backsub_lean.py compares the two bit for bit).
+__device__ __forceinline__ double rounded(double x) { asm("" : "+v"(x)); return x; }
+
+// v = F y, E and the robustified residual of one observation: load_FE_rc and the sums over F of its callers, with F never held
+// as a whole.  Pw: the point; sp, mp: its Jacobi scale and variable mask, multiplied into spm (fe_from_j's sp0..2) where E needs
+// them — next to the loads of the camera's scales and step, not across the projection.
+__device__ __forceinline__ void load_vE_rc(const Dev& d, int slot, int cam, const double (&Pw)[3], const double* __restrict__ sp, double mp,
+                                           double (&spm)[3], double (&E)[6], double& v0, double& v1, double& r0, double& r1) {
+    const size_t ns = (size_t)d.n_slots;
+    const CamLin& c = d.camrec[cam];
+    double M[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
+    double j[6];
+    if (d.Jp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
+        r0 = d.rt[slot]; r1 = d.rt[ns + slot];
+    } else {
+        obs_rj(d, slot, cam, M, Pw, r0, r1, j);
+    }
+    const double rp0 = M[0] * Pw[0] + M[1] * Pw[1] + M[2] * Pw[2];
+    const double rp1 = M[3] * Pw[0] + M[4] * Pw[1] + M[5] * Pw[2];
+    const double rp2 = M[6] * Pw[0] + M[7] * Pw[1] + M[8] * Pw[2];
+    const double* y = d.px + 6 * (size_t)cam;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) spm[k] = sp[k] * mp;
+    double v[2];
+#pragma unroll
+    for (int row = 0; row < 2; ++row) {
+        const double a = j[3 * row], b = j[3 * row + 1], cc = j[3 * row + 2];
+        double vr = 0.0;
+        vr += -2.0 * (b * rp2 - cc * rp1) * c.sq[0] * y[0];
+        vr += -2.0 * (cc * rp0 - a * rp2) * c.sq[1] * y[1];
+        vr += -2.0 * (a * rp1 - b * rp0) * c.sq[2] * y[2];
+        vr += a * c.st[0] * y[3];
+        vr += b * c.st[1] * y[4];
+        vr += cc * c.st[2] * y[5];
+        v[row] = vr;
+        E[3 * row + 0] = (a * M[0] + b * M[3] + cc * M[6]) * spm[0];
+        E[3 * row + 1] = (a * M[1] + b * M[4] + cc * M[7]) * spm[1];
+        E[3 * row + 2] = (a * M[2] + b * M[5] + cc * M[8]) * spm[2];
+    }
+    v0 = v[0]; v1 = v[1];
+}
+
+template <bool PREP, bool YP>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(XBA_BACKSUB_LEAN_WAVES, XBA_BACKSUB_LEAN_WAVES)))
+void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, double radius) {
+    typedef __attribute__((address_space(1))) const void* gptr;
+    typedef __attribute__((address_space(3))) void* lptr;
+    __shared__ __attribute__((aligned(16))) unsigned char hg[kWavesPerBlock * kBsLdsWave];
+    if ((int)blockIdx.x >= n_item_blocks) {
+        const int c = (blockIdx.x - n_item_blocks) * kBlock + threadIdx.x;
+        if (c < d.n_cams) cam_update_one(d, c, d.px + 6 * (size_t)c, camrec_cand);
+        return;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blockIdx.x * kWavesPerBlock + wave;                     // wave-uniform: item / tile records through scalar loads
+    if (item >= d.n_items) return;
+    const Item it = d.items[item];
+    if (it.n_tiles != 1) return;                                             // k_backsub_long
+    const SlotCtx s = load_slot(d, it.first_tile, lane);
+    const int maxlen = d.tile_maxlen[it.first_tile];
+    // the wave's own 4.5 KB: [3][64] x 16 B of Hpp, [64] x 16 B + [2][64] x 4 B of g_p, lane-linear (the hardware adds lane x size
+    // to the wave-uniform base it is given, for the lanes that are on).  One tile per wave and no other use of this memory: nothing to wait for before the request.
+    unsigned char* const lw = hg + wave * kBsLdsWave;
+    if (s.head) {
+        const double* h = (PREP ? d.Hpp : d.Hinv) + 6 * (size_t)s.pt;
+        const unsigned char* g = reinterpret_cast<const unsigned char*>(d.gp + 3 * (size_t)s.pt);
+        __builtin_amdgcn_global_load_lds((gptr)h, (lptr)lw, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(h + 2), (lptr)(lw + kBsLdsH), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(h + 4), (lptr)(lw + 2 * kBsLdsH), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)g, (lptr)(lw + 3 * kBsLdsH), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(g + 16), (lptr)(lw + 4 * kBsLdsH), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(g + 20), (lptr)(lw + 4 * kBsLdsH + kBsLdsW), 4, 0, 0);
+    }
+    double model = 0.0, step2 = 0.0;
+    double E[6], v0, v1, r0, r1;                                            // read by lanes with an observation only
+    double w[3] = {0, 0, 0};                                                // operand of the segmented sum: zeros on the other lanes
+    // scale_p (times the variable mask: x 1.0 is exact, and a constant point takes no step) and P: loaded once, for every lane's
+    // recomputation and for the head lane's update
+    double spm[3], Pv[3];
+    bool var = false;
+    if (s.valid) {
+        const double* P = d.P + 3 * (size_t)s.pt;
+        var = !d.pt_const[s.pt];
+        const double mp = var ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Pv[k] = P[k];
+        load_vE_rc(d, s.slot, s.cam, Pv, d.scale_p + 3 * (size_t)s.pt, mp, spm, E, v0, v1, r0, r1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = rounded(E[k] * v0) + E[3 + k] * v1;
+    } else { dead_values(spm); dead_values(Pv); dead_values(E); XBA_DEAD_VALUE(v0); XBA_DEAD_VALUE(v1); XBA_DEAD_VALUE(r0); XBA_DEAD_VALUE(r1); }
+    seg_reduce<3>(w, s.pt, lane, maxlen);
+    double u[3];                                       // head lanes compute it, the lanes of the track fetch it from their head
+    if (s.head) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // the direct-to-LDS loads count as vector memory loads
+        const double2* hq = reinterpret_cast<const double2*>(lw) + lane;
+        const double2 h01 = hq[0], h23 = hq[kWave], h45 = hq[2 * kWave];
+        const double hh[6] = {h01.x, h01.y, h23.x, h23.y, h45.x, h45.y};
+        const unsigned* gq = reinterpret_cast<const unsigned*>(lw + 3 * kBsLdsH);
+        const unsigned g0 = gq[4 * lane], g1 = gq[4 * lane + 1], g2 = gq[4 * lane + 2], g3 = gq[4 * lane + 3], g4 = gq[4 * kWave + lane], g5 = gq[5 * kWave + lane];
+        const double a0 = __hiloint2double((int)g1, (int)g0) - w[0], a1 = __hiloint2double((int)g3, (int)g2) - w[1],
+                     a2 = __hiloint2double((int)g5, (int)g4) - w[2];
+        if (PREP) {
+            double cf[6];
+            point_factor(hh, radius, cf);                     // Hinv = C C^T, C upper {c00 c01 c02 c11 c12 c22}
+            const double s0 = cf[0] * a0, s1 = rounded(cf[1] * a0) + cf[3] * a1, s2 = cf[2] * a0 + rounded(cf[4] * a1) + cf[5] * a2;
+            u[0] = cf[0] * s0 + rounded(cf[1] * s1) + cf[2] * s2;
+            u[1] = cf[3] * s1 + rounded(cf[4] * s2);
+            u[2] = cf[5] * s2;
+        } else {
+            u[0] = hh[0] * a0 + rounded(hh[1] * a1) + hh[2] * a2;
+            u[1] = hh[1] * a0 + rounded(hh[3] * a1) + hh[4] * a2;
+            u[2] = hh[2] * a0 + rounded(hh[4] * a1) + hh[5] * a2;
+        }
+        double* Pc = d.P_cand + 3 * (size_t)s.pt;
+        double df[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double dl = var ? -u[k] * spm[k] : 0.0;
+            const double pn = Pv[k] + dl;
+            Pc[k] = pn;
+            if (YP) d.yp[3 * (size_t)s.pt + k] = u[k];
+            df[k] = pn - Pv[k];
+        }
+        step2 = df[0] * df[0] + rounded(df[1] * df[1]) + df[2] * df[2];
+    } else dead_values(u);
+    const int hl = seg_head_lane(s.head || !s.valid, lane);
+    u[0] = __shfl(u[0], hl, kWave); u[1] = __shfl(u[1], hl, kWave); u[2] = __shfl(u[2], hl, kWave);
+    if (s.valid) {
+        const double m0 = v0 + E[0] * u[0] + E[1] * u[1] + E[2] * u[2];
+        const double m1 = v1 + E[3] * u[0] + E[4] * u[1] + E[5] * u[2];
+        model = m0 * (r0 - 0.5 * m0) + rounded(m1 * (r1 - 0.5 * m1));
+    }
+    model = wave_sum(model);
+    step2 = wave_sum(step2);
+    if (lane == 0) { d.part[2 * d.n_items + item] = model; d.part[3 * d.n_items + item] = step2; }
+}
+
+// The tracks longer than a tile: wave = one entry of long_items (item indices, ascending).  Writes the same partials and
+// candidate points as k_backsub_parent does for these items.
+template <bool PREP>
+__global__ __launch_bounds__(kBlock) void k_backsub_long(Dev d, const int* __restrict__ long_items, int n_long, double radius, int store_yp) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int li = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+    if (li >= n_long) return;
+    const int item = long_items[li];
+    const Item it = d.items[item];
+    double model = 0.0, step2 = 0.0;
+    backsub_long_item<PREP>(d, it, lane, radius, store_yp != 0, model, step2);
     model = wave_sum(model);
     step2 = wave_sum(step2);
     if (lane == 0) { d.part[2 * d.n_items + item] = model; d.part[3 * d.n_items + item] = step2; }

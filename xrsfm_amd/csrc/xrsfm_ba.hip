@@ -199,6 +199,9 @@ struct xrsfm_ba_context {
                                     // cameras inside the tile fill: no k_point_prep launch (XRSFM_BA_PREP_FUSED=0: round-2 schedule)
     double step_radius = 0.0;       // radius of the step being assembled / solved (prepare_step, assemble_wide)
     bool step_prep = false;         // ... and whether its kernels form the point factors themselves
+    bool backsub_lean = true;       // back-substitution by the 5-wave kernels (k_backsub + k_backsub_long over long_items); XRSFM_BA_BACKSUB_LEAN=0:
+                                    // k_backsub_parent, the A/B reference (tests/test_gpu_backsub_lean.py)
+    int* long_items = nullptr; int n_long = 0;      // items of more than one tile (tracks longer than 64 observations), ascending
     bool step_valid = false;        // a step of the current linearisation has been assembled and solved (xrsfm_ba_debug_backsub needs it)
     bool backsub_done = false;      // ... and xrsfm_ba_debug_backsub has run on it (xrsfm_ba_debug_backsub_layout: campart, candidate intrinsics)
     bool gradmax_done = false, published = false;    // the linearisation tail did these in its own launch
@@ -1420,6 +1423,30 @@ void accept_candidate(xrsfm_ba_context* c) {
     std::swap(d.Hpp, c->alt.Hpp); std::swap(d.gp, c->alt.gp); std::swap(d.camlin, c->alt.camlin);
 }
 
+// The back-substitution launches over the tracks: nbi workgroups of items, then nbc of candidate cameras (cam_update_one; cr: also
+// their linearisation records).  want_yp: d.yp, the scaled point step, is stored too — only xrsfm_ba_debug_backsub hands it out.
+void launch_backsub(xrsfm_ba_context* c, int nbi, int nbc, CamLin* cr, bool want_yp) {
+    Dev& d = c->d;
+    const dim3 grid(nbi + nbc), block(kBlock);
+    if (!c->backsub_lean) {
+        if (c->step_prep) LAUNCH(c, K_BACKSUB, k_backsub_parent<true>, grid, block, 0, d, nbi, cr, c->step_radius);
+        else LAUNCH(c, K_BACKSUB, k_backsub_parent<false>, grid, block, 0, d, nbi, cr, c->step_radius);
+        return;
+    }
+    if (c->step_prep) {
+        if (want_yp) LAUNCH(c, K_BACKSUB, (k_backsub<true, true>), grid, block, 0, d, nbi, cr, c->step_radius);
+        else LAUNCH(c, K_BACKSUB, (k_backsub<true, false>), grid, block, 0, d, nbi, cr, c->step_radius);
+    } else {
+        if (want_yp) LAUNCH(c, K_BACKSUB, (k_backsub<false, true>), grid, block, 0, d, nbi, cr, c->step_radius);
+        else LAUNCH(c, K_BACKSUB, (k_backsub<false, false>), grid, block, 0, d, nbi, cr, c->step_radius);
+    }
+    if (c->n_long > 0) {
+        const dim3 lgrid(cdiv(c->n_long, kWavesPerBlock));
+        if (c->step_prep) LAUNCH(c, K_BACKSUB, k_backsub_long<true>, lgrid, block, 0, d, c->long_items, c->n_long, c->step_radius, want_yp ? 1 : 0);
+        else LAUNCH(c, K_BACKSUB, k_backsub_long<false>, lgrid, block, 0, d, c->long_items, c->n_long, c->step_radius, want_yp ? 1 : 0);
+    }
+}
+
 // Back-substitution -> candidate state, then either
 //   speculate: linearisation AT the candidate (its cost is the candidate cost; if the step is accepted the next iteration
 //              starts from it and nothing else has to run), or
@@ -1437,10 +1464,7 @@ int finish_step(xrsfm_ba_context* c, double huber_a, bool speculate) {
     } else {
         const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cams_done ? cdiv(d.n_cams, kBlock) : 0;
         CamLin* cr = (cams_done && speculate) ? c->alt.camrec : (CamLin*)nullptr;
-        if (nbi + nbc > 0) {
-            if (c->step_prep) LAUNCH(c, K_BACKSUB, k_backsub<true>, dim3(nbi + nbc), dim3(kBlock), 0, d, nbi, cr, c->step_radius);
-            else LAUNCH(c, K_BACKSUB, k_backsub<false>, dim3(nbi + nbc), dim3(kBlock), 0, d, nbi, cr, c->step_radius);
-        }
+        if (nbi + nbc > 0) launch_backsub(c, nbi, nbc, cr, false);
         if (d.n_cams > 0 && !cams_done) LAUNCH(c, K_SMALL, k_cam_update, dim3(cdiv(d.n_cams, kBlock)), dim3(kBlock), 0, d);
     }
     if (speculate) {
@@ -2471,6 +2495,10 @@ static int create_body(const xrsfm_ba_problem* p, int device, xrsfm_ba_context* 
         auto P_ = [](auto& member) { return const_cast<std::remove_const_t<std::remove_pointer_t<std::remove_reference_t<decltype(member)>>>**>(&member); };
         up.add_raw(reinterpret_cast<void**>(const_cast<Item**>(&d.items)), k.items.data(), k.items.size() * sizeof(int));
         up.add(P_(d.cam), cams); up.add(P_(d.cam_cand), cams); up.add(&c->cam0, cams);
+        std::vector<int> longs;
+        for (size_t i = 0; i + 1 < k.items.size(); i += 2) if (k.items[i + 1] > 1) longs.push_back((int)(i / 2));
+        c->n_long = (int)longs.size();
+        if (c->n_long > 0) up.add(&c->long_items, longs);
         up.add(P_(d.cam_model), model); up.add(P_(d.cam_const), cconst); up.add(P_(d.cam_act), cam_act);
         if (c->dev_packed) {
             d.slot_cam = dres.slot_cam; d.slot_pt = dres.slot_pt; d.slot_campos = dres.slot_campos; d.slot_u = dres.slot_u; d.slot_v = dres.slot_v;
@@ -2534,6 +2562,8 @@ static int create_body(const xrsfm_ba_problem* p, int device, xrsfm_ba_context* 
         c->fused = !(fz && fz[0] == '0');
         const char* pf = std::getenv("XRSFM_BA_PREP_FUSED");
         c->prep_fused = !(pf && pf[0] == '0');
+        const char* bl = std::getenv("XRSFM_BA_BACKSUB_LEAN");        // (read per context: the A/B test switches it inside one process)
+        c->backsub_lean = !(bl && bl[0] == '0');
         const char* pc = std::getenv("XRSFM_BA_PCG_COARSE");
         c->pcg_coarse = !(pc && pc[0] == '0');
     }
@@ -4748,8 +4778,7 @@ int xrsfm_ba_debug_backsub(xrsfm_ba_context* c, double* part_model, double* part
     const int nbi = cdiv(d.n_items, kWavesPerBlock), nbc = cdiv(d.n_cams, kBlock);
     if (nbi + nbc > 0) {
         if (c->wide) hipLaunchKernelGGL(k9_backsub, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, c->w, nbi, c->step_radius);
-        else if (c->step_prep) hipLaunchKernelGGL(k_backsub<true>, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, nbi, (CamLin*)nullptr, c->step_radius);
-        else hipLaunchKernelGGL(k_backsub<false>, dim3(nbi + nbc), dim3(kBlock), 0, c->stream, d, nbi, (CamLin*)nullptr, c->step_radius);
+        else launch_backsub(c, nbi, nbc, nullptr, true);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
