@@ -937,6 +937,13 @@ int xrsfm_ba_debug_backsub(xrsfm_ba_context *ctx, double *part_model, double *pa
 int xrsfm_ba_debug_backsub_layout(xrsfm_ba_context *ctx, int32_t *pt_orig, int32_t *item_tiles, double *campart, int32_t flags[2],
                                   double *cand_intr, double *scale_c, double *scale_p);
 
+/* TEST ENTRY.  counts = {tiles whose camera records k_backsub stages in LDS once per tile, tiles whose lanes gather their camera's
+ * operands themselves}: single-tile Gram items of at most 8 cameras take the first route unless the environment says
+ * XRSFM_BA_CAM_STAGE=0 (read when the context is created); bal9 contexts report {0, 0}.  Counted on the host with the predicate
+ * the kernels evaluate (cam_staged), not by the kernels.  The merged k_schur_pairs launch stages the same tiles; with
+ * XRSFM_BA_GRAM_MERGE=0 there is no merged launch and the S assembly gathers every tile, whatever this entry reports. */
+int xrsfm_ba_debug_cam_stage(xrsfm_ba_context *ctx, int32_t counts[2]);
+
 /* Whether the context currently keeps the per-observation residual and Jacobian stored (1) or recomputes them in the
  * consumers (0, the J-free linearisation of the Cholesky path): after xrsfm_ba_run, the mode its last iterations used. */
 int xrsfm_ba_debug_stored_j(xrsfm_ba_context *ctx, int32_t *stored);

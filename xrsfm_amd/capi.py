@@ -123,6 +123,7 @@ EXPORTS = [
     "xrsfm_ba_two_view_options_default", "xrsfm_ba_two_view_init", "xrsfm_ba_debug_two_view_samples",
     "xrsfm_ba_verify_pairs_options", "xrsfm_ba_verify_pairs", "xrsfm_ba_debug_fund_samples",
     "xrsfm_ba_match_options_default", "xrsfm_ba_match_descriptors", "xrsfm_ba_debug_match_table",
+    "xrsfm_ba_debug_cam_stage",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -210,6 +211,9 @@ def load(path: str | None = None):
     if hasattr(lib, "xrsfm_ba_debug_backsub_layout"):
         lib.xrsfm_ba_debug_backsub_layout.argtypes = [vp, _c_int32_p, _c_int32_p, _c_double_p, _c_int32_p] + [_c_double_p] * 3
         lib.xrsfm_ba_debug_backsub_layout.restype = C.c_int
+    if hasattr(lib, "xrsfm_ba_debug_cam_stage"):       # (absent in a parent build loaded through XRSFM_BA_LIB for an A/B run)
+        lib.xrsfm_ba_debug_cam_stage.argtypes = [vp, _c_int32_p]
+        lib.xrsfm_ba_debug_cam_stage.restype = C.c_int
     lib.xrsfm_ba_debug_set_block_pattern.argtypes = [vp, C.c_int, _c_int32_p]
     lib.xrsfm_ba_debug_set_block_pattern.restype = C.c_int
     lib.xrsfm_pg_default_options.argtypes = [C.POINTER(CPgOptions)]
@@ -585,6 +589,12 @@ class Context:
         check(self.lib.xrsfm_ba_debug_backsub(self._h, *[_dp(out[k]) for k in ("part_model", "part_step2", "cand_points", "point_step",
                                                                                   "cand_cam_q", "cand_cam_t")]), "debug_backsub")
         return out
+
+    def debug_cam_stage(self) -> tuple:
+        """xrsfm_ba_debug_cam_stage: (tiles on the staged route of k_backsub, tiles on the gather route)."""
+        counts = np.zeros(2, np.int32)
+        check(self.lib.xrsfm_ba_debug_cam_stage(self._h, counts.ctypes.data_as(_c_int32_p)), "debug_cam_stage")
+        return int(counts[0]), int(counts[1])
 
     def debug_backsub_layout(self, after_backsub: bool = False, scales: bool = False) -> dict:
         """xrsfm_ba_debug_backsub_layout: pt_orig [n_points_packed], item_tiles [n_items][2] (first tile, tiles), the flags step_prep

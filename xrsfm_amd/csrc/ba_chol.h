@@ -444,6 +444,7 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
             if (b1 > a1 && b1 < C0 && a1 < kGramTabLd) dt1 = src[a1 * C0 + b1];
             if (NIK <= 2 && gram4) g4_se = gram4_sched_load<6>(C0, lane, g4_n);       // (NIK = 0: g4_n = 0 for the tiles that take the 16x16 form)
         }
+        const int run = (MERGED && d.cam_stage) ? d.tile_run[(size_t)it.first_tile * kTileRunLd + min(lane, kTileRunLd - 1)] : 0;     // (staged route, below)
         const SlotCtx s = load_slot(d, it.first_tile, lane);
         const int cp = d.slot_campos_s[s.slot];
         const int cidx_raw = GRAM ? (int)d.slot_cidx[s.slot] : 0;
@@ -463,7 +464,44 @@ void k_schur_pairs(Dev d, const int* __restrict__ item_list, const int* __restri
         {
             double o28[28];
             XBA_STAMP(0, 1);
-            if (s.valid) {
+            // staged route (ba_kernels.h: cam_staged): the tile's camera records — CamLin | CamRec bytes 32..127 (t, pad, intr) | model
+            // word, kSpRecLd doubles each — are copied once into the head of the wave's LDS region, which is not written before `red`
+            // below.  240 bytes: consecutive records start 60 banks apart.  The point and the observation are requested after the
+            // records, not with them: five values held across the staging cost this kernel spilled registers (profiles/r10_cam_stage.md).
+            // Merged launch only: <true, true, 3> spilled with it, and the per-height launches are the XRSFM_BA_GRAM_MERGE=0 oracle.
+            // The two routes below repeat the lines around load_FE_at / load_FE_rc on purpose: with the body written once (a lambda
+            // taking the CamOps, inlined under both branches) <true, true, 0> spilled a register at 128.
+            constexpr int kSpRecLd = 30;
+            const bool staged = MERGED && cam_staged(d.cam_stage, 1, d.tile_ncam[it.first_tile]);        // (wave-uniform)
+            if (staged) {
+                const int C0 = d.tile_ncam[it.first_tile];
+                const int camL = stage_tile_cam(C0, run, s.cam, lane);
+                const int model = d.cam_model[camL];
+                CamStage st;
+                st.request(C0, camL, lane, {d.camrec, 128u, 0u, 8}, {d.cam, 128u, 32u, 6});
+                st.deposit(smem, kSpRecLd);
+                *reinterpret_cast<int*>(smem + min(lane, C0 - 1) * kSpRecLd + 28) = model;
+                stage_done();
+            }
+            if (staged && s.valid) {
+                double hcv[6], gv[3];
+                {
+                    const double* hc = (PREP ? d.Hpp : d.Hc) + 6 * (size_t)s.pt;
+                    const double* g = d.gp + 3 * (size_t)s.pt;
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) hcv[k] = hc[k];
+                    gv[0] = g[0]; gv[1] = g[1]; gv[2] = g[2];
+                }
+                double F[12], E[6], r0, r1;
+                const double* r = smem + cidx_raw * kSpRecLd;
+                const CamOps o = {r, r + 16, r + 20, nullptr, reinterpret_cast<const int*>(r + 28), d.slot_u + s.slot, d.slot_v + s.slot};
+                load_FE_at(d, s.slot, s.pt, o, d.P + 3 * (size_t)s.pt, F, E, r0, r1);
+                if (PREP) { double hf[6]; point_factor(hcv, radius, hf);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) hcv[k] = hf[k]; }
+                pairs_V<PREP>(F, E, hcv, V);
+                pairs_diag<PREP>(F, V, hcv, gv, o28);
+            } else if (s.valid) {
                 // the point's factor of Hinv and gradient are requested with the Jacobian records (left where they are used, the
                 // compiler issues them after the first batch of loads has returned: one more memory round trip per tile)
                 double hcv[6], gv[3];

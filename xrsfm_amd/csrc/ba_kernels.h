@@ -49,6 +49,8 @@ static_assert(sizeof(CamLin) == 128, "CamLin must be 128 bytes");
 
 struct Dev {
     int n_cams, n_pts, n_tiles, n_slots, n_items;
+    int cam_stage;            // != 0: k_backsub and the merged k_schur_pairs launch copy a tile's camera records into LDS once
+                              // (cam_staged below); XRSFM_BA_CAM_STAGE=0: every lane gathers its camera's operands, as before
     // per slot
     const int* slot_cam; const int* slot_pt; const int* slot_campos;
     const double* slot_u; const double* slot_v;
@@ -321,6 +323,53 @@ __device__ __forceinline__ SlotCtx load_slot(const Dev& d, int tile, int lane) {
 }
 
 
+// ---- camera records of a tile, staged in LDS (XRSFM_BA_CAM_STAGE=0: every tile gathers)
+// A Gram tile has C distinct cameras (2-4 in a sequential map, 5-8 with missed detections) and up to 64 lanes that each gathered
+// their camera's ~33 doubles from four arrays: the same 2-8 records 8-32 times over, each piece a round trip that the compiler
+// sinks into the branch that first needs it.  On the staged route the wave copies the C records into its own LDS once — 16 lanes
+// per camera, 16 bytes per lane, one wave-wide request per 4 cameras, plus what a record has beyond 16 pieces from the lanes
+// 0..C-1 — next to the requests for the per-slot and per-point operands, and every lane reads its camera's operands from LDS
+// where it needs them.  All 64 lanes request and deposit (lanes past the last camera or piece repeat the last: the same bytes to
+// the same place), so the staging is straight-line code.
+constexpr int kCamStageMax = 8;           // C <= 8 takes the staged route; 9-10 cameras, non-Gram tiles and long items gather
+__host__ __device__ inline bool cam_staged(int on, int n_tiles, int C) { return on && n_tiles == 1 && C > 0 && C <= kCamStageMax; }
+
+// Camera min(lane, C - 1) of the tile: the one of its run's first lane.  run: the tile's tile_run entry of camera
+// min(lane, kTileRunLd - 1) (requested with the slot record); cam: the lane's slot_cam.
+__device__ __forceinline__ int stage_tile_cam(int C, int run, int cam, int lane) {
+    return __shfl(cam, (__shfl(run, min(lane, C - 1), kWave) >> 16) & 63, kWave);
+}
+// One per-camera array a record takes pieces from: record stride and first byte taken, number of 16-byte pieces.
+struct StagePart { const void* base; unsigned stride, first; int n; };
+// The pieces of up to three arrays, in order, become the first doubles of the record: 2 per piece, at most 16 pieces.
+struct CamStage {
+    static constexpr int kPass = kCamStageMax / 4;      // both passes always: with C <= 4 the second repeats camera C - 1
+    int p, ci[kPass];
+    double2 x[kPass];
+    __device__ __forceinline__ void request(int C, int camL, int lane, const StagePart a, const StagePart b, const StagePart c = {nullptr, 0u, 0u, 0}) {
+        p = min(lane & 15, a.n + b.n + c.n - 1);
+        const unsigned char* base = static_cast<const unsigned char*>(a.base);          // (selects, no branches)
+        unsigned stride = a.stride, piece = a.first + 16u * p;
+        if (p >= a.n) { base = static_cast<const unsigned char*>(b.base); stride = b.stride; piece = b.first + 16u * (p - a.n); }
+        if (c.n > 0 && p >= a.n + b.n) { base = static_cast<const unsigned char*>(c.base); stride = c.stride; piece = c.first + 16u * (p - a.n - b.n); }
+#pragma unroll
+        for (int k = 0; k < kPass; ++k) {
+            ci[k] = min(4 * k + (lane >> 4), C - 1);
+            // (24-bit multiply, 32-bit byte offset: a v_mad_u32_u24 — camera ids below 2^24, which xrsfm_ba_create requires of a context that stages)
+            x[k] = *reinterpret_cast<const double2*>(base + (__umul24((unsigned)__shfl(camL, ci[k], kWave), stride) + piece));
+        }
+    }
+    __device__ __forceinline__ void deposit(double* rec, int ld) const {       // rec: the wave's [kCamStageMax][ld], 16-byte aligned rows
+#pragma unroll
+        for (int k = 0; k < kPass; ++k) *reinterpret_cast<double2*>(rec + ci[k] * ld + 2 * p) = x[k];
+    }
+};
+__device__ __forceinline__ void stage_done() {          // the deposits have landed before any lane reads
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+}
+
+
 // Residual of one observation, robustified: pr (projection and d r / d Pc), rho and sw = sqrt(rho').  The one place that
 // evaluates it for the linearisation: k_linearize and the consumers that recompute what it no longer stores (obs_rj).
 __device__ __forceinline__ void robust_obs(const double (&M)[9], const double t[3], const double* intr, int model, const double Pw[3],
@@ -334,19 +383,25 @@ __device__ __forceinline__ void robust_obs(const double (&M)[9], const double t[
 // What k_linearize stores in rt / Jp for one observation, recomputed at the current state: r = sw r, j = sw d r / d Pc.
 // M: the camera's CamLin::M (quat_to_mat of the same q k_linearize converts).  The outputs leave through an empty asm, so
 // the arithmetic that consumes them is contracted exactly as it is on a loaded value (bit-identical to the stored path).
-__device__ __forceinline__ void obs_rj(const Dev& d, int slot, int cam, const double (&M)[9], const double Pw[3],
-                                       double& r0, double& r1, double (&j)[6]) {
-    const CamRec& c = d.cam[cam];
-    const double t[3] = {c.t[0], c.t[1], c.t[2]};
+// obs_rj_at: the camera's t, intr and model and the observation by address — CamRec in HBM, or the wave's copy of the tile's camera records
+// in LDS (k_backsub's staged route).
+__device__ __forceinline__ void obs_rj_at(const double* tp, const double* intr, const int* model, const double* u, const double* v, double huber_a,
+                                          const double (&M)[9], const double Pw[3], double& r0, double& r1, double (&j)[6]) {
+    const double t[3] = {tp[0], tp[1], tp[2]};
     Proj pr;
     double rho, sw;
-    robust_obs(M, t, c.intr, d.cam_model[cam], Pw, d.slot_u[slot], d.slot_v[slot], d.huber_a, pr, rho, sw);
+    robust_obs(M, t, intr, *model, Pw, *u, *v, huber_a, pr, rho, sw);
     r0 = pr.r0 * sw; r1 = pr.r1 * sw;
 #pragma unroll
     for (int k = 0; k < 6; ++k) j[k] = pr.jp[k] * sw;
     asm("" : "+v"(r0), "+v"(r1));
 #pragma unroll
     for (int k = 0; k < 6; ++k) asm("" : "+v"(j[k]));
+}
+__device__ __forceinline__ void obs_rj(const Dev& d, int slot, int cam, const double (&M)[9], const double Pw[3],
+                                       double& r0, double& r1, double (&j)[6]) {
+    const CamRec& c = d.cam[cam];
+    obs_rj_at(c.t, c.intr, d.cam_model + cam, d.slot_u + slot, d.slot_v + slot, d.huber_a, M, Pw, r0, r1, j);
 }
 
 // Rebuild the Jacobi-scaled, robustified blocks of one observation:
@@ -388,15 +443,27 @@ __device__ __forceinline__ void load_FE(const Dev& d, int slot, int cam, int pt,
     fe_from_j(d, c, M, pt, P[0], P[1], P[2], j, F, E);
 }
 
+// The camera's operands of one observation's recomputation, by address (CamOps): gathered from HBM by every lane, or read from
+// the wave's LDS copy of the tile's camera records (the staged routes of k_backsub and k_schur_pairs).  The arithmetic is
+// written once, for both.
+struct CamOps {
+    const double* lin;      // CamLin as 15 doubles: M[9], sq[3], st[3]
+    const double* t;        // CamRec::t
+    const double* intr;     // CamRec::intr
+    const double* y;        // the camera's step, px[6] (k_backsub)
+    const int* model;
+    const double* u; const double* v;       // the observation (per slot, not per camera: it travels with them to where obs_rj_at reads it)
+};
+
 // F / E and the robustified residual r of one observation: from rt / Jp when they are stored, recomputed from the state and
-// uv otherwise (d.Jp == nullptr, a wave-uniform test).  The same F / E arithmetic either way (fe_from_j).
-__device__ __forceinline__ void load_FE_rc(const Dev& d, int slot, int cam, int pt, double (&F)[12], double (&E)[6], double& r0, double& r1) {
+// uv otherwise (d.Jp == nullptr, a wave-uniform test).  The same F / E arithmetic either way (fe_from_j).  P: the point.
+__device__ __forceinline__ void load_FE_at(const Dev& d, int slot, int pt, const CamOps& o, const double* P, double (&F)[12], double (&E)[6],
+                                           double& r0, double& r1) {
     const size_t ns = (size_t)d.n_slots;
-    const CamLin& c = d.camrec[cam];
+    const CamLin& c = *reinterpret_cast<const CamLin*>(o.lin);
     double M[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) M[k] = c.M[k];
-    const double* P = d.P + 3 * (size_t)pt;
     const double Pw[3] = {P[0], P[1], P[2]};
     double j[6];
     if (d.Jp) {
@@ -404,9 +471,14 @@ __device__ __forceinline__ void load_FE_rc(const Dev& d, int slot, int cam, int 
         for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
         r0 = d.rt[slot]; r1 = d.rt[ns + slot];
     } else {
-        obs_rj(d, slot, cam, M, Pw, r0, r1, j);
+        obs_rj_at(o.t, o.intr, o.model, o.u, o.v, d.huber_a, M, Pw, r0, r1, j);
     }
     fe_from_j(d, c, M, pt, Pw[0], Pw[1], Pw[2], j, F, E);
+}
+__device__ __forceinline__ void load_FE_rc(const Dev& d, int slot, int cam, int pt, double (&F)[12], double (&E)[6], double& r0, double& r1) {
+    const CamRec& c = d.cam[cam];
+    const CamOps o = {reinterpret_cast<const double*>(d.camrec + cam), c.t, c.intr, nullptr, d.cam_model + cam, d.slot_u + slot, d.slot_v + slot};
+    load_FE_at(d, slot, pt, o, d.P + 3 * (size_t)pt, F, E, r0, r1);
 }
 
 // Per-camera linearisation record (run before every linearisation: cameras, scales and masks as they are now).
@@ -1691,7 +1763,6 @@ __device__ __forceinline__ void backsub_long_item(const Dev& d, const Item it, i
 #define XBA_BACKSUB_LEAN_WAVES 5
 #endif
 constexpr int kBsLdsH = 16 * kWave, kBsLdsW = 4 * kWave;              // one direct-to-LDS load of the wave: 16 / 4 bytes per lane
-constexpr int kBsLdsWave = 4 * kBsLdsH + 2 * kBsLdsW;                 // 4608 bytes per wave
 
 // A sum of two products can be contracted around either product, and which one the compiler rounds first depends on the code
 // around it.  k_backsub rounds the product that went through rounded() first and fuses the other, which is what the compiler makes
@@ -1701,25 +1772,27 @@ __device__ __forceinline__ double rounded(double x) { asm("" : "+v"(x)); return 
 // v = F y, E and the robustified residual of one observation: load_FE_rc and the sums over F of its callers, with F never held
 // as a whole.  Pw: the point; sp, mp: its Jacobi scale and variable mask, multiplied into spm (fe_from_j's sp0..2) where E needs
 // them — next to the loads of the camera's scales and step, not across the projection.
-__device__ __forceinline__ void load_vE_rc(const Dev& d, int slot, int cam, const double (&Pw)[3], const double* __restrict__ sp, double mp,
+__device__ __forceinline__ void load_vE_rc(const Dev& d, int slot, const CamOps& c, const double (&Pw)[3],
+                                           const double* __restrict__ sp, double mp,
                                            double (&spm)[3], double (&E)[6], double& v0, double& v1, double& r0, double& r1) {
     const size_t ns = (size_t)d.n_slots;
-    const CamLin& c = d.camrec[cam];
+    const double* sq = c.lin + 9;
+    const double* st = c.lin + 12;
     double M[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) M[k] = c.M[k];
+    for (int k = 0; k < 9; ++k) M[k] = c.lin[k];
     double j[6];
     if (d.Jp) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) j[k] = d.Jp[k * ns + slot];
         r0 = d.rt[slot]; r1 = d.rt[ns + slot];
     } else {
-        obs_rj(d, slot, cam, M, Pw, r0, r1, j);
+        obs_rj_at(c.t, c.intr, c.model, c.u, c.v, d.huber_a, M, Pw, r0, r1, j);
     }
     const double rp0 = M[0] * Pw[0] + M[1] * Pw[1] + M[2] * Pw[2];
     const double rp1 = M[3] * Pw[0] + M[4] * Pw[1] + M[5] * Pw[2];
     const double rp2 = M[6] * Pw[0] + M[7] * Pw[1] + M[8] * Pw[2];
-    const double* y = d.px + 6 * (size_t)cam;
+    const double* y = c.y;
 #pragma unroll
     for (int k = 0; k < 3; ++k) spm[k] = sp[k] * mp;
     double v[2];
@@ -1727,18 +1800,37 @@ __device__ __forceinline__ void load_vE_rc(const Dev& d, int slot, int cam, cons
     for (int row = 0; row < 2; ++row) {
         const double a = j[3 * row], b = j[3 * row + 1], cc = j[3 * row + 2];
         double vr = 0.0;
-        vr += -2.0 * (b * rp2 - cc * rp1) * c.sq[0] * y[0];
-        vr += -2.0 * (cc * rp0 - a * rp2) * c.sq[1] * y[1];
-        vr += -2.0 * (a * rp1 - b * rp0) * c.sq[2] * y[2];
-        vr += a * c.st[0] * y[3];
-        vr += b * c.st[1] * y[4];
-        vr += cc * c.st[2] * y[5];
+        vr += -2.0 * (b * rp2 - cc * rp1) * sq[0] * y[0];
+        vr += -2.0 * (cc * rp0 - a * rp2) * sq[1] * y[1];
+        vr += -2.0 * (a * rp1 - b * rp0) * sq[2] * y[2];
+        vr += a * st[0] * y[3];
+        vr += b * st[1] * y[4];
+        vr += cc * st[2] * y[5];
         v[row] = vr;
         E[3 * row + 0] = (a * M[0] + b * M[3] + cc * M[6]) * spm[0];
         E[3 * row + 1] = (a * M[1] + b * M[4] + cc * M[7]) * spm[1];
         E[3 * row + 2] = (a * M[2] + b * M[5] + cc * M[8]) * spm[2];
     }
     v0 = v[0]; v1 = v[1];
+}
+
+// k_backsub's camera record in LDS (kBsRecLd doubles): [0,16) CamLin | [16,28) CamRec bytes 32..127 (t, pad, intr) | [28,34) px |
+// [34] model word.  288 bytes: consecutive records start 8 banks apart, so the lanes' reads of the same piece of 2-8 records
+// do not collide.
+constexpr int kBsRecLd = 36;
+constexpr int kBsLdsHead = 4 * kBsLdsH + 2 * kBsLdsW;                 // the head lanes' Hpp / g_p: 4608 bytes per wave
+constexpr int kBsLdsWave = kBsLdsHead + kCamStageMax * kBsRecLd * 8;    // ... and the tile's camera records behind them: 6912
+__device__ __forceinline__ void backsub_stage_cams(const Dev& d, int C, int run, int cam, int lane, double* rec) {
+    const int cl = min(lane, C - 1);
+    const int camL = stage_tile_cam(C, run, cam, lane);
+    const double2 y45 = *reinterpret_cast<const double2*>(d.px + 6 * (size_t)camL + 4);
+    const int model = d.cam_model[camL];
+    CamStage st;
+    st.request(C, camL, lane, {d.camrec, 128u, 0u, 8}, {d.cam, 128u, 32u, 6}, {d.px, 48u, 0u, 2});
+    st.deposit(rec, kBsRecLd);
+    *reinterpret_cast<double2*>(rec + cl * kBsRecLd + 32) = y45;
+    *reinterpret_cast<int*>(rec + cl * kBsRecLd + 34) = model;
+    stage_done();
 }
 
 template <bool PREP, bool YP>
@@ -1758,9 +1850,10 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
     if (item >= d.n_items) return;
     const Item it = d.items[item];
     if (it.n_tiles != 1) return;                                             // k_backsub_long
+    const int run = d.cam_stage ? d.tile_run[(size_t)it.first_tile * kTileRunLd + min(lane, kTileRunLd - 1)] : 0;     // (requested with the slot record)
     const SlotCtx s = load_slot(d, it.first_tile, lane);
     const int maxlen = d.tile_maxlen[it.first_tile];
-    // the wave's own 4.5 KB: [3][64] x 16 B of Hpp, [64] x 16 B + [2][64] x 4 B of g_p, lane-linear (the hardware adds lane x size
+    // the wave's own 6.75 KB: the tile's camera records (staged route) behind the head lanes' 4.5 KB: [3][64] x 16 B of Hpp, [64] x 16 B + [2][64] x 4 B of g_p, lane-linear (the hardware adds lane x size
     // to the wave-uniform base it is given, for the lanes that are on).  One tile per wave and no other use of this memory: nothing to wait for before the request.
     unsigned char* const lw = hg + wave * kBsLdsWave;
     if (s.head) {
@@ -1780,13 +1873,41 @@ void k_backsub(Dev d, int n_item_blocks, CamLin* __restrict__ camrec_cand, doubl
     // recomputation and for the head lane's update
     double spm[3], Pv[3];
     bool var = false;
-    if (s.valid) {
+    const int C = d.tile_ncam[it.first_tile];
+    if (cam_staged(d.cam_stage, 1, C)) {                                     // (wave-uniform)
+        // staged route: the per-slot and per-point operands are requested first, the tile's camera records behind them, all in
+        // one round trip; the lanes then read their camera's operands from the wave's LDS copy
+        double* const rec = reinterpret_cast<double*>(lw + kBsLdsHead);
+        double uo, vo;
+        int cidx = 0, fixed = 0;                                             // (bytes as loaded: nothing waits for them before the records are requested)
+        if (s.valid) {
+            const double* P = d.P + 3 * (size_t)s.pt;
+            fixed = d.pt_const[s.pt];
+            cidx = d.slot_cidx[s.slot];
+            uo = d.slot_u[s.slot]; vo = d.slot_v[s.slot];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) Pv[k] = P[k];
+        } else { dead_values(Pv); XBA_DEAD_VALUE(uo); XBA_DEAD_VALUE(vo); }
+        backsub_stage_cams(d, C, run, s.cam, lane, rec);
+        asm volatile("" : "+v"(cidx), "+v"(fixed));                        // first looked at here: no wait for them among the requests above
+        var = s.valid && !fixed;
+        if (s.valid) {
+            const double* r = rec + cidx * kBsRecLd;
+            const CamOps ops = {r, r + 16, r + 20, r + 28, reinterpret_cast<const int*>(r + 34), &uo, &vo};
+            load_vE_rc(d, s.slot, ops, Pv, d.scale_p + 3 * (size_t)s.pt, var ? 1.0 : 0.0, spm, E, v0, v1, r0, r1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[k] = rounded(E[k] * v0) + E[3 + k] * v1;
+        } else { dead_values(spm); dead_values(E); XBA_DEAD_VALUE(v0); XBA_DEAD_VALUE(v1); XBA_DEAD_VALUE(r0); XBA_DEAD_VALUE(r1); }
+    } else if (s.valid) {
         const double* P = d.P + 3 * (size_t)s.pt;
         var = !d.pt_const[s.pt];
         const double mp = var ? 1.0 : 0.0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) Pv[k] = P[k];
-        load_vE_rc(d, s.slot, s.cam, Pv, d.scale_p + 3 * (size_t)s.pt, mp, spm, E, v0, v1, r0, r1);
+        const CamRec& cr = d.cam[s.cam];
+        const CamOps ops = {reinterpret_cast<const double*>(d.camrec + s.cam), cr.t, cr.intr, d.px + 6 * (size_t)s.cam, d.cam_model + s.cam,
+                            d.slot_u + s.slot, d.slot_v + s.slot};
+        load_vE_rc(d, s.slot, ops, Pv, d.scale_p + 3 * (size_t)s.pt, mp, spm, E, v0, v1, r0, r1);
 #pragma unroll
         for (int k = 0; k < 3; ++k) w[k] = rounded(E[k] * v0) + E[3 + k] * v1;
     } else { dead_values(spm); dead_values(Pv); dead_values(E); XBA_DEAD_VALUE(v0); XBA_DEAD_VALUE(v1); XBA_DEAD_VALUE(r0); XBA_DEAD_VALUE(r1); }

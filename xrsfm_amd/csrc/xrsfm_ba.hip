@@ -2564,6 +2564,8 @@ static int create_body(const xrsfm_ba_problem* p, int device, xrsfm_ba_context* 
         c->prep_fused = !(pf && pf[0] == '0');
         const char* bl = std::getenv("XRSFM_BA_BACKSUB_LEAN");        // (read per context: the A/B test switches it inside one process)
         c->backsub_lean = !(bl && bl[0] == '0');
+        const char* cs = std::getenv("XRSFM_BA_CAM_STAGE");           // (per context too: tests/test_gpu_cam_stage.py)
+        d.cam_stage = !(cs && cs[0] == '0') && d.n_cams < (1 << 24);      // (the staging forms 32-bit record offsets with a 24-bit multiply)
         const char* pc = std::getenv("XRSFM_BA_PCG_COARSE");
         c->pcg_coarse = !(pc && pc[0] == '0');
     }
@@ -4829,6 +4831,25 @@ int xrsfm_ba_debug_backsub_layout(xrsfm_ba_context* c, int32_t* pt_orig, int32_t
         }
     }
     return 0;
+}
+
+// Which route the tiles of the context take through k_backsub and the merged k_schur_pairs launch (cam_staged,
+// ba_kernels.h: the predicate the kernels evaluate).
+int xrsfm_ba_debug_cam_stage(xrsfm_ba_context* c, int32_t counts[2]) {
+    if (c && c->poisoned) return XRSFM_BA_ESTATE;
+    if (!c || !counts) return XRSFM_BA_EINVAL;
+    counts[0] = counts[1] = 0;
+    if (c->wide) return 0;                                  // bal9 contexts run k9_backsub: no tile on either route
+    return no_throw([&]() -> int {
+        if (int e = ensure_host_pack(c, 1)) return e;
+        const Packed& k = c->pk;
+        for (size_t i = 0; i + 1 < k.items.size(); i += 2) {
+            const int first = k.items[i], n = k.items[i + 1];
+            if (cam_staged(c->d.cam_stage, n, k.tile_ncam[first])) counts[0] += 1;
+            else counts[1] += n;
+        }
+        return 0;
+    });
 }
 
 // Device-side packing against the host's (ba_pack_dev.h / ba_pack.h): packs `p` both ways and compares every array.
