@@ -13,6 +13,7 @@
 #pragma once
 #include "ba_kernels.h"
 #include "ba_pack.h"
+#include "ba_plan.h"
 
 namespace xba {
 
@@ -793,6 +794,94 @@ __device__ __forceinline__ void compose_tile(const CholDev& c, const Dev& d, con
     __syncthreads();
 }
 
+// Gather form of compose_tile (ba_plan.h: FillRec / TileDesc; XRSFM_BA_CHAIN_DESC): where a value comes from and where it goes is
+// resolved per set-up, so a tile costs record range -> records -> values instead of tiles / tptr -> tent -> blk_rc -> cam_off ->
+// values.  The values are formed by the very expressions of compose_tile (every element of a tile has one writer: same bits).
+// Requests and LDS writes are apart, so that a caller can have the loads of two tiles in flight before its first barrier.
+struct FillRecs { const FillRec* rec; const double* Sblk; double radius; };      // radius: as FillLists
+constexpr int kGatherU = 4;        // elements per thread and request: 4 x 256 = the 28 blocks most tiles stay within
+struct GatherBatch { int pk[kGatherU]; double v[kGatherU]; };      // pk: FillRec::pk | element of the block << 20, -1 none
+// off-diagonal blocks: elements w0 + 256 u of the n36 = 36 x records values of the records from q0 on
+__device__ __forceinline__ void gather_request(GatherBatch& g, const FillRecs& f, int q0, int n36, int w0) {
+    FillRec r[kGatherU];
+#pragma unroll
+    for (int u = 0; u < kGatherU; ++u) {
+        const int w = w0 + 256 * u;
+        r[u] = w < n36 ? f.rec[q0 + w / 36] : FillRec{0, 0};
+    }
+#pragma unroll
+    for (int u = 0; u < kGatherU; ++u) {
+        const int w = w0 + 256 * u, e = w % 36;
+        g.pk[u] = w < n36 ? (r[u].pk | (e << 20)) : -1;
+        g.v[u] = w < n36 ? -f.Sblk[36 * (size_t)r[u].id + e] : 0.0;
+    }
+}
+template <int LD>
+__device__ __forceinline__ void gather_write(const GatherBatch& g, double* A) {
+#pragma unroll
+    for (int u = 0; u < kGatherU; ++u) {
+        const int pk = g.pk[u];
+        if (pk < 0) continue;
+        const int e = pk >> 20, r = e / 6, col = e % 6, orow = pk & 63, ocol = (pk >> 8) & 63;
+        if (pk & kFillTransposed) A[(ocol + col) * LD + orow + r] = g.v[u];
+        else A[(orow + r) * LD + ocol + col] = g.v[u];
+    }
+}
+// diagonal blocks of a diagonal tile (its first nd records): thread t holds element t % 21 of the packed upper triangle of camera
+// t / 21 of the tile — one request covers the ten cameras — and, for the first six, the camera's right-hand-side row
+static_assert(21 * kCamsPerTileDev <= 256, "one thread per upper-triangle element of a tile's diagonal blocks");
+struct DiagReq { int o, p; double v, dl, g, s21; };      // o: the camera's first row in the tile, -1 none
+__device__ __forceinline__ int packed_row(int p) { return (p >= 6) + (p >= 11) + (p >= 15) + (p >= 18) + (p >= 20); }
+__device__ __forceinline__ void diag_request(DiagReq& q, const FillRecs& f, const Dev& d, int q0, int nd, bool want_rhs) {
+    const int t = threadIdx.x;
+    q.o = -1; q.p = 0; q.v = 0.0; q.dl = 0.0; q.g = 0.0; q.s21 = 0.0;
+    if (t >= 21 * nd) return;
+    const FillRec rc = f.rec[q0 + t / 21];
+    const int cam = rc.id, p = t % 21, r = packed_row(p);
+    const double* S = d.camS + 28 * (size_t)cam;
+    q.o = rc.pk & 63; q.p = p;
+    q.v = S[p];
+    if (p == 6 * r - r * (r - 1) / 2) q.dl = f.radius > 0.0 ? d.camlin[12 * (size_t)cam + r] : d.Dc2[6 * (size_t)cam + r];
+    if (want_rhs && p < 6) { q.g = d.camlin[12 * (size_t)cam + 6 + p]; q.s21 = S[21 + p]; }
+}
+template <int LD>
+__device__ __forceinline__ void diag_write(const DiagReq& q, const FillRecs& f, double* A, double* rl) {
+    if (q.o < 0) return;
+    const int r = packed_row(q.p), col = q.p - (6 * r - r * (r - 1) / 2) + r;
+    double v = q.v;
+    if (r == col) v += f.radius > 0.0 ? clampd(q.dl, kLmDiagMin, kLmDiagMax) / f.radius : q.dl;
+    A[(q.o + col) * LD + q.o + r] = v;
+    if (rl && q.p < 6) rl[q.o + q.p] = q.g + q.s21;
+}
+// the records of a tile beyond the first request of every thread (tiles of more than 28 blocks)
+template <int LD>
+__device__ __forceinline__ void gather_rest(const FillRecs& f, int q0, int n36, double* A) {
+    for (int w0 = threadIdx.x + 256 * kGatherU; w0 < n36; w0 += 256 * kGatherU) {
+        GatherBatch g;
+        gather_request(g, f, q0, n36, w0);
+        gather_write<LD>(g, A);
+    }
+}
+// compose_tile from the records of tile td.  Called by all 256 threads; ends with a barrier.
+template <int LD>
+__device__ __forceinline__ void compose_tile_rec(const TileDesc& td, const Dev& d, const FillRecs& f, double* A, double* rl) {
+    const int t = threadIdx.x;
+    DiagReq dq; GatherBatch g;
+    const int q0 = td.q0 + td.nd, n36 = (td.q1 - q0) * 36;
+    diag_request(dq, f, d, td.q0, td.nd, rl != nullptr);
+    gather_request(g, f, q0, n36, t);
+    for (int e = t; e < kNB * kNB; e += 256) {          // (off-diagonal tile: nrows = 64)
+        const int r = e >> 6, col = e & 63;
+        A[r * LD + col] = (r == col && r >= td.nrows) ? 1.0 : 0.0;
+    }
+    if (rl && t < kNB) rl[t] = 0.0;
+    __syncthreads();
+    diag_write<LD>(dq, f, A, rl);
+    gather_write<LD>(g, A);
+    gather_rest<LD>(f, q0, n36, A);
+    __syncthreads();
+}
+
 // list (or nullptr = every tile): the tiles to compose — the tiles outside the first level's columns when there are thousands of
 // them (k_lv_factor<true> composes them in trailing workgroups otherwise, but holds one workgroup per CU: 40 000 tiles of a
 // dissected photo collection took 2.1 ms there)
@@ -812,6 +901,20 @@ __global__ __launch_bounds__(256) void k_tile_fill(CholDev c, Dev d, const int* 
         base[(size_t)r * c.ld + col] = A[r * (kNB + 1) + col];
     }
     if (ti == tj && t < kNB) c.rhs[ti * kNB + t] = rl[t];
+}
+// ... from gather records
+__global__ __launch_bounds__(256) void k_tile_fill_rec(CholDev c, Dev d, const TileDesc* __restrict__ tdesc, FillRecs f, const int* __restrict__ list = nullptr) {
+    __shared__ double A[kNB * (kNB + 1)];
+    __shared__ double rl[kNB];
+    const TileDesc td = tdesc[list ? list[blockIdx.x] : (int)blockIdx.x];
+    const int t = threadIdx.x;
+    compose_tile_rec<kNB + 1>(td, d, f, A, rl);
+    double* base = c.S + (size_t)td.off64 * kNB;
+    for (int e = t; e < kNB * kNB; e += 256) {
+        const int r = e >> 6, col = e & 63;
+        base[(size_t)r * c.ld + col] = A[r * (kNB + 1) + col];
+    }
+    if (td.ti == td.tj && t < kNB) c.rhs[td.ti * kNB + t] = rl[t];
 }
 
 // the solution back in camera order
@@ -1705,10 +1808,13 @@ __global__ __launch_bounds__(256) void k_ll_update_reduce(CholDev c, const int* 
 // FILL (first level of the tree; its lists are empty): the tiles are not read from S but composed here from the block values
 // (what k_tile_fill does: one launch and a global round trip of every level-0 tile less per LM iteration; a single-tile
 // system — LBA-sized calls — has no fill launch at all); workgroups >= n_factor compose the tiles of the other columns.
-struct LvFill { Dev d; FillLists f; const int* fz_q; const int* rest; int n_factor; };
+struct LvFill { Dev d; FillLists f; const int* fz_q; const int* rest; int n_factor;
+                // DESC (XRSFM_BA_CHAIN_DESC; ba_plan.h: ChainDesc): one record per workgroup instead of tiles / dptr / fz_q / tile_rows / the tile
+                // map and the first list entries, gather records instead of the fill lists
+                FillRecs g; const TileDesc* tdesc; const TileDesc* fz_fill; const FzDesc* fzd; };
 // late / Ql (look-ahead schedule, else nullptr): per entry the partial slots of (k,k) and (i,k) whose tiles the accumulators start
 // from (the contribution of column k-2, formed by the previous launch), -1 none.
-template <bool FILL>
+template <bool FILL, bool DESC = false>
 __device__ __forceinline__ void lv_factor_body(const CholDev& c, const int b, const int* __restrict__ tiles, const int* __restrict__ dptr,
                                                const int* __restrict__ dj, const int* __restrict__ tile_cam, double* __restrict__ px,
                                                const LvFill& lf, double (*A)[kLdT], double (*Li)[kLdT], double (*Xs)[kLdT], double (*Tb)[16][17],
@@ -1717,6 +1823,17 @@ __device__ __forceinline__ void lv_factor_body(const CholDev& c, const int b, co
     // there while the pivot tile is factored (it used to stay in 64 registers across potrf_lds: with them the in-register 16x16
     // factorisation ran out of architectural VGPRs and copied every broadcast value through AGPRs — 4 of its 8 instructions per column
     // update; 109 KB of LDS = one workgroup per CU, the grid of a level has <= 1 per CU anyway)
+    if (FILL && DESC && b >= lf.n_factor) {
+        const TileDesc td = lf.tdesc[lf.rest[b - lf.n_factor]];
+        compose_tile_rec<kLdT>(td, lf.d, lf.g, &A[0][0], yv);
+        double* base = c.S + (size_t)td.off64 * kNB;
+        for (int e = threadIdx.x; e < kNB * kNB; e += 256) {
+            const int r = e >> 6, col = e & 63;
+            base[(size_t)r * c.ld + col] = A[r][col];
+        }
+        if (td.ti == td.tj && threadIdx.x < kNB) c.rhs[td.ti * kNB + threadIdx.x] = yv[threadIdx.x];
+        return;
+    }
     if (FILL && b >= lf.n_factor) {        // a tile of a later column: compose and store (k_tile_fill)
         const int q = lf.rest[b - lf.n_factor];
         const int ti = lf.f.tiles[2 * q], tj = lf.f.tiles[2 * q + 1];
@@ -1729,20 +1846,54 @@ __device__ __forceinline__ void lv_factor_body(const CholDev& c, const int b, co
         if (ti == tj && threadIdx.x < kNB) c.rhs[ti * kNB + threadIdx.x] = yv[threadIdx.x];
         return;
     }
-    const int i = tiles[2 * b], k = tiles[2 * b + 1];
+    // DESC: everything below comes from one record (a wave-uniform wide load), requested at the first instruction
+    TileDesc tk{}, to{}; FzDesc fz{};
+    if (DESC && FILL) { tk = lf.fz_fill[2 * b]; to = lf.fz_fill[2 * b + 1]; }
+    else if (DESC) fz = lf.fzd[b];
+    const int i = DESC ? (FILL ? to.ti : fz.i) : tiles[2 * b], k = DESC ? (FILL ? to.tj : fz.k) : tiles[2 * b + 1];
     const bool diag = (i == k);
     XBA_STAMP(1, 0);
-    const int nb = (c.tile_rows[k] + 15) >> 4;
+    const int nb = DESC ? (FILL ? (tk.nrows + 15) >> 4 : fz.nb) : (c.tile_rows[k] + 15) >> 4;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int r0 = (wave >> 1) * 32, c0 = (wave & 1) * 32;
     const int o = t >> 2, part = t & 3;
     const size_t ld = c.ld;
-    const double* Skk = tile_ptr(c, k, k);
-    double* Sik = tile_ptr(c, i, k);
+    const double* Skk = DESC ? c.S + (size_t)(FILL ? tk.off64 : fz.kk) * kNB : tile_ptr(c, k, k);
+    double* Sik = DESC ? c.S + (size_t)(FILL ? to.off64 : fz.ik) * kNB : tile_ptr(c, i, k);
     // the assembled tiles, in the accumulator layout of tile_abt_mfma (requested now, used after the update phase)
     v4d skk[2][2], sik[2][2], akk[2][2], aik[2][2];
-    if (FILL) {
+    if (FILL && DESC) {
+        // both tiles at once: their records and values are requested before the first barrier, the two LDS images (own tile in
+        // Li's storage, pivot tile in A) are zero-filled while the loads are in flight
+        DiagReq dq; GatherBatch gk, gi;
+        const int qk = tk.q0 + tk.nd, nk36 = (tk.q1 - qk) * 36, ni36 = diag ? 0 : (to.q1 - to.q0) * 36;
+        diag_request(dq, lf.g, lf.d, tk.q0, tk.nd, true);
+        gather_request(gk, lf.g, qk, nk36, t);
+        gather_request(gi, lf.g, to.q0, ni36, t);
+        for (int e = t; e < kNB * kNB; e += 256) {
+            const int r = e >> 6, col = e & 63;
+            A[r][col] = (r == col && r >= tk.nrows) ? 1.0 : 0.0;
+            if (!diag) Li[r][col] = 0.0;
+        }
+        if (t < kNB) yv[t] = 0.0;
+        __syncthreads();
+        gather_write<kLdT>(gi, &Li[0][0]);
+        gather_rest<kLdT>(lf.g, to.q0, ni36, &Li[0][0]);
+        diag_write<kLdT>(dq, lf.g, &A[0][0], yv);      // yv: the 64 rhs rows of tile k
+        gather_write<kLdT>(gk, &A[0][0]);
+        gather_rest<kLdT>(lf.g, qk, nk36, &A[0][0]);
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    sik[m][n2][g] = diag ? 0.0 : Li[r0 + 16 * m + lk + 4 * g][c0 + 16 * n2 + li];
+                    skk[m][n2][g] = 0.0; akk[m][n2][g] = 0.0; aik[m][n2][g] = 0.0;
+                }
+    } else if (FILL) {
         // off-diagonal tile first (composed in Li's storage, kept in registers), then the pivot tile straight into A
         if (!diag) compose_tile<kLdT>(c, lf.d, lf.f, lf.fz_q[2 * b + 1], &Li[0][0], nullptr);
 #pragma unroll
@@ -1792,21 +1943,31 @@ __device__ __forceinline__ void lv_factor_body(const CholDev& c, const int b, co
     if (t < kNB) fv[t] = (diag && late_kk >= 0) ? Ql[(size_t)late_kk * kPartStride + kNB * kNB + t] : 0.0;
     if (!FILL) {
         double* As = &A[0][0]; double* Bs = &Li[0][0];
-        const int qa = dptr[b], qb = dptr[b + 1];
+        const int qa = DESC ? fz.qa : dptr[b], qb = DESC ? fz.qa + fz.n : dptr[b + 1];
         double2 ra[8], rb[8];
         if (qa < qb) {
+            if (DESC) {
+                load_tile_regs(rb, c.S + (size_t)fz.pre[0].kj * kNB, ld);
+                if (!diag && fz.pre[0].jj >= 0) load_tile_regs(ra, c.S + (size_t)fz.pre[0].ij * kNB, ld);
+            } else {
             const int jj = dj[qa]; const bool own = jj >= 0; const int j = own ? jj : ~jj;
             load_tile_regs(rb, tile_ptr(c, k, j), ld);
             if (!diag && own) load_tile_regs(ra, tile_ptr(c, i, j), ld);
+            }
         }
+        static_assert(kFzPre == 2, "the first two list entries come from the record");
         for (int q = qa; q < qb; ++q) {
-            const int jj = dj[q]; const bool own = jj >= 0; const int j = own ? jj : ~jj;
+            const int jj = (DESC && q - qa < kFzPre) ? (q == qa ? fz.pre[0].jj : fz.pre[1].jj) : dj[q];
+            const bool own = jj >= 0; const int j = own ? jj : ~jj;
             __syncthreads();                       // the previous products no longer read LDS
             store_tile_lds(Bs, rb);
             if (!diag && own) store_tile_lds(As, ra);
             if (diag && t < kNB) yv[t] = c.y[j * kNB + t];
             __syncthreads();
-            if (q + 1 < qb) {                      // next contribution: loads in flight during the MFMAs below
+            if (DESC && q == qa && q + 1 < qb) {
+                load_tile_regs(rb, c.S + (size_t)fz.pre[1].kj * kNB, ld);
+                if (!diag && fz.pre[1].jj >= 0) load_tile_regs(ra, c.S + (size_t)fz.pre[1].ij * kNB, ld);
+            } else if (q + 1 < qb) {               // next contribution: loads in flight during the MFMAs below
                 const int jn = dj[q + 1]; const bool ownn = jn >= 0; const int j2 = ownn ? jn : ~jn;
                 load_tile_regs(rb, tile_ptr(c, k, j2), ld);
                 if (!diag && ownn) load_tile_regs(ra, tile_ptr(c, i, j2), ld);
@@ -1897,7 +2058,7 @@ __device__ __forceinline__ void lv_factor_body(const CholDev& c, const int b, co
 #pragma unroll
             for (int g = 0; g < 4; ++g) Sik[(size_t)(r0 + 16 * m + lk + 4 * g) * ld + c0 + 16 * n2 + li] = acc[m][n2][g];
 }
-template <bool FILL>
+template <bool FILL, bool DESC = false>
 __global__ __launch_bounds__(256) void k_lv_factor(CholDev c, const int* __restrict__ tiles, const int* __restrict__ dptr,
                                                    const int* __restrict__ dj, const int* __restrict__ tile_cam, double* __restrict__ px,
                                                    LvFill lf) {
@@ -1906,7 +2067,7 @@ __global__ __launch_bounds__(256) void k_lv_factor(CholDev c, const int* __restr
     __shared__ double Xs[kNB][kLdT];
     __shared__ double Tb[3][16][17];
     __shared__ double yv[kNB], fv[kNB];
-    lv_factor_body<FILL>(c, blockIdx.x, tiles, dptr, dj, tile_cam, px, lf, A, Li, Xs, Tb, yv, fv);
+    lv_factor_body<FILL, DESC>(c, blockIdx.x, tiles, dptr, dj, tile_cam, px, lf, A, Li, Xs, Tb, yv, fv);
 }
 
 // Look-ahead panel schedule (ba_plan.h: lookahead; level = column): ONE launch per column s.  Workgroups [0, n_factor): the
@@ -2102,20 +2263,26 @@ __global__ __launch_bounds__(256) void k_lv_bwd_chunk(CholDev c, const int* __re
 typedef __attribute__((address_space(1))) unsigned long long xba_gu64;
 constexpr int kBwdPre = 4;                    // ancestors per round: one per wave polls, their tile values sit in registers
 constexpr unsigned kBwdSpinMax = 1u << 21;
+//  * DESC (XRSFM_BA_CHAIN_DESC): order / klist / cptr collapse into one record per ticket position (ba_plan.h: BwdDesc), which also
+//    names the row tiles of the first round, whether their x is final, and where their tiles are stored; later rounds walk ci.
+static_assert(kBwdPre == kBwdRound, "BwdDesc holds one round of ancestors");
+template <bool DESC>
 __global__ __launch_bounds__(256) void k_lv_bwd_all(CholDev c, const int* __restrict__ klist, const int* __restrict__ cptr, const int* __restrict__ ci,
                                                     const int* __restrict__ tile_cam, double* __restrict__ px, const int* __restrict__ order,
                                                     const unsigned char* __restrict__ col_final, unsigned long long* gx, unsigned* counter,
                                                     unsigned base, unsigned epoch, unsigned* err, double* err_scal, unsigned spin_max,
-                                                    unsigned wait_epoch) {
+                                                    unsigned wait_epoch, const BwdDesc* __restrict__ bdv) {
     __shared__ double xs[kBwdPre][kNB];
     __shared__ double acc[kNB];
     __shared__ int s_b;
     const int t = threadIdx.x, o = t >> 2, part = t & 3, lane = t & 63, wave = t >> 6;
     if (t == 0) s_b = (int)(atomicAdd(counter, 1u) - base);
     __syncthreads();
-    const int e = order[s_b];
-    const int k = klist[e];
-    const int q0 = cptr[e], q1 = cptr[e + 1];
+    BwdDesc bd{};
+    int e = 0;
+    if (DESC) bd = bdv[s_b]; else e = order[s_b];
+    const int k = DESC ? bd.k : klist[e];
+    const int q0 = DESC ? bd.q0 : cptr[e], q1 = DESC ? bd.q1 : cptr[e + 1];
     const double* Lk = c.Linv + (size_t)k * kNB * kNB;
     double lk[16];
 #pragma unroll
@@ -2133,14 +2300,19 @@ __global__ __launch_bounds__(256) void k_lv_bwd_all(CholDev c, const int* __rest
 #pragma unroll
         for (int u = 0; u < kBwdPre; ++u)
             if (u < n) {
-                const double* Mp = tile_ptr(c, ci[qb + u], k) + (size_t)(part * 16) * c.ld + o;
+                const double* Mt = (DESC && qe == q1) ? c.S + (size_t)bd.pre[u].ik * kNB : tile_ptr(c, ci[qb + u], k);
+                const double* Mp = Mt + (size_t)(part * 16) * c.ld + o;
 #pragma unroll
                 for (int m = 0; m < 16; ++m) M[u][m] = Mp[(size_t)m * c.ld];
             }
         if (wave < n) {                                  // wave w fetches x of ancestor w of this round
-            const int i = ci[qb + wave];
+            int i; bool fin;
+            if (DESC && qe == q1) {
+                const int iw = wave == 0 ? bd.pre[0].i : (wave == 1 ? bd.pre[1].i : (wave == 2 ? bd.pre[2].i : bd.pre[3].i));
+                i = iw & (kBwdFinal - 1); fin = (iw & kBwdFinal) != 0;
+            } else { i = ci[qb + wave]; fin = col_final[i] != 0; }
             double xv;
-            if (col_final[i]) xv = c.x[i * kNB + lane];
+            if (fin) xv = c.x[i * kNB + lane];
             else {
                 xba_gu64* g = (xba_gu64*)(gx + (size_t)i * (2 * kNB) + 2 * lane);
                 unsigned long long a0 = 0, a1 = 0;

@@ -87,6 +87,109 @@ struct CholPlan {
     std::vector<int> tile_cam;          // [T][kCamsPerTile] camera in slot q of tile t, -1 = none (backward kernel: candidate cameras)
 };
 
+// ---- flattened index chains of the reduced-camera chain (chol_chain_desc, XRSFM_BA_CHAIN_DESC)
+// Everything the head of a chain launch used to resolve through dependent loads of the lists above, resolved once per set-up.
+// A tile's storage is named by its element offset / 64 (dense: i * n_pad + k, packed: 65 * index — both forms keep tiles
+// 64-double aligned), so a packed plan needs no tile-map read either.
+//
+// Gather record of one 6x6 block of a tile (same order as tf_ent: the diagonal blocks of a diagonal tile first):
+//   id   block id (off-diagonal: value e of the block at Sblk[36 id + e]) or camera (diagonal: camS[28 id + ..], camlin[12 id + ..])
+//   pk   first tile row | first tile column << 8 of the element (r = 0, col = 0) | kFillTransposed: element (r, col) goes to
+//        (column + col, row + r) instead of (row + r, column + col); off-diagonal values are stored negated, as compose_tile does
+struct alignas(8) FillRec { int id, pk; };
+constexpr int kFillTransposed = 1 << 16;
+// One tile to compose: records [q0, q1), the first nd of them diagonal blocks; nrows = cameras' rows of a diagonal tile (unit
+// pivots below them), 64 on the others; off64 = where the tile is stored
+struct alignas(16) TileDesc { int q0, nd, q1, nrows, ti, tj; unsigned off64; int pad; };
+// One workgroup of k_lv_factor<false>: its tiles (i,k) and (k,k), nb = 16-row blocks of the pivot tile that hold cameras, the
+// n entries of its list from fz_dj[qa] on, and the first kFzPre of them resolved: jj as in fz_dj (j, or ~j if (i,j) is not
+// in the pattern), where (k,j) and (i,j) are stored
+constexpr int kFzPre = 2;
+struct alignas(64) FzDesc {
+    int i, k, nb, n;
+    unsigned kk, ik; int qa, pad;
+    struct { int jj; unsigned kj, ij; } pre[kFzPre];
+    int pad2[2];
+};
+// One column of k_lv_bwd_all, by ticket position (bw_order): column k, its list lv_bi[q0, q1), and the entries of the first
+// round (the last kBwdRound of the list: the root side) resolved: row tile i | kBwdFinal if x_i was solved in the last level's
+// factor launch, where (i,k) is stored
+constexpr int kBwdRound = 4;          // (ba_chol.h: kBwdPre)
+constexpr int kBwdFinal = 1 << 30;
+struct alignas(16) BwdDesc {
+    int k, q0, q1, pad;
+    struct { int i; unsigned ik; } pre[kBwdRound];
+};
+static_assert(sizeof(FillRec) == 8 && sizeof(TileDesc) == 32 && sizeof(FzDesc) == 64 && sizeof(BwdDesc) == 48, "records are read with wide loads");
+struct ChainDesc {
+    std::vector<FillRec> fill_rec;      // per tf_ent entry
+    std::vector<TileDesc> tile_desc;    // per structurally non-zero tile (tiles_nz order): k_tile_fill, trailing workgroups of the first level
+    std::vector<TileDesc> fz_fill;      // per fused-kernel entry of level 0: the pivot tile, then the own tile (k_lv_factor<true>)
+    std::vector<FzDesc> fz_desc;        // per fused-kernel entry (every level; fz_off)
+};
+// where tile (i,k) is stored, in units of 64 doubles
+inline unsigned chain_off64(const CholPlan& P, bool packed, int i, int k) {
+    return packed ? (unsigned)P.tile_map[(size_t)i * P.T + k] * (unsigned)(kPlanTile + 1) : (unsigned)i * (unsigned)P.n_pad + (unsigned)k;
+}
+// the record of column e (index into lv_k) for k_lv_bwd_all; is_final: columns of the last level
+inline BwdDesc chain_bwd_desc(const CholPlan& P, bool packed, int e, const std::vector<unsigned char>& is_final) {
+    BwdDesc b{};
+    b.k = P.lv_k[e]; b.q0 = P.lv_bptr[e]; b.q1 = P.lv_bptr[e + 1];
+    const int qb = std::max(b.q0, b.q1 - kBwdRound);
+    for (int u = 0; u < b.q1 - qb; ++u) {
+        const int i = P.lv_bi[qb + u];
+        b.pre[u].i = i | (is_final[i] ? kBwdFinal : 0);
+        b.pre[u].ik = chain_off64(P, packed, i, b.k);
+    }
+    return b;
+}
+
+// packed: the tile storage chol_setup chose (tile (i,k) at tile_map[i T + k] * (4096 + 64) doubles, else dense with ld = n_pad)
+inline void chol_chain_desc(const CholPlan& P, bool packed, ChainDesc& D) {
+    auto off64 = [&](int i, int k) -> unsigned { return chain_off64(P, packed, i, k); };
+    D.fill_rec.resize(P.tf_ent.size());
+    D.tile_desc.resize(P.n_tiles_nz);
+    for (int q = 0; q < P.n_tiles_nz; ++q) {
+        const int ti = P.tiles_nz[2 * q], tj = P.tiles_nz[2 * q + 1];
+        TileDesc t{};
+        t.q0 = P.tf_ptr[q]; t.q1 = P.tf_ptr[q + 1]; t.nd = 0;
+        t.nrows = ti == tj ? P.tile_rows[ti] : kPlanTile; t.ti = ti; t.tj = tj; t.off64 = off64(ti, tj);
+        for (int w = t.q0; w < t.q1; ++w) {
+            const int ent = P.tf_ent[w];
+            FillRec r{};
+            if (ent < 0) {                  // (chol_plan_build lists the cameras of a tile before its blocks)
+                r.id = -ent - 1;
+                const int o = P.cam_off[r.id] & 63;
+                r.pk = o | (o << 8);
+                ++t.nd;
+            } else {
+                const int orow = P.cam_off[P.blk_rc[2 * (size_t)ent]], ocol = P.cam_off[P.blk_rc[2 * (size_t)ent + 1]];
+                r.id = ent;
+                r.pk = (orow & 63) | ((ocol & 63) << 8) | (orow > ocol ? 0 : kFillTransposed);
+            }
+            D.fill_rec[w] = r;
+        }
+        D.tile_desc[q] = t;
+    }
+    const size_t n_fz = P.fz_tile.size() / 2;
+    const size_t n_fz0 = P.fz_off.size() > 1 ? (size_t)P.fz_off[1] : 0;
+    D.fz_fill.resize(2 * n_fz0);
+    for (size_t e = 0; e < n_fz0; ++e) { D.fz_fill[2 * e] = D.tile_desc[P.fz_q[2 * e]]; D.fz_fill[2 * e + 1] = D.tile_desc[P.fz_q[2 * e + 1]]; }
+    D.fz_desc.resize(n_fz);
+    for (size_t e = 0; e < n_fz; ++e) {
+        FzDesc f{};
+        f.i = P.fz_tile[2 * e]; f.k = P.fz_tile[2 * e + 1];
+        f.nb = (P.tile_rows[f.k] + 15) >> 4;
+        f.qa = P.fz_dptr[e]; f.n = P.fz_dptr[e + 1] - f.qa;
+        f.kk = off64(f.k, f.k); f.ik = off64(f.i, f.k);
+        for (int p = 0; p < kFzPre && p < f.n; ++p) {
+            const int jj = P.fz_dj[f.qa + p], j = jj >= 0 ? jj : ~jj;
+            f.pre[p].jj = jj; f.pre[p].kj = off64(f.k, j); f.pre[p].ij = off64(f.i, j);
+        }
+        D.fz_desc[e] = f;
+    }
+}
+
 struct PairKey {                 // ((cam_b << 32) | cam_a, pair index); trivially constructible: the lists below are never zero-filled
     unsigned long long first; int second;
     bool operator<(const PairKey& o) const { return first != o.first ? first < o.first : second < o.second; }

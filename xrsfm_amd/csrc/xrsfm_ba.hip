@@ -152,6 +152,8 @@ struct CholHost {
     bool S_filled = false;                                   // chol_assemble ran k_tile_fill (else the first level composes its tiles)
     std::vector<int> fz_off;
     int *tf_ptr = nullptr, *tf_ent = nullptr;                // per non-zero tile: its 6x6 blocks (k_tile_fill)
+    // flattened index chains (ba_plan.h: ChainDesc; XRSFM_BA_CHAIN_DESC=0: the lists above and the kernel paths that walk them)
+    bool chain_desc = false; FillRec* cd_rec = nullptr; TileDesc *cd_tile = nullptr, *cd_fz_fill = nullptr; FzDesc* cd_fz = nullptr; BwdDesc* cd_bwd = nullptr;
     std::vector<int> cam_off_host;
     std::vector<int> tile_map_host; size_t S_doubles = 0;    // packed tile storage of S (CholDev::tmap), its size in doubles
     std::vector<int> lv_k_host, lv_bptr_host, lv_bi_host;    // host copies of the level lists (xrsfm_ba_covariance: which tile columns a selection reaches)
@@ -1012,7 +1014,16 @@ int chol_setup(xrsfm_ba_context* c) {
     h.sp_chunk_off = P.sp_chunk_off; h.sp_rt_off = P.sp_rt_off; h.mp_off = P.mp_off; h.fz_off = P.fz_off;
     int *d_cam_off = nullptr, *d_tile_rows = nullptr, *d_tmap = nullptr;
 #define TRYC(x) do { e = (x); if (e) return e; } while (0)
+    // The index chains at the head of the chain launches, flattened (ba_plan.h: ChainDesc).  XRSFM_BA_CHAIN_DESC=0 keeps the lists
+    // and the kernel paths that walk them.
+    ChainDesc CD;
+    { const char* cde = std::getenv("XRSFM_BA_CHAIN_DESC"); h.chain_desc = !(cde && cde[0] == '0'); }      // (read per set-up: the A/B test switches it)
+    if (h.chain_desc) {
+        try { chol_chain_desc(P, chol_packed_storage(P), CD); }
+        catch (const std::bad_alloc&) { return XRSFM_BA_ENOMEM; }
+    }
     BatchUpload up(c);
+    if (h.chain_desc) { up.add(&h.cd_rec, CD.fill_rec); up.add(&h.cd_tile, CD.tile_desc); up.add(&h.cd_fz_fill, CD.fz_fill); up.add(&h.cd_fz, CD.fz_desc); }
     if (dev_keys) { h.slot_pair_ptr = KR.spp; h.pair_dst = KR.pair_dst; h.blk_ptr = KR.blk_ptr; h.blk_rc = KR.blk_rc; }
     else { up.add(&h.slot_pair_ptr, P.spp); up.add(&h.pair_dst, P.pair_dst); up.add(&h.blk_ptr, P.blk_ptr); up.add(&h.blk_rc, P.blk_rc); }
     up.add(&h.tiles_nz, P.tiles_nz); up.add(&h.cols_flat, P.cols_flat); up.add(&h.bw2_ent, P.bw2_ent);
@@ -1124,6 +1135,11 @@ int chol_setup(xrsfm_ba_context* c) {
             for (int e2 = P.lv_k_off[P.n_levels - 1]; e2 < P.lv_k_off[P.n_levels]; ++e2) fin[P.lv_k[e2]] = 1;
             h.bw_n = (int)order.size(); h.bw_launches = 0;
             TRYC(dev_upload(c, &h.bw_order, order)); TRYC(dev_upload(c, &h.bw_final, fin));
+            if (h.chain_desc) {       // one record per ticket position (ba_plan.h: BwdDesc)
+                std::vector<BwdDesc> bd(order.size());
+                for (size_t q = 0; q < order.size(); ++q) bd[q] = chain_bwd_desc(P, packed, order[q], fin);
+                TRYC(dev_upload(c, &h.cd_bwd, bd));
+            }
             TRYC(dev_alloc(c, &h.bw_gx, (size_t)P.T * 2 * kNB)); TRYC(dev_alloc(c, &h.bw_ctr, (size_t)2));
             HIPCHK(hipMemsetAsync(h.bw_gx, 0, sizeof(unsigned long long) * (size_t)P.T * 2 * kNB, c->stream));      // tag 0 = never written
             HIPCHK(hipMemsetAsync(h.bw_ctr, 0, sizeof(unsigned) * 2, c->stream));                                   // [0] tickets, [1] error word
@@ -1244,9 +1260,14 @@ int chol_assemble(xrsfm_ba_context* c, bool materialize = false) {
     int e = allreduce(c, d.camS, (size_t)d.n_cams * 28 + (size_t)h.n_blocks * 36, kNcclSum);   // camS | Sblk are contiguous
     if (e) return e;
     h.S_filled = materialize;          // (else the first level's factor launch composes the tiles from the block values)
-    if (h.S_filled && h.n_tiles_nz > 0)
+    if (h.S_filled && h.n_tiles_nz > 0) {
+        if (h.chain_desc)
+            LAUNCH(c, K_DENSE_FILL, k_tile_fill_rec, dim3(h.n_tiles_nz), dim3(256), 0, h.dev, d, (const TileDesc*)h.cd_tile,
+                   FillRecs{h.cd_rec, h.Sblk, c->step_prep ? c->step_radius : 0.0});
+        else
         LAUNCH(c, K_DENSE_FILL, k_tile_fill, dim3(h.n_tiles_nz), dim3(256), 0, h.dev, d, h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc,
                c->step_prep ? c->step_radius : 0.0);
+    }
     return 0;
 }
 
@@ -1297,9 +1318,15 @@ int chol_factor_solve(xrsfm_ba_context* c) {
                 LvFill lf{};
                 lf.d = d; lf.f = FillLists{h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc, c->step_prep ? c->step_radius : 0.0};
                 lf.fz_q = h.fz_q; lf.rest = h.fill_rest; lf.n_factor = nf;
-                if (nf + h.n_fill_rest > 0)
+                lf.g = FillRecs{h.cd_rec, h.Sblk, lf.f.radius}; lf.tdesc = h.cd_tile; lf.fz_fill = h.cd_fz_fill;
+                if (nf + h.n_fill_rest > 0) {
+                    if (h.chain_desc)
+                        LAUNCH(c, K_POTRF, (k_lv_factor<true, true>), dim3(nf + h.n_fill_rest), dim3(256), 0, h.dev, h.fz_tile, h.fz_dptr, h.fz_dj,
+                               (const int*)h.tile_cam, (double*)nullptr, lf);
+                    else
                     LAUNCH(c, K_POTRF, k_lv_factor<true>, dim3(nf + h.n_fill_rest), dim3(256), 0, h.dev, h.fz_tile, h.fz_dptr, h.fz_dj,
                            (const int*)h.tile_cam, (double*)nullptr, lf);
+                }
                 if (a.n_reduce + a.n_part + a.n_late > 0) return XRSFM_BA_EINTERNAL;      // columns 1 and 2 have nothing older than column 0
                 continue;
             }
@@ -1344,15 +1371,27 @@ int chol_factor_solve(xrsfm_ba_context* c) {
                 // through S); trailing workgroups compose the tiles of all other columns
                 lf.d = d; lf.f = FillLists{h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc, c->step_prep ? c->step_radius : 0.0};
                 lf.fz_q = h.fz_q; lf.rest = h.fill_rest; lf.n_factor = nf;
+                lf.g = FillRecs{h.cd_rec, h.Sblk, lf.f.radius}; lf.tdesc = h.cd_tile; lf.fz_fill = h.cd_fz_fill;
                 // thousands of tiles outside the first level: composed by a launch of their own (several workgroups per CU)
                 const bool rest_apart = h.rest_apart;
-                if (rest_apart)
+                if (rest_apart && h.chain_desc)
+                    LAUNCH(c, K_DENSE_FILL, k_tile_fill_rec, dim3(h.n_fill_rest), dim3(256), 0, h.dev, d, (const TileDesc*)h.cd_tile, lf.g, (const int*)h.fill_rest);
+                else if (rest_apart)
                     LAUNCH(c, K_DENSE_FILL, k_tile_fill, dim3(h.n_fill_rest), dim3(256), 0, h.dev, d, h.tiles_nz, h.tf_ptr, h.tf_ent, h.Sblk, h.blk_rc,
                            c->step_prep ? c->step_radius : 0.0, (const int*)h.fill_rest);
                 const int n_rest = rest_apart ? 0 : h.n_fill_rest;
-                if (nf + n_rest > 0)
+                if (nf + n_rest > 0) {
+                    if (h.chain_desc)
+                        LAUNCH(c, K_POTRF, (k_lv_factor<true, true>), dim3(nf + n_rest), dim3(256), 0, h.dev, h.fz_tile, h.fz_dptr, h.fz_dj,
+                               (const int*)h.tile_cam, with_bwd ? px_out : (double*)nullptr, lf);
+                    else
                     LAUNCH(c, K_POTRF, k_lv_factor<true>, dim3(nf + n_rest), dim3(256), 0, h.dev, h.fz_tile, h.fz_dptr, h.fz_dj,
                            (const int*)h.tile_cam, with_bwd ? px_out : (double*)nullptr, lf);
+                }
+            } else if (nf > 0 && h.chain_desc) {
+                lf.fzd = h.cd_fz + h.fz_off[lv];
+                LAUNCH(c, K_POTRF, (k_lv_factor<false, true>), dim3(nf), dim3(256), 0, h.dev, h.fz_tile + 2 * (size_t)h.fz_off[lv], h.fz_dptr + h.fz_off[lv], h.fz_dj,
+                       (const int*)h.tile_cam, with_bwd ? px_out : (double*)nullptr, lf);
             } else if (nf > 0)
                 LAUNCH(c, K_POTRF, k_lv_factor<false>, dim3(nf), dim3(256), 0, h.dev, h.fz_tile + 2 * (size_t)h.fz_off[lv], h.fz_dptr + h.fz_off[lv], h.fz_dj,
                        (const int*)h.tile_cam, with_bwd ? px_out : (double*)nullptr, lf);
@@ -1392,9 +1431,14 @@ int chol_factor_solve(xrsfm_ba_context* c) {
             // all remaining levels in one launch: x travels between the workgroups of the launch as tagged granules (ba_chol.h)
             const unsigned base = h.bw_launches * (unsigned)h.bw_n;       // tickets handed out so far (unsigned wrap-around is fine)
             const unsigned epoch = ++h.bw_launches;
-            LAUNCH(c, K_TRISOLVE, k_lv_bwd_all, dim3(h.bw_n), dim3(256), 0, h.dev, (const int*)h.lv_k, (const int*)h.lv_bptr, (const int*)h.lv_bi,
+            if (h.chain_desc)
+                LAUNCH(c, K_TRISOLVE, k_lv_bwd_all<true>, dim3(h.bw_n), dim3(256), 0, h.dev, (const int*)h.lv_k, (const int*)h.lv_bptr, (const int*)h.lv_bi,
+                       (const int*)h.tile_cam, px_out, (const int*)h.bw_order, (const unsigned char*)h.bw_final, h.bw_gx, h.bw_ctr, base, epoch, h.bw_ctr + 1,
+                       d.scal + S_BWD_ERR, h.bw_debug_timeout ? 64u : kBwdSpinMax, h.bw_debug_timeout ? epoch + 1u : epoch, (const BwdDesc*)h.cd_bwd);
+            else
+            LAUNCH(c, K_TRISOLVE, k_lv_bwd_all<false>, dim3(h.bw_n), dim3(256), 0, h.dev, (const int*)h.lv_k, (const int*)h.lv_bptr, (const int*)h.lv_bi,
                    (const int*)h.tile_cam, px_out, (const int*)h.bw_order, (const unsigned char*)h.bw_final, h.bw_gx, h.bw_ctr, base, epoch, h.bw_ctr + 1,
-                   d.scal + S_BWD_ERR, h.bw_debug_timeout ? 64u : kBwdSpinMax, h.bw_debug_timeout ? epoch + 1u : epoch);
+                   d.scal + S_BWD_ERR, h.bw_debug_timeout ? 64u : kBwdSpinMax, h.bw_debug_timeout ? epoch + 1u : epoch, (const BwdDesc*)nullptr);
             return 0;
         }
         for (int lv = h.n_levels - 2; lv >= 0; --lv) {      // (the last level: inside its k_lv_factor launch)
@@ -1488,8 +1532,9 @@ int finish_step(xrsfm_ba_context* c, double huber_a, bool speculate) {
     return fetch_scalars(c);
 }
 
-// k_lv_bwd_all bounds its spins and raises a device word when one gives up (a granule that never arrived): checked once per
-// solve, after the stream has drained (level schedules with >= 2 levels only: never an LBA-sized call).
+// k_lv_bwd_all bounds its spins and raises a device word when one gives up (a granule that never arrived): read back by the
+// covariance entry points after their solves, which have no scalar hand-over behind them (the run path checks S_BWD_ERR with every
+// hand-over instead: bwd_err_check; level schedules with >= 2 levels only: never an LBA-sized call).
 int bwd_all_status(xrsfm_ba_context* c) {
     CholHost& h = c->chol;
     if (!h.bwd_all || h.bw_launches == 0 || !h.bw_ctr) return 0;
@@ -2986,7 +3031,8 @@ static int ba_run_impl(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_
         sum->termination = term; sum->termination_reason = reason; sum->final_cost = cost;
         (void)hipStreamSynchronize(st);
         sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        if (int be = bwd_all_status(c)) return be;
+        // (no bwd_all_status() here: every chol_factor_solve of this function is followed by finish_step, whose two exits both end in
+        //  fetch_scalars -> bwd_err_check on the scalar block handed over behind that k_lv_bwd_all launch)
         if (c->profiling) {
             profile_collect(c);
             int best = 0;
