@@ -828,6 +828,60 @@ int xrsfm_ba_debug_match_table(float *table /* [262145] */);
 int xrsfm_ba_debug_match_top2(int32_t n_a, const uint8_t *desc_a, int32_t n_b, const uint8_t *desc_b,
                               int32_t *row_top /* [n_a][3] */, int32_t *col_top /* [n_b][3] */);
 
+/* Batched SIFT scale space and keypoint detection: the first half of what SiftExtractor computes for every image
+ * (SiftGPU::RunSIFT: reference 3rdparty/SiftGPU/PyramidCU.cpp BuildPyramid, DetectKeypointsEX, GenerateFeatureList and
+ * DownloadKeypoints; ProgramCU.cu FilterH/FilterV, UpsampleKernel, DownsampleKernel, ComputeDOG_Kernel, ComputeKEY_Kernel), with the
+ * orientation fixed to 0: the keypoint list of the reference's upright mode.  All arithmetic is FP32; the rule is restated in
+ * xrsfm_amd/csrc/ba_sift_rule.h and DESIGN.md 5m.  All images of a call, whatever their sizes, go through the same kernel launches.
+ *
+ * Image i is width[i] x height[i] 8-bit grey, row-major and packed, at pixels + pixel_ptr[i]; pixel_ptr[i+1] - pixel_ptr[i] =
+ * width[i] * height[i].  The width is truncated to a multiple of 4 (the columns beyond are ignored).  Octave o of the pyramid has
+ * height h0 >> o and the STORED width roundup4(w0 >> o), (w0, h0) = (W, H) << 1 for first_octave -1; there are
+ * min(num_octaves, max(1, floor(log2(min(w0, h0))) - 3)) octaves.
+ *   keys[k]         (X, Y, S, 0): position and scale in input-image pixels (DownloadKeypoints), orientation 0
+ *   loc[k]          (octave, DoG level j in 0..2, row, col): the integer location in the octave, for the descriptor stage
+ *   sign[k]         +1 maximum, -1 minimum
+ *   key_ptr         the keypoints of image i are key_ptr[i] .. key_ptr[i+1], in the order octave, level, row, column ascending
+ *                   (the reference's order within a level is that of its histogram pyramid and is not reproduced)
+ *   level_count     [n_images][num_octaves * 3], may be NULL: the keypoints of every level BEFORE the budget (0 for octaves the
+ *                   image does not have).  The budget: levels are visited from the last octave to the first and from j = 2 to 0;
+ *                   a level contributes nothing if the total already exceeds max_num_features, else all of its keypoints
+ * If the pyramids of the call exceed XRSFM_BA_SIFT_WORKSPACE_MB (environment, default 4096) the call runs in chunks of images
+ * (an image larger than the budget runs alone); the results do not depend on the split by a bit.
+ *
+ * XRSFM_BA_EINVAL, checked before the device is touched, one line on stderr, outputs untouched: NULL opt; a negative n_images or
+ * capacity; first_octave outside {-1, 0}; num_octaves outside 1 .. 8; a non-finite or non-positive threshold; max_num_features or
+ * max_image_size < 1; with n_images > 0: NULL width, height, pixel_ptr, pixels or key_ptr, NULL keys, loc or sign with a capacity,
+ * a truncated width or a height below 16, a side above max_image_size (the reference down-samples such images: not built), a
+ * pixel_ptr that does not start at 0 or disagrees with the sizes.  XRSFM_BA_EINVAL after the computation, with one line on stderr
+ * that names the needed size, when the keypoints do not fit capacity: key_ptr and level_count are written, keys, loc and sign are
+ * not.  XRSFM_BA_ENODEV without a device (there is no CPU path); XRSFM_BA_ENOMEM when the workspace cannot be had.  n_images == 0
+ * is success and needs no device. */
+typedef struct xrsfm_ba_sift_options {
+    int32_t first_octave;      /* -1      sift_extractor.h; -1 or 0 */
+    int32_t num_octaves;       /* 4       1 .. 8 */
+    float   peak_threshold;    /* 0.02/3  */
+    float   edge_threshold;    /* 10      */
+    int32_t max_num_features;  /* 8192    */
+    int32_t max_image_size;    /* 3200    */
+} xrsfm_ba_sift_options;
+#define XRSFM_BA_SIFT_MAX_TAPS 33
+#define XRSFM_BA_SIFT_MAX_OCTAVES 8
+void xrsfm_ba_sift_options_default(xrsfm_ba_sift_options *opt);   /* the values above */
+int xrsfm_ba_detect_keypoints(const xrsfm_ba_sift_options *opt, int32_t n_images, const int32_t *width, const int32_t *height /* [n_images] */,
+                              const int64_t *pixel_ptr /* [n_images+1] */, const uint8_t *pixels, int64_t capacity,
+                              int64_t *key_ptr /* [n_images+1] */, float *keys /* [capacity][4] */, int32_t *loc /* [capacity][4] */,
+                              int8_t *sign /* [capacity] */, int32_t *level_count /* [n_images][num_octaves*3], may be NULL */);
+/* TEST ENTRY, no GPU: the taps of the Gaussian filter of one sigma (CreateFilterKernel); taps beyond *width are 0. */
+int xrsfm_ba_debug_sift_taps(float sigma, float *taps /* [33] */, int32_t *width);
+/* TEST ENTRY: the six Gaussian and the five DoG levels of one octave of one image, [level][h][w] with w the stored width. */
+int xrsfm_ba_debug_sift_levels(const xrsfm_ba_sift_options *opt, int32_t width, int32_t height, const uint8_t *pixels, int32_t octave,
+                               float *gauss /* [6][h][w] */, float *dog /* [5][h][w] */);
+/* TEST ENTRY: the keypoints of one image as xrsfm_ba_detect_keypoints orders them, with the sub-pixel offsets the interface
+ * folds into keys: offsets[k] = (sign, dx, dy, ds).  *n_keys is written even when capacity is too small (XRSFM_BA_EINVAL). */
+int xrsfm_ba_debug_sift_offsets(const xrsfm_ba_sift_options *opt, int32_t width, int32_t height, const uint8_t *pixels, int64_t capacity,
+                                int64_t *n_keys, int32_t *loc /* [capacity][4] */, float *offsets /* [capacity][4] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

@@ -75,6 +75,11 @@ class CMatchOptions(C.Structure):
     _fields_ = [("max_distance", C.c_float), ("max_ratio", C.c_float), ("mutual_best", C.c_int32), ("max_features", C.c_int32)]
 
 
+class CSiftOptions(C.Structure):
+    _fields_ = [("first_octave", C.c_int32), ("num_octaves", C.c_int32), ("peak_threshold", C.c_float), ("edge_threshold", C.c_float),
+                ("max_num_features", C.c_int32), ("max_image_size", C.c_int32)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -124,6 +129,8 @@ EXPORTS = [
     "xrsfm_ba_verify_pairs_options", "xrsfm_ba_verify_pairs", "xrsfm_ba_debug_fund_samples",
     "xrsfm_ba_match_options_default", "xrsfm_ba_match_descriptors", "xrsfm_ba_debug_match_table",
     "xrsfm_ba_debug_cam_stage",
+    "xrsfm_ba_sift_options_default", "xrsfm_ba_detect_keypoints", "xrsfm_ba_debug_sift_taps", "xrsfm_ba_debug_sift_levels",
+    "xrsfm_ba_debug_sift_offsets",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -161,6 +168,8 @@ FUND_LOCAL_BIT = 1 << 30  # best_trial: the 8-point local model of that trial is
 MATCH_MAX_FEATURES = 16384  # XRSFM_BA_MATCH_MAX_FEATURES: most descriptors of a frame xrsfm_ba_match_descriptors takes
 MATCH_DIM = 128          # XRSFM_BA_MATCH_DIM
 MATCH_TABLE_SIZE = (1 << 18) + 1  # entries of xrsfm_ba_debug_match_table
+SIFT_MAX_TAPS = 33       # XRSFM_BA_SIFT_MAX_TAPS
+SIFT_MAX_OCTAVES = 8     # XRSFM_BA_SIFT_MAX_OCTAVES
 EINVAL, ESTATE = -1, -5
 
 ERRORS = {-1: "EINVAL", -2: "ENODEV (no HIP device / HIP error; there is no CPU fallback)", -3: "ENOMEM",
@@ -296,6 +305,18 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_match_table.restype = C.c_int
     lib.xrsfm_ba_debug_match_top2.argtypes = [C.c_int32, _c_uint8_p, C.c_int32, _c_uint8_p, _c_int32_p, _c_int32_p]
     lib.xrsfm_ba_debug_match_top2.restype = C.c_int
+    _c_float_p, _c_int64_p, _so = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(CSiftOptions)
+    lib.xrsfm_ba_sift_options_default.argtypes = [_so]
+    lib.xrsfm_ba_sift_options_default.restype = None
+    lib.xrsfm_ba_detect_keypoints.argtypes = [_so, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_uint8_p, C.c_int64, _c_int64_p, _c_float_p, _c_int32_p,
+                                               C.POINTER(C.c_int8), _c_int32_p]
+    lib.xrsfm_ba_detect_keypoints.restype = C.c_int
+    lib.xrsfm_ba_debug_sift_taps.argtypes = [C.c_float, _c_float_p, _c_int32_p]
+    lib.xrsfm_ba_debug_sift_taps.restype = C.c_int
+    lib.xrsfm_ba_debug_sift_levels.argtypes = [_so, C.c_int32, C.c_int32, _c_uint8_p, C.c_int32, _c_float_p, _c_float_p]
+    lib.xrsfm_ba_debug_sift_levels.restype = C.c_int
+    lib.xrsfm_ba_debug_sift_offsets.argtypes = [_so, C.c_int32, C.c_int32, _c_uint8_p, C.c_int64, _c_int64_p, _c_int32_p, _c_float_p]
+    lib.xrsfm_ba_debug_sift_offsets.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1242,3 +1263,99 @@ def debug_pack_gram(problem: ProblemArrays) -> dict:
     out.update(tile_ncam=ncam[:st["tiles"]], slot_cidx=cidx[:st["slots"]], slot_campos_g=cpg[:st["slots"]], slot_obs=st["slot_obs"],
                items=st["items"], long_items=st["long_items"])
     return out
+
+
+def sift_options(**overrides) -> CSiftOptions:
+    """xrsfm_ba_sift_options_default: the settings of the reference's SiftExtractor."""
+    o = CSiftOptions()
+    load().xrsfm_ba_sift_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def sift_geometry(width: int, height: int, options: CSiftOptions | None = None) -> list:
+    """[(stored width, height)] of the octaves of a width x height image (include/xrsfm_ba.h)."""
+    o = options if options is not None else sift_options()
+    w0, h0 = (width & ~3) << (1 if o.first_octave < 0 else 0), height << (1 if o.first_octave < 0 else 0)
+    n = min(int(o.num_octaves), max(1, min(w0, h0).bit_length() - 1 - 3))
+    return [(((w0 >> k) + 3) // 4 * 4, h0 >> k) for k in range(n)]
+
+
+def _grey(image) -> np.ndarray:
+    a = np.asarray(image)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError("an image must be a 2-D uint8 array")
+    return np.ascontiguousarray(a)
+
+
+def detect_keypoints(images, options: CSiftOptions | None = None, capacity: int | None = None) -> list:
+    """xrsfm_ba_detect_keypoints on a list of 2-D uint8 arrays (any sizes): per image a dict of keys [n][4] (X, Y, S, 0), loc [n][4]
+    (octave, level, row, col), sign [n] and level_count [num_octaves * 3] (before the budget).  capacity: of the output arrays;
+    by default the call is repeated once with the size the library names."""
+    o = options if options is not None else sift_options()
+    imgs = [_grey(a) for a in images]
+    n = len(imgs)
+    w = np.array([a.shape[1] for a in imgs], np.int32); h = np.array([a.shape[0] for a in imgs], np.int32)
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:] = np.cumsum([a.size for a in imgs])
+    pix = np.concatenate([a.ravel() for a in imgs]) if n else np.zeros(0, np.uint8)
+    nl = max(int(o.num_octaves), 0) * 3
+    lc = np.zeros((n, nl), np.int32); kp = np.zeros(n + 1, np.int64)
+    lib = load()
+
+    def run(cap):
+        k = np.zeros((cap, 4), np.float32); l = np.zeros((cap, 4), np.int32); s = np.zeros(cap, np.int8)
+        code = lib.xrsfm_ba_detect_keypoints(C.byref(o), n, w.ctypes.data_as(_c_int32_p), h.ctypes.data_as(_c_int32_p), ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             pix.ctypes.data_as(_c_uint8_p), cap, kp.ctypes.data_as(C.POINTER(C.c_int64)), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                             l.ctypes.data_as(_c_int32_p), s.ctypes.data_as(C.POINTER(C.c_int8)), lc.ctypes.data_as(_c_int32_p))
+        return code, k, l, s
+    # (the budget lets an image exceed max_num_features by part of one level only)
+    first = max(n, 1) * min(max(int(o.max_num_features), 0) + 4096, 65536) if capacity is None else int(capacity)
+    code, k, l, s = run(first)
+    if code == EINVAL and capacity is None and n > 0 and kp[-1] > first:
+        code, k, l, s = run(int(kp[-1]))
+    check(code, "xrsfm_ba_detect_keypoints")
+    return [dict(keys=k[kp[i]:kp[i + 1]].copy(), loc=l[kp[i]:kp[i + 1]].copy(), sign=s[kp[i]:kp[i + 1]].copy(), level_count=lc[i].copy()) for i in range(n)]
+
+
+def debug_sift_taps(sigma: float) -> np.ndarray:
+    """xrsfm_ba_debug_sift_taps: the normalised taps of one sigma, cut to their width (no GPU)."""
+    t = np.zeros(SIFT_MAX_TAPS, np.float32)
+    wd = C.c_int32(0)
+    check(load().xrsfm_ba_debug_sift_taps(float(sigma), t.ctypes.data_as(C.POINTER(C.c_float)), C.byref(wd)), "xrsfm_ba_debug_sift_taps")
+    return t[:wd.value].copy()
+
+
+def debug_sift_levels(image, octave: int, options: CSiftOptions | None = None) -> tuple:
+    """xrsfm_ba_debug_sift_levels: (gauss [6][h][w], dog [5][h][w]) of one octave of one image."""
+    o = options if options is not None else sift_options()
+    a = _grey(image)
+    geo = sift_geometry(a.shape[1], a.shape[0], o)
+    if not 0 <= octave < len(geo):
+        raise ValueError("debug_sift_levels: the image has no such octave")
+    ws, hs = geo[octave]
+    g = np.zeros((6, hs, ws), np.float32); d = np.zeros((5, hs, ws), np.float32)
+    check(load().xrsfm_ba_debug_sift_levels(C.byref(o), a.shape[1], a.shape[0], a.ctypes.data_as(_c_uint8_p), octave, g.ctypes.data_as(C.POINTER(C.c_float)),
+                                            d.ctypes.data_as(C.POINTER(C.c_float))), "xrsfm_ba_debug_sift_levels")
+    return g, d
+
+
+def debug_sift_offsets(image, options: CSiftOptions | None = None) -> tuple:
+    """xrsfm_ba_debug_sift_offsets: (loc [n][4], offsets [n][4] = (sign, dx, dy, ds)) of one image, in the order of detect_keypoints."""
+    o = options if options is not None else sift_options()
+    a = _grey(image)
+    n = C.c_int64(0)
+    cap = 4096
+    for _ in range(2):
+        l = np.zeros((cap, 4), np.int32); f = np.zeros((cap, 4), np.float32)
+        code = load().xrsfm_ba_debug_sift_offsets(C.byref(o), a.shape[1], a.shape[0], a.ctypes.data_as(_c_uint8_p), cap, C.byref(n), l.ctypes.data_as(_c_int32_p),
+                                                  f.ctypes.data_as(C.POINTER(C.c_float)))
+        if code == EINVAL and n.value > cap:
+            cap = int(n.value)
+            continue
+        break
+    check(code, "xrsfm_ba_debug_sift_offsets")
+    return l[:n.value].copy(), f[:n.value].copy()

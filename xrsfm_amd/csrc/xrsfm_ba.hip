@@ -37,6 +37,7 @@
 #include "ba_fund.h"
 #include "ba_match.h"
 #include "ba_refine.h"
+#include "ba_sift.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
 #include "ba_wide.h"
@@ -4390,6 +4391,380 @@ int xrsfm_ba_match_descriptors(const xrsfm_ba_match_options* opt, int32_t n_fram
 
 int xrsfm_ba_debug_match_top2(int32_t n_a, const uint8_t* desc_a, int32_t n_b, const uint8_t* desc_b, int32_t* row_top, int32_t* col_top) {
     return no_throw([&] { return debug_match_top2_impl(n_a, desc_a, n_b, desc_b, row_top, col_top); });
+}
+
+// ---------------------------------------------------------------- batched SIFT scale space and keypoint detection (ba_sift.h)
+void xrsfm_ba_sift_options_default(xrsfm_ba_sift_options* opt) {
+    if (!opt) return;
+    opt->first_octave = -1;                   // sift_extractor.h:36-107
+    opt->num_octaves = 4;
+    opt->peak_threshold = 0.02f / 3;
+    opt->edge_threshold = 10.0f;
+    opt->max_num_features = 8192;
+    opt->max_image_size = 3200;
+}
+
+int xrsfm_ba_debug_sift_taps(float sigma, float* taps, int32_t* width) {
+    if (!taps || !width || !(sigma > 0.0f) || !std::isfinite(sigma)) return XRSFM_BA_EINVAL;
+    xsift::Taps t;
+    xsift::build_taps(sigma, &t);
+    memcpy(taps, t.w, sizeof(t.w));
+    *width = t.width;
+    return XRSFM_BA_OK;
+}
+
+namespace {
+struct SiftLevelsRequest { int image, octave; float* gauss; float* dog; };
+struct SiftResult {                           // of the whole call, held back until nothing can fail any more
+    std::vector<int32_t> level_count;                   // [n][num_octaves * 3], before the budget
+    std::vector<int64_t> count;                         // [n] keypoints after the budget
+    std::vector<std::vector<float>> keys, off;          // per image [count][4]
+    std::vector<std::vector<int32_t>> loc;              // per image [count][4]
+};
+
+// Everything after the argument checks.
+int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
+             const uint8_t* pixels, const SiftLevelsRequest* want, SiftResult* R) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int NL = opt->num_octaves * xsift::kKeyLevels;
+    R->level_count.assign((size_t)n_images * NL, 0); R->count.assign((size_t)n_images, 0);
+    R->keys.assign((size_t)n_images, {}); R->off.assign((size_t)n_images, {}); R->loc.assign((size_t)n_images, {});
+    const xsift::Params P = xsift::make_params(opt->first_octave, opt->peak_threshold, opt->edge_threshold);
+    xsift::Taps taps[xsift::kDog + 1];                  // the five level filters, then the initial smoothing
+    for (int i = 0; i < xsift::kDog; ++i) xsift::build_taps(P.level_sigma[i], &taps[i]);
+    if (P.init_sigma > 0.0f) xsift::build_taps(P.init_sigma, &taps[xsift::kDog]); else taps[xsift::kDog].width = 0;
+    std::vector<xsift::Geometry> geo((size_t)n_images);
+    std::vector<size_t> plane_floats((size_t)n_images, 0);
+    for (int i = 0; i < n_images; ++i) {
+        geo[(size_t)i] = xsift::geometry(width[i], height[i], opt->first_octave, opt->num_octaves);
+        for (int o = 0; o < geo[(size_t)i].n_oct; ++o) plane_floats[(size_t)i] += (size_t)kSiftPlanes * (size_t)geo[(size_t)i].w[o] * (size_t)geo[(size_t)i].h[o];
+    }
+    // chunks of images under the workspace budget (XRSFM_BA_SIFT_WORKSPACE_MB, default 4096); an image above it runs alone
+    size_t budget = (size_t)4096 << 20;
+    if (const char* s = getenv("XRSFM_BA_SIFT_WORKSPACE_MB")) { const long long mb = atoll(s); if (mb >= 0) budget = (size_t)mb << 20; }
+    std::vector<std::pair<int, int>> chunks;
+    {
+        int first = 0;
+        size_t bytes = 0;
+        for (int i = 0; i < n_images; ++i) {
+            const size_t b = al(plane_floats[(size_t)i] * sizeof(float)) + al((size_t)(pixel_ptr[i + 1] - pixel_ptr[i]));
+            if (i > first && bytes + b > budget) { chunks.push_back({first, i}); first = i; bytes = 0; }
+            bytes += b;
+        }
+        chunks.push_back({first, n_images});
+    }
+    HIPCHK(hipSetDevice(0));
+    HostBundle hb;
+    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
+    hipStream_t st = hb.stream;
+    // XRSFM_BA_SIFT_TIMING: the kernels' times from events on the stream, one line on stderr (tools/keypoint_timing.py)
+    struct Span { hipEvent_t a, b; int what; };
+    struct Events { std::vector<Span> ev; bool on = false; ~Events() { for (const Span& x : ev) { (void)hipEventDestroy(x.a); (void)hipEventDestroy(x.b); } } } tm;
+    tm.on = getenv("XRSFM_BA_SIFT_TIMING") != nullptr;
+    enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTN };
+    double ms[kTN] = {};
+    int e = 0;
+    struct Dev { void* p = nullptr; size_t cls = 0; ~Dev() { if (p) g_cache.put(0, p, cls); } };
+    struct Pin { unsigned char* p = nullptr; size_t cap = 0; ~Pin() { if (p) g_pinned.put(p, cap); } };
+    for (size_t ci = 0; ci < chunks.size() && !e; ++ci) {
+        const int i0 = chunks[ci].first, ni = chunks[ci].second - chunks[ci].first;
+        // layout of the chunk: [imgs | tiles | taps] uploaded, [tile slots] both ways, pixels, planes
+        std::vector<SiftImg> imgs((size_t)ni);
+        std::vector<SiftTile> tiles;
+        int oct_most = 0;
+        size_t tile_first[xsift::kMaxOctaves + 1] = {}, slot_first[xsift::kMaxOctaves + 1] = {};
+        int64_t pix = 0, fl = 0;
+        for (int q = 0; q < ni; ++q) {
+            const xsift::Geometry& g = geo[(size_t)(i0 + q)];
+            SiftImg& im = imgs[(size_t)q];
+            memset(&im, 0, sizeof(im));
+            im.pix_off = pix; pix += (int64_t)al((size_t)(pixel_ptr[i0 + q + 1] - pixel_ptr[i0 + q]));
+            im.stride = width[i0 + q]; im.w_in = g.w_in; im.h_in = g.h_in; im.n_oct = g.n_oct;
+            for (int o = 0; o < g.n_oct; ++o) { im.w[o] = g.w[o]; im.h[o] = g.h[o]; im.plane[o] = fl; fl += (int64_t)kSiftPlanes * g.w[o] * g.h[o]; }
+            fl = (int64_t)(al((size_t)fl * sizeof(float)) / sizeof(float));
+            oct_most = std::max(oct_most, (int)g.n_oct);
+        }
+        for (int o = 0; o < oct_most; ++o) {
+            tile_first[o] = tiles.size();
+            for (int q = 0; q < ni; ++q)
+                if (o < imgs[(size_t)q].n_oct)
+                    for (int ty = 0; ty < (imgs[(size_t)q].h[o] + kSiftTH - 1) / kSiftTH; ++ty)
+                        for (int tx = 0; tx < (imgs[(size_t)q].w[o] + kSiftTW - 1) / kSiftTW; ++tx) tiles.push_back(SiftTile{q, tx, ty, 0});
+            tile_first[o + 1] = tiles.size();
+            slot_first[o + 1] = slot_first[o] + (size_t)xsift::kKeyLevels * (tile_first[o + 1] - tile_first[o]);
+        }
+        const size_t n_slots = slot_first[oct_most];
+        const size_t o_img = 0, o_tile = o_img + al(sizeof(SiftImg) * (size_t)ni), o_taps = o_tile + al(sizeof(SiftTile) * tiles.size());
+        const size_t in_bytes = o_taps + al(sizeof(float) * xsift::kMaxTaps * (xsift::kDog + 1));
+        const size_t slot_bytes = al(sizeof(int32_t) * n_slots);           // three arrays: counts, first slots, emitted counts
+        const size_t o_slot = in_bytes, o_pix = o_slot + 3 * slot_bytes, o_planes = o_pix + al((size_t)pix);
+        const size_t total = o_planes + (size_t)fl * sizeof(float);
+        Dev ws;
+        ws.p = g_cache.get(0, total, &ws.cls);
+        Pin stage, pstage, slots;
+        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap);
+        pstage.p = (unsigned char*)g_pinned.get((size_t)pix ? (size_t)pix : 8, &pstage.cap);
+        slots.p = (unsigned char*)g_pinned.get(3 * slot_bytes, &slots.cap);
+        if (!ws.p || !stage.p || !pstage.p || !slots.p) { e = XRSFM_BA_ENOMEM; break; }
+        unsigned char* base = (unsigned char*)ws.p;
+        memcpy(stage.p + o_img, imgs.data(), sizeof(SiftImg) * (size_t)ni);
+        memcpy(stage.p + o_tile, tiles.data(), sizeof(SiftTile) * tiles.size());
+        for (int i = 0; i <= xsift::kDog; ++i) memcpy(stage.p + o_taps + sizeof(float) * xsift::kMaxTaps * (size_t)i, taps[i].w, sizeof(float) * xsift::kMaxTaps);
+        for (int q = 0; q < ni; ++q) memcpy(pstage.p + imgs[(size_t)q].pix_off, pixels + pixel_ptr[i0 + q], (size_t)(pixel_ptr[i0 + q + 1] - pixel_ptr[i0 + q]));
+        const SiftImg* d_img = (const SiftImg*)(base + o_img);
+        const SiftTile* d_tile = (const SiftTile*)(base + o_tile);
+        const float* d_taps = (const float*)(base + o_taps);
+        int32_t* d_cnt = (int32_t*)(base + o_slot);
+        int32_t* d_first = (int32_t*)(base + o_slot + slot_bytes);
+        int32_t* d_emit = (int32_t*)(base + o_slot + 2 * slot_bytes);
+        float* d_planes = (float*)(base + o_planes);
+        if (hipMemcpyAsync(base, stage.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(base + o_pix, pstage.p, (size_t)pix, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+        // one timed launch: events around it when timing is on
+        auto timed = [&](int what, auto&& launch) {
+            hipEvent_t a = nullptr, b = nullptr;
+            const bool on = tm.on && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+            if (on) (void)hipEventRecord(a, st);
+            launch();
+            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+            if (on) { (void)hipEventRecord(b, st); tm.ev.push_back(Span{a, b, what}); }
+            else if (a) (void)hipEventDestroy(a);
+        };
+        auto key_params = [&](int o) {
+            return SiftKeyParams{P.T0, P.T, P.E, P.step, xsift::octave_scale(opt->first_octave, o), P.key_sigma[0], P.key_sigma[1], P.key_sigma[2]};
+        };
+        const bool smooth = taps[xsift::kDog].width > 0;
+        for (int o = 0; o < oct_most && !e; ++o) {
+            const unsigned nt = (unsigned)(tile_first[o + 1] - tile_first[o]);
+            const SiftTile* tl = d_tile + tile_first[o];
+            if (o == 0) {
+                timed(kTBase, [&] { hipLaunchKernelGGL(k_sift_base, dim3(nt), dim3(kSiftThreads), 0, st, d_img, tl, (const uint8_t*)(base + o_pix), d_planes,
+                                                       (int)opt->first_octave, smooth ? kSiftScratchPlane : 0); });
+                if (smooth && !e)
+                    timed(kTInit, [&] { hipLaunchKernelGGL(k_sift_filter, dim3(nt), dim3(kSiftThreads), 0, st, d_img, tl, d_planes, 0, kSiftScratchPlane, 0, -1,
+                                                           d_taps + xsift::kMaxTaps * xsift::kDog, (int)taps[xsift::kDog].width); });
+            } else {
+                timed(kTDown, [&] { hipLaunchKernelGGL(k_sift_down, dim3(nt), dim3(kSiftThreads), 0, st, d_img, tl, d_planes, o); });
+            }
+            for (int i = 0; i < xsift::kDog && !e; ++i)
+                timed(kTFilter0 + i, [&] { hipLaunchKernelGGL(k_sift_filter, dim3(nt), dim3(kSiftThreads), 0, st, d_img, tl, d_planes, o, i, i + 1, xsift::kGauss + i,
+                                                              d_taps + xsift::kMaxTaps * i, (int)taps[i].width); });
+            if (!e)
+                timed(kTCount, [&] { hipLaunchKernelGGL(k_sift_key<false>, dim3(nt, xsift::kKeyLevels), dim3(kSiftThreads), 0, st, d_img, tl, (const float*)d_planes, o, (int)nt,
+                                                        key_params(o), d_cnt + slot_first[o], (const int32_t*)nullptr, (int32_t*)nullptr, (float4*)nullptr, (int4*)nullptr, (float4*)nullptr); });
+        }
+        if (e) { (void)hipStreamSynchronize(st); break; }
+        if (hipMemcpyAsync(slots.p, d_cnt, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+        // counts -> level_count -> budget -> the first slot of every (image, level) and of every tile
+        const int32_t* sl = (const int32_t*)slots.p;
+        int32_t* sl_first = (int32_t*)(slots.p + slot_bytes);
+        const int32_t* sl_emit = (const int32_t*)(slots.p + 2 * slot_bytes);
+        for (int o = 0; o < oct_most; ++o) {
+            const size_t nt = tile_first[o + 1] - tile_first[o];
+            for (int j = 0; j < xsift::kKeyLevels; ++j)
+                for (size_t t = 0; t < nt; ++t) {
+                    const int32_t c = sl[slot_first[o] + (size_t)j * nt + t];
+                    if (c < 0 || c > kSiftTW * kSiftTH) { e = XRSFM_BA_EINTERNAL; break; }
+                    R->level_count[(size_t)(i0 + tiles[tile_first[o] + t].img) * NL + (size_t)(o * xsift::kKeyLevels + j)] += c;
+                }
+        }
+        if (e) break;
+        std::vector<int64_t> level_first((size_t)ni * NL, -1);
+        int64_t n_keys = 0;
+        for (int q = 0; q < ni; ++q) {
+            uint8_t take[xsift::kMaxOctaves * xsift::kKeyLevels] = {};
+            const int32_t* lc = &R->level_count[(size_t)(i0 + q) * NL];
+            R->count[(size_t)(i0 + q)] = xsift::budget(lc, imgs[(size_t)q].n_oct, opt->max_num_features, take);
+            for (int l = 0; l < imgs[(size_t)q].n_oct * xsift::kKeyLevels; ++l)
+                if (take[l]) { level_first[(size_t)q * NL + l] = n_keys; n_keys += lc[l]; }
+        }
+        if (n_keys > 0x7fffffff) { e = XRSFM_BA_ETOOBIG; break; }
+        {
+            std::vector<int64_t> next = level_first;
+            for (int o = 0; o < oct_most; ++o) {
+                const size_t nt = tile_first[o + 1] - tile_first[o];
+                for (int j = 0; j < xsift::kKeyLevels; ++j)
+                    for (size_t t = 0; t < nt; ++t) {
+                        const size_t at = slot_first[o] + (size_t)j * nt + t;
+                        int64_t& nx = next[(size_t)tiles[tile_first[o] + t].img * NL + (size_t)(o * xsift::kKeyLevels + j)];
+                        const int32_t c = sl[at];
+                        sl_first[at] = nx < 0 || c == 0 ? -1 : (int32_t)nx;
+                        if (nx >= 0) nx += c;
+                    }
+            }
+        }
+        if (n_keys > 0) {
+            const size_t k_keys = 0, k_loc = al(16 * (size_t)n_keys), k_off = k_loc + al(16 * (size_t)n_keys), k_total = k_off + al(16 * (size_t)n_keys);
+            Dev kd;
+            kd.p = g_cache.get(0, k_total, &kd.cls);
+            Pin back;
+            back.p = (unsigned char*)g_pinned.get(k_total, &back.cap);
+            if (!kd.p || !back.p) { e = XRSFM_BA_ENOMEM; break; }
+            unsigned char* kb = (unsigned char*)kd.p;
+            if (hipMemcpyAsync(d_first, sl_first, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            for (int o = 0; o < oct_most && !e; ++o) {
+                const unsigned nt = (unsigned)(tile_first[o + 1] - tile_first[o]);
+                timed(kTEmit, [&] { hipLaunchKernelGGL(k_sift_key<true>, dim3(nt, xsift::kKeyLevels), dim3(kSiftThreads), 0, st, d_img, d_tile + tile_first[o], (const float*)d_planes,
+                                                       o, (int)nt, key_params(o), d_cnt + slot_first[o], (const int32_t*)(d_first + slot_first[o]), d_emit + slot_first[o], (float4*)(kb + k_keys),
+                                                       (int4*)(kb + k_loc), (float4*)(kb + k_off)); });
+            }
+            if (e) { (void)hipStreamSynchronize(st); break; }
+            if (hipMemcpyAsync(back.p, kb, k_total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(slots.p + 2 * slot_bytes, d_emit, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            // the two passes are separate instantiations of one decision: a tile that emitted another number than it counted would
+            // leave a slot unwritten (or would have been cut short by the kernel): refuse the call rather than hand that out
+            for (size_t at = 0; at < n_slots && !e; ++at)
+                if (sl_first[at] >= 0 && sl_emit[at] != sl[at]) {
+                    fprintf(stderr, "[xrsfm_ba] keypoint detection: a tile emitted %d keypoints where it had counted %d\n", (int)sl_emit[at], (int)sl[at]);
+                    e = XRSFM_BA_EINTERNAL;
+                }
+            if (e) break;
+            // every level into row-major order (the tiles wrote theirs in no fixed order)
+            const float* hk = (const float*)(back.p + k_keys); const int32_t* hl = (const int32_t*)(back.p + k_loc); const float* ho = (const float*)(back.p + k_off);
+            std::vector<std::pair<int64_t, int64_t>> order;
+            for (int q = 0; q < ni; ++q) {
+                const size_t img = (size_t)(i0 + q);
+                std::vector<float>& K = R->keys[img]; std::vector<float>& O = R->off[img]; std::vector<int32_t>& L = R->loc[img];
+                K.reserve(4 * (size_t)R->count[img]); O.reserve(4 * (size_t)R->count[img]); L.reserve(4 * (size_t)R->count[img]);
+                for (int l = 0; l < imgs[(size_t)q].n_oct * xsift::kKeyLevels; ++l) {
+                    const int64_t f = level_first[(size_t)q * NL + l];
+                    if (f < 0) continue;
+                    const int64_t c = R->level_count[img * NL + l];
+                    order.clear();
+                    for (int64_t k = f; k < f + c; ++k) order.push_back({(int64_t)hl[4 * k + 2] * imgs[(size_t)q].w[l / xsift::kKeyLevels] + hl[4 * k + 3], k});
+                    std::sort(order.begin(), order.end());
+                    for (const auto& pr : order) {
+                        K.insert(K.end(), hk + 4 * pr.second, hk + 4 * pr.second + 4);
+                        O.insert(O.end(), ho + 4 * pr.second, ho + 4 * pr.second + 4);
+                        L.insert(L.end(), hl + 4 * pr.second, hl + 4 * pr.second + 4);
+                    }
+                }
+            }
+        }
+        if (want && want->image >= i0 && want->image < i0 + ni) {
+            const SiftImg& im = imgs[(size_t)(want->image - i0)];
+            const size_t n = (size_t)im.w[want->octave] * (size_t)im.h[want->octave];
+            const float* src = d_planes + im.plane[want->octave];
+            if (hipMemcpy(want->gauss, src, sizeof(float) * n * xsift::kGauss, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(want->dog, src + n * xsift::kGauss, sizeof(float) * n * xsift::kDog, hipMemcpyDeviceToHost) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+        }
+    }
+    if (e) (void)hipStreamSynchronize(st);
+    if (tm.on && !e) {
+        for (const Span& x : tm.ev) {
+            float a = 0.f;
+            if (hipEventElapsedTime(&a, x.a, x.b) == hipSuccess) ms[x.what] += a;
+        }
+        fprintf(stderr, "[xrsfm_ba] sift timing: base %.4f ms, init %.4f ms, filter %.4f %.4f %.4f %.4f %.4f ms, down %.4f ms, count %.4f ms, emit %.4f ms, chunks %zu\n",
+                ms[kTBase], ms[kTInit], ms[kTFilter0], ms[kTFilter0 + 1], ms[kTFilter0 + 2], ms[kTFilter0 + 3], ms[kTFilter0 + 4], ms[kTDown], ms[kTCount], ms[kTEmit], chunks.size());
+    }
+    g_bundles.put(0, hb);
+    return e;
+}
+
+int sift_no_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the keypoint detection has no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    return 0;
+}
+
+// the checks of the options and of the images; what: the entry's name
+int sift_check(const char* who, const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
+               const uint8_t* pixels) {
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_images < 0) return bad("negative count");
+    if (opt->first_octave != -1 && opt->first_octave != 0) return bad("first_octave outside {-1, 0}");
+    if (opt->num_octaves < 1 || opt->num_octaves > XRSFM_BA_SIFT_MAX_OCTAVES) return bad("num_octaves outside 1 .. 8");
+    if (!std::isfinite(opt->peak_threshold) || !std::isfinite(opt->edge_threshold)) return bad("non-finite threshold");
+    if (opt->peak_threshold <= 0.0f || opt->edge_threshold <= 0.0f) return bad("non-positive threshold");
+    if (opt->max_num_features < 1) return bad("max_num_features < 1");
+    if (opt->max_image_size < 1) return bad("max_image_size < 1");
+    if (n_images == 0) return XRSFM_BA_OK;
+    if (!width || !height || !pixel_ptr || !pixels) return bad("NULL width, height, pixel_ptr or pixels");
+    if (pixel_ptr[0] != 0) return bad("pixel_ptr does not start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 0 || height[i] < 0) return bad("negative image size");
+        if (xsift::truncate_width(width[i]) < xsift::kMinSide || height[i] < xsift::kMinSide) return bad("a truncated width or a height below 16");
+        if (width[i] > opt->max_image_size || height[i] > opt->max_image_size) return bad("an image side above max_image_size (down-sampling of the input is not built)");
+        if (pixel_ptr[i + 1] - pixel_ptr[i] != (int64_t)width[i] * height[i]) return bad("pixel_ptr disagrees with width * height");
+    }
+    return XRSFM_BA_OK;
+}
+
+int detect_keypoints_impl(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
+                          const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign, int32_t* level_count) {
+    const char* who = "xrsfm_ba_detect_keypoints";
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (opt && capacity < 0) return bad("negative count");
+    if (int e = sift_check(who, opt, n_images, width, height, pixel_ptr, pixels)) return e;
+    if (n_images == 0) return XRSFM_BA_OK;
+    if (!key_ptr) return bad("NULL key_ptr");
+    if (capacity > 0 && (!keys || !loc || !sign)) return bad("NULL keys, loc or sign");
+    if (int e = sift_no_device()) return e;
+    SiftResult R;
+    if (int e = sift_run(opt, n_images, width, height, pixel_ptr, pixels, nullptr, &R)) return e;
+    key_ptr[0] = 0;
+    for (int i = 0; i < n_images; ++i) key_ptr[i + 1] = key_ptr[i] + R.count[(size_t)i];
+    if (level_count) memcpy(level_count, R.level_count.data(), sizeof(int32_t) * R.level_count.size());
+    if (key_ptr[n_images] > capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: capacity %lld is below the %lld keypoints of the call\n", who, (long long)capacity, (long long)key_ptr[n_images]);
+        return XRSFM_BA_EINVAL;
+    }
+    for (int i = 0; i < n_images; ++i) {
+        const size_t c = (size_t)R.count[(size_t)i];
+        if (!c) continue;
+        memcpy(keys + 4 * key_ptr[i], R.keys[(size_t)i].data(), sizeof(float) * 4 * c);
+        memcpy(loc + 4 * key_ptr[i], R.loc[(size_t)i].data(), sizeof(int32_t) * 4 * c);
+        for (size_t k = 0; k < c; ++k) sign[key_ptr[i] + (int64_t)k] = (int8_t)R.off[(size_t)i][4 * k];
+    }
+    return XRSFM_BA_OK;
+}
+
+int debug_sift_levels_impl(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int32_t octave, float* gauss, float* dog) {
+    const int64_t ptr[2] = {0, (int64_t)width * height};
+    if (int e = sift_check("xrsfm_ba_debug_sift_levels", opt, 1, &width, &height, ptr, pixels)) return e;
+    if (!gauss || !dog || octave < 0 || octave >= xsift::geometry(width, height, opt->first_octave, opt->num_octaves).n_oct) return XRSFM_BA_EINVAL;
+    if (int e = sift_no_device()) return e;
+    const SiftLevelsRequest want{0, octave, gauss, dog};
+    SiftResult R;
+    return sift_run(opt, 1, &width, &height, ptr, pixels, &want, &R);
+}
+
+int debug_sift_offsets_impl(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int64_t capacity, int64_t* n_keys,
+                            int32_t* loc, float* offsets) {
+    const int64_t ptr[2] = {0, (int64_t)width * height};
+    if (int e = sift_check("xrsfm_ba_debug_sift_offsets", opt, 1, &width, &height, ptr, pixels)) return e;
+    if (!n_keys || capacity < 0 || (capacity > 0 && (!loc || !offsets))) return XRSFM_BA_EINVAL;
+    if (int e = sift_no_device()) return e;
+    SiftResult R;
+    if (int e = sift_run(opt, 1, &width, &height, ptr, pixels, nullptr, &R)) return e;
+    *n_keys = R.count[0];
+    if (R.count[0] > capacity) return XRSFM_BA_EINVAL;
+    if (R.count[0] > 0) {
+        memcpy(loc, R.loc[0].data(), sizeof(int32_t) * 4 * (size_t)R.count[0]);
+        memcpy(offsets, R.off[0].data(), sizeof(float) * 4 * (size_t)R.count[0]);
+    }
+    return XRSFM_BA_OK;
+}
+}  // namespace
+
+int xrsfm_ba_detect_keypoints(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
+                              const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign, int32_t* level_count) {
+    return no_throw([&] { return detect_keypoints_impl(opt, n_images, width, height, pixel_ptr, pixels, capacity, key_ptr, keys, loc, sign, level_count); });
+}
+
+int xrsfm_ba_debug_sift_levels(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int32_t octave, float* gauss, float* dog) {
+    return no_throw([&] { return debug_sift_levels_impl(opt, width, height, pixels, octave, gauss, dog); });
+}
+
+int xrsfm_ba_debug_sift_offsets(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int64_t capacity, int64_t* n_keys,
+                                int32_t* loc, float* offsets) {
+    return no_throw([&] { return debug_sift_offsets_impl(opt, width, height, pixels, capacity, n_keys, loc, offsets); });
 }
 
 // ---------------------------------------------------------------- diagnostics
