@@ -882,6 +882,47 @@ int xrsfm_ba_debug_sift_levels(const xrsfm_ba_sift_options *opt, int32_t width, 
 int xrsfm_ba_debug_sift_offsets(const xrsfm_ba_sift_options *opt, int32_t width, int32_t height, const uint8_t *pixels, int64_t capacity,
                                 int64_t *n_keys, int32_t *loc /* [capacity][4] */, float *offsets /* [capacity][4] */);
 
+/* Batched SIFT orientation and descriptors: images to uint8 features, the whole of FeatureExtract (SiftExtractor::ExtractUINT8:
+ * SiftGPU::RunSIFT with one orientation per keypoint, reference 3rdparty/SiftGPU/ProgramCU.cu ComputeDOG_Kernel's gradient half,
+ * ComputeOrientation_Kernel, ComputeDescriptor_Kernel<false>, NormalizeDescriptor_Kernel, PyramidCU.cpp DownloadKeypoints; then
+ * sift_extractor.cc L1RootNormalizeFeatureDescriptors and sift_extractor.h FeatureDescriptorsToUnsignedByte).  The rule is restated
+ * in xrsfm_amd/csrc/ba_sift_desc_rule.h and DESIGN.md 5n; FP32 throughout.
+ *
+ * key_ptr, loc, sign, level_count and keys[k][0..2] are what xrsfm_ba_detect_keypoints returns for the same images and options, bit
+ * for bit and in the same order.
+ *   keys[k][3]      the orientation as DownloadKeypoints hands it out: (float) fmod(2 pi - w, 2 pi) in double on the float w of the
+ *                   orientation histogram's parabola; 0 with upright
+ *   desc[k]         the 128 bytes of ExtractUINT8, [cell = 4 iy + ix][8 bins]: desc with key_ptr is the desc / desc_ptr that
+ *                   xrsfm_ba_match_descriptors takes
+ *   desc_float[k]   may be NULL: what ExtractFLOAT returns, after the L1 root
+ * A parabola whose denominator is zero (the reference: NaN) has the offset 0.  A descriptor sample whose bin position theta rounds
+ * to exactly 8.0f is dropped, as ComputeDescriptor_Kernel<false> drops it.  Chunking under XRSFM_BA_SIFT_WORKSPACE_MB works as in
+ * xrsfm_ba_detect_keypoints, the budget counts the gradient planes (6 more floats per pixel of an octave), and the results do not
+ * depend on the split by a bit.
+ *
+ * Errors as in xrsfm_ba_detect_keypoints; XRSFM_BA_EINVAL before the device is touched, outputs untouched, also for a NULL dopt, an
+ * upright outside {0, 1} and a NULL desc with a capacity; when capacity is too small key_ptr and level_count are written and
+ * nothing else.  Not built: max_num_orientations 2, affine shape, domain-size pooling, the RECT descriptor, L2 as the final
+ * normalisation, existing-keypoint input. */
+typedef struct xrsfm_ba_sift_desc_options {
+    int32_t upright;   /* 0   sift_extractor.h; 1 = "-ofix": orientation 0, descriptors at angle 0 */
+} xrsfm_ba_sift_desc_options;
+void xrsfm_ba_sift_desc_options_default(xrsfm_ba_sift_desc_options *opt);
+int xrsfm_ba_extract_features(const xrsfm_ba_sift_options *opt, const xrsfm_ba_sift_desc_options *dopt, int32_t n_images,
+                              const int32_t *width, const int32_t *height, const int64_t *pixel_ptr, const uint8_t *pixels,
+                              int64_t capacity, int64_t *key_ptr, float *keys /* [capacity][4] */, int32_t *loc, int8_t *sign,
+                              uint8_t *desc /* [capacity][128] */, float *desc_float /* [capacity][128], may be NULL */,
+                              int32_t *level_count);
+/* TEST ENTRY: (grd, rot) of G[1..3] of one octave of one image, [3][h][w][2] with w the stored width; border pixels are (0, 0). */
+int xrsfm_ba_debug_sift_gradient(const xrsfm_ba_sift_options *opt, int32_t width, int32_t height, const uint8_t *pixels, int32_t octave,
+                                 float *grad /* [3][h][w][2] */);
+/* TEST ENTRY: per keypoint of one image, in the interface's order: okeys the octave-space key (x, y, sigma, w) the descriptor kernel
+ * read, raw the 128 sums before normalisation, unit the vector after the NormalizeDescriptor_Kernel arithmetic (what
+ * GetFeatureVector gives).  *n_keys is written even when capacity is too small (XRSFM_BA_EINVAL). */
+int xrsfm_ba_debug_sift_describe(const xrsfm_ba_sift_options *opt, const xrsfm_ba_sift_desc_options *dopt, int32_t width, int32_t height,
+                                 const uint8_t *pixels, int64_t capacity, int64_t *n_keys, int32_t *loc /* [capacity][4] */,
+                                 float *okeys /* [capacity][4] */, float *raw /* [capacity][128] */, float *unit /* [capacity][128] */);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

@@ -80,6 +80,10 @@ class CSiftOptions(C.Structure):
                 ("max_num_features", C.c_int32), ("max_image_size", C.c_int32)]
 
 
+class CSiftDescOptions(C.Structure):
+    _fields_ = [("upright", C.c_int32)]
+
+
 class CTriOptions(C.Structure):
     _fields_ = [("min_tri_angle_rad", C.c_double), ("max_error_rad", C.c_double), ("confidence", C.c_double),
                 ("min_inlier_ratio", C.c_double), ("max_num_trials", C.c_int32), ("exhaustive_threshold", C.c_int32)]
@@ -131,6 +135,7 @@ EXPORTS = [
     "xrsfm_ba_debug_cam_stage",
     "xrsfm_ba_sift_options_default", "xrsfm_ba_detect_keypoints", "xrsfm_ba_debug_sift_taps", "xrsfm_ba_debug_sift_levels",
     "xrsfm_ba_debug_sift_offsets",
+    "xrsfm_ba_sift_desc_options_default", "xrsfm_ba_extract_features", "xrsfm_ba_debug_sift_gradient", "xrsfm_ba_debug_sift_describe",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -317,6 +322,16 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_sift_levels.restype = C.c_int
     lib.xrsfm_ba_debug_sift_offsets.argtypes = [_so, C.c_int32, C.c_int32, _c_uint8_p, C.c_int64, _c_int64_p, _c_int32_p, _c_float_p]
     lib.xrsfm_ba_debug_sift_offsets.restype = C.c_int
+    _sd = C.POINTER(CSiftDescOptions)
+    lib.xrsfm_ba_sift_desc_options_default.argtypes = [_sd]
+    lib.xrsfm_ba_sift_desc_options_default.restype = None
+    lib.xrsfm_ba_extract_features.argtypes = [_so, _sd, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_uint8_p, C.c_int64, _c_int64_p, _c_float_p, _c_int32_p,
+                                               C.POINTER(C.c_int8), _c_uint8_p, _c_float_p, _c_int32_p]
+    lib.xrsfm_ba_extract_features.restype = C.c_int
+    lib.xrsfm_ba_debug_sift_gradient.argtypes = [_so, C.c_int32, C.c_int32, _c_uint8_p, C.c_int32, _c_float_p]
+    lib.xrsfm_ba_debug_sift_gradient.restype = C.c_int
+    lib.xrsfm_ba_debug_sift_describe.argtypes = [_so, _sd, C.c_int32, C.c_int32, _c_uint8_p, C.c_int64, _c_int64_p, _c_int32_p, _c_float_p, _c_float_p, _c_float_p]
+    lib.xrsfm_ba_debug_sift_describe.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1359,3 +1374,92 @@ def debug_sift_offsets(image, options: CSiftOptions | None = None) -> tuple:
         break
     check(code, "xrsfm_ba_debug_sift_offsets")
     return l[:n.value].copy(), f[:n.value].copy()
+
+
+def sift_desc_options(**overrides) -> CSiftDescOptions:
+    """xrsfm_ba_sift_desc_options_default: one orientation per keypoint, not upright."""
+    o = CSiftDescOptions()
+    load().xrsfm_ba_sift_desc_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def extract_features(images, options: CSiftOptions | None = None, desc_options: CSiftDescOptions | None = None, capacity: int | None = None,
+                     floats: bool = True) -> list:
+    """xrsfm_ba_extract_features on a list of 2-D uint8 arrays: per image the dict of detect_keypoints (keys[:, 3] now the
+    orientation) plus desc [n][128] uint8 and desc_float [n][128] (None with floats=False)."""
+    o = options if options is not None else sift_options()
+    do = desc_options if desc_options is not None else sift_desc_options()
+    imgs = [_grey(a) for a in images]
+    n = len(imgs)
+    w = np.array([a.shape[1] for a in imgs], np.int32); h = np.array([a.shape[0] for a in imgs], np.int32)
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:] = np.cumsum([a.size for a in imgs])
+    pix = np.concatenate([a.ravel() for a in imgs]) if n else np.zeros(0, np.uint8)
+    nl = max(int(o.num_octaves), 0) * 3
+    lc = np.zeros((n, nl), np.int32); kp = np.zeros(n + 1, np.int64)
+    lib = load()
+
+    def run(cap):
+        k = np.zeros((cap, 4), np.float32); l = np.zeros((cap, 4), np.int32); s = np.zeros(cap, np.int8)
+        d = np.zeros((cap, 128), np.uint8); f = np.zeros((cap, 128), np.float32) if floats else None
+        code = lib.xrsfm_ba_extract_features(C.byref(o), C.byref(do), n, w.ctypes.data_as(_c_int32_p), h.ctypes.data_as(_c_int32_p), ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             pix.ctypes.data_as(_c_uint8_p), cap, kp.ctypes.data_as(C.POINTER(C.c_int64)), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                             l.ctypes.data_as(_c_int32_p), s.ctypes.data_as(C.POINTER(C.c_int8)), d.ctypes.data_as(_c_uint8_p),
+                                             f.ctypes.data_as(C.POINTER(C.c_float)) if floats else None, lc.ctypes.data_as(_c_int32_p))
+        return code, k, l, s, d, f
+    first = max(n, 1) * min(max(int(o.max_num_features), 0) + 4096, 65536) if capacity is None else int(capacity)
+    code, k, l, s, d, f = run(first)
+    if code == EINVAL and capacity is None and n > 0 and kp[-1] > first:
+        code, k, l, s, d, f = run(int(kp[-1]))
+    check(code, "xrsfm_ba_extract_features")
+    return [dict(keys=k[kp[i]:kp[i + 1]].copy(), loc=l[kp[i]:kp[i + 1]].copy(), sign=s[kp[i]:kp[i + 1]].copy(), level_count=lc[i].copy(),
+                 desc=d[kp[i]:kp[i + 1]].copy(), desc_float=f[kp[i]:kp[i + 1]].copy() if floats else None) for i in range(n)]
+
+
+def feature_frames(results) -> tuple:
+    """(desc [N][128] uint8, desc_ptr [n + 1], keypoints_xy [N][2]) of extract_features' results, ready for match_descriptors and
+    matched_points."""
+    ptr = np.zeros(len(results) + 1, np.int64)
+    ptr[1:] = np.cumsum([len(r["desc"]) for r in results])
+    desc = np.concatenate([r["desc"] for r in results]) if results else np.zeros((0, 128), np.uint8)
+    xy = np.concatenate([r["keys"][:, :2] for r in results]) if results else np.zeros((0, 2), np.float32)
+    return np.ascontiguousarray(desc.reshape(-1, 128)), ptr, np.ascontiguousarray(xy.reshape(-1, 2).astype(np.float32))
+
+
+def debug_sift_gradient(image, octave: int, options: CSiftOptions | None = None) -> np.ndarray:
+    """xrsfm_ba_debug_sift_gradient: (grd, rot) of G[1..3] of one octave, [3][h][w][2]."""
+    o = options if options is not None else sift_options()
+    a = _grey(image)
+    geo = sift_geometry(a.shape[1], a.shape[0], o)
+    if not 0 <= octave < len(geo):
+        raise ValueError("debug_sift_gradient: the image has no such octave")
+    ws, hs = geo[octave]
+    g = np.zeros((3, hs, ws, 2), np.float32)
+    check(load().xrsfm_ba_debug_sift_gradient(C.byref(o), a.shape[1], a.shape[0], a.ctypes.data_as(_c_uint8_p), octave, g.ctypes.data_as(C.POINTER(C.c_float))),
+          "xrsfm_ba_debug_sift_gradient")
+    return g
+
+
+def debug_sift_describe(image, options: CSiftOptions | None = None, desc_options: CSiftDescOptions | None = None) -> dict:
+    """xrsfm_ba_debug_sift_describe: loc [n][4], okeys [n][4], raw [n][128], unit [n][128] of one image."""
+    o = options if options is not None else sift_options()
+    do = desc_options if desc_options is not None else sift_desc_options()
+    a = _grey(image)
+    n = C.c_int64(0)
+    cap = 4096
+    fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+    for _ in range(2):
+        l = np.zeros((cap, 4), np.int32); k = np.zeros((cap, 4), np.float32); r = np.zeros((cap, 128), np.float32); u = np.zeros((cap, 128), np.float32)
+        code = load().xrsfm_ba_debug_sift_describe(C.byref(o), C.byref(do), a.shape[1], a.shape[0], a.ctypes.data_as(_c_uint8_p), cap, C.byref(n),
+                                                   l.ctypes.data_as(_c_int32_p), fp(k), fp(r), fp(u))
+        if code == EINVAL and n.value > cap:
+            cap = int(n.value)
+            continue
+        break
+    check(code, "xrsfm_ba_debug_sift_describe")
+    m = n.value
+    return dict(loc=l[:m].copy(), okeys=k[:m].copy(), raw=r[:m].copy(), unit=u[:m].copy())

@@ -38,6 +38,7 @@
 #include "ba_match.h"
 #include "ba_refine.h"
 #include "ba_sift.h"
+#include "ba_sift_desc.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
 #include "ba_wide.h"
@@ -4414,21 +4415,30 @@ int xrsfm_ba_debug_sift_taps(float sigma, float* taps, int32_t* width) {
 }
 
 namespace {
-struct SiftLevelsRequest { int image, octave; float* gauss; float* dog; };
+struct SiftLevelsRequest { int image, octave; float* gauss; float* dog; float* grad; };          // each may be null
+// the second half (ba_sift_desc.h): null for xrsfm_ba_detect_keypoints
+struct SiftDescRequest { int upright; bool floats, stages; };          // stages: raw and unit of xrsfm_ba_debug_sift_describe
 struct SiftResult {                           // of the whole call, held back until nothing can fail any more
     std::vector<int32_t> level_count;                   // [n][num_octaves * 3], before the budget
     std::vector<int64_t> count;                         // [n] keypoints after the budget
     std::vector<std::vector<float>> keys, off;          // per image [count][4]
     std::vector<std::vector<int32_t>> loc;              // per image [count][4]
+    std::vector<std::vector<float>> okeys;              // per image [count][4]: the octave-space key (x, y, sigma, w)
+    std::vector<std::vector<uint8_t>> desc;             // per image [count][128]
+    std::vector<std::vector<float>> desc_float, raw, unit;
 };
 
 // Everything after the argument checks.
 int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
-             const uint8_t* pixels, const SiftLevelsRequest* want, SiftResult* R) {
+             const uint8_t* pixels, const SiftLevelsRequest* want, SiftResult* R, const SiftDescRequest* dq = nullptr) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int NL = opt->num_octaves * xsift::kKeyLevels;
     R->level_count.assign((size_t)n_images * NL, 0); R->count.assign((size_t)n_images, 0);
     R->keys.assign((size_t)n_images, {}); R->off.assign((size_t)n_images, {}); R->loc.assign((size_t)n_images, {});
+    R->okeys.assign((size_t)n_images, {}); R->desc.assign((size_t)n_images, {}); R->desc_float.assign((size_t)n_images, {});
+    R->raw.assign((size_t)n_images, {}); R->unit.assign((size_t)n_images, {});
+    const bool with_grad = dq || (want && want->grad);          // the gradient planes: 3 x float2 per pixel of an octave
+    const size_t plane_units = (size_t)kSiftPlanes + (with_grad ? 2 * (size_t)kSiftdGradPlanes : 0);
     const xsift::Params P = xsift::make_params(opt->first_octave, opt->peak_threshold, opt->edge_threshold);
     xsift::Taps taps[xsift::kDog + 1];                  // the five level filters, then the initial smoothing
     for (int i = 0; i < xsift::kDog; ++i) xsift::build_taps(P.level_sigma[i], &taps[i]);
@@ -4437,7 +4447,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
     std::vector<size_t> plane_floats((size_t)n_images, 0);
     for (int i = 0; i < n_images; ++i) {
         geo[(size_t)i] = xsift::geometry(width[i], height[i], opt->first_octave, opt->num_octaves);
-        for (int o = 0; o < geo[(size_t)i].n_oct; ++o) plane_floats[(size_t)i] += (size_t)kSiftPlanes * (size_t)geo[(size_t)i].w[o] * (size_t)geo[(size_t)i].h[o];
+        for (int o = 0; o < geo[(size_t)i].n_oct; ++o) plane_floats[(size_t)i] += plane_units * (size_t)geo[(size_t)i].w[o] * (size_t)geo[(size_t)i].h[o];
     }
     // chunks of images under the workspace budget (XRSFM_BA_SIFT_WORKSPACE_MB, default 4096); an image above it runs alone
     size_t budget = (size_t)4096 << 20;
@@ -4461,7 +4471,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
     struct Span { hipEvent_t a, b; int what; };
     struct Events { std::vector<Span> ev; bool on = false; ~Events() { for (const Span& x : ev) { (void)hipEventDestroy(x.a); (void)hipEventDestroy(x.b); } } } tm;
     tm.on = getenv("XRSFM_BA_SIFT_TIMING") != nullptr;
-    enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTN };
+    enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTGrad, kTRecord, kTOrient, kTDesc, kTN };
     double ms[kTN] = {};
     int e = 0;
     struct Dev { void* p = nullptr; size_t cls = 0; ~Dev() { if (p) g_cache.put(0, p, cls); } };
@@ -4470,6 +4480,8 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         const int i0 = chunks[ci].first, ni = chunks[ci].second - chunks[ci].first;
         // layout of the chunk: [imgs | tiles | taps] uploaded, [tile slots] both ways, pixels, planes
         std::vector<SiftImg> imgs((size_t)ni);
+        std::vector<SiftdImg> dimgs((size_t)ni);
+        int64_t gr = 0;                                     // float2 of the chunk's gradient planes
         std::vector<SiftTile> tiles;
         int oct_most = 0;
         size_t tile_first[xsift::kMaxOctaves + 1] = {}, slot_first[xsift::kMaxOctaves + 1] = {};
@@ -4480,7 +4492,8 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
             memset(&im, 0, sizeof(im));
             im.pix_off = pix; pix += (int64_t)al((size_t)(pixel_ptr[i0 + q + 1] - pixel_ptr[i0 + q]));
             im.stride = width[i0 + q]; im.w_in = g.w_in; im.h_in = g.h_in; im.n_oct = g.n_oct;
-            for (int o = 0; o < g.n_oct; ++o) { im.w[o] = g.w[o]; im.h[o] = g.h[o]; im.plane[o] = fl; fl += (int64_t)kSiftPlanes * g.w[o] * g.h[o]; }
+            for (int o = 0; o < g.n_oct; ++o) { im.w[o] = g.w[o]; im.h[o] = g.h[o]; im.plane[o] = fl; fl += (int64_t)kSiftPlanes * g.w[o] * g.h[o];
+                                               dimgs[(size_t)q].grad[o] = gr; if (with_grad) gr += (int64_t)kSiftdGradPlanes * g.w[o] * g.h[o]; }
             fl = (int64_t)(al((size_t)fl * sizeof(float)) / sizeof(float));
             oct_most = std::max(oct_most, (int)g.n_oct);
         }
@@ -4498,7 +4511,8 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         const size_t in_bytes = o_taps + al(sizeof(float) * xsift::kMaxTaps * (xsift::kDog + 1));
         const size_t slot_bytes = al(sizeof(int32_t) * n_slots);           // three arrays: counts, first slots, emitted counts
         const size_t o_slot = in_bytes, o_pix = o_slot + 3 * slot_bytes, o_planes = o_pix + al((size_t)pix);
-        const size_t total = o_planes + (size_t)fl * sizeof(float);
+        const size_t o_grad = o_planes + al((size_t)fl * sizeof(float));
+        const size_t total = o_grad + (size_t)gr * sizeof(float2);
         Dev ws;
         ws.p = g_cache.get(0, total, &ws.cls);
         Pin stage, pstage, slots;
@@ -4518,6 +4532,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         int32_t* d_first = (int32_t*)(base + o_slot + slot_bytes);
         int32_t* d_emit = (int32_t*)(base + o_slot + 2 * slot_bytes);
         float* d_planes = (float*)(base + o_planes);
+        float2* d_grad = (float2*)(base + o_grad);
         if (hipMemcpyAsync(base, stage.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipMemcpyAsync(base + o_pix, pstage.p, (size_t)pix, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
         // one timed launch: events around it when timing is on
@@ -4620,6 +4635,67 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                     e = XRSFM_BA_EINTERNAL;
                 }
             if (e) break;
+            // the second half on the keypoints of the chunk, while its planes are resident: gradient planes of the levels that keep a
+            // keypoint, one record per keypoint, orientation, descriptor; then ONE read-back of keys, bytes and the optional floats
+            Dev dd;
+            Pin dback, dstage;
+            const size_t nk = (size_t)n_keys;
+            const size_t d_okey = 0, d_desc = al(16 * nk), d_float = d_desc + al(128 * nk), d_raw = d_float + (dq && dq->floats ? al(512 * nk) : 0),
+                         d_unit = d_raw + (dq && dq->stages ? al(512 * nk) : 0), d_out = d_unit + (dq && dq->stages ? al(512 * nk) : 0), d_rec = d_out;
+            std::vector<int32_t> need((size_t)ni * NL, 0);
+            std::vector<SiftdLevel> levels;
+            for (int q = 0; q < ni; ++q)
+                for (int l = 0; l < imgs[(size_t)q].n_oct * xsift::kKeyLevels; ++l) {
+                    const int64_t f = level_first[(size_t)q * NL + l];
+                    const int32_t c = R->level_count[(size_t)(i0 + q) * NL + l];
+                    const int o = l / xsift::kKeyLevels, j = l % xsift::kKeyLevels;
+                    if (dq && f >= 0 && c > 0) {
+                        need[(size_t)q * NL + l] = 1;
+                        levels.push_back(SiftdLevel{f, dimgs[(size_t)q].grad[o] + (int64_t)j * imgs[(size_t)q].w[o] * imgs[(size_t)q].h[o], c, imgs[(size_t)q].w[o],
+                                                    imgs[(size_t)q].h[o], 0, P.key_sigma[j], P.step});
+                    }
+                }
+            if (dq) {
+                const size_t u_dimg = 0, u_need = al(sizeof(SiftdImg) * (size_t)ni), u_lev = u_need + al(sizeof(int32_t) * need.size()),
+                             u_total = u_lev + al(sizeof(SiftdLevel) * levels.size());
+                const size_t d_up = d_rec + al(sizeof(SiftdRec) * nk);
+                dd.p = g_cache.get(0, d_up + u_total, &dd.cls);
+                dback.p = (unsigned char*)g_pinned.get(d_out, &dback.cap);
+                dstage.p = (unsigned char*)g_pinned.get(u_total, &dstage.cap);
+                if (!dd.p || !dback.p || !dstage.p) { e = XRSFM_BA_ENOMEM; break; }
+                unsigned char* db = (unsigned char*)dd.p;
+                memcpy(dstage.p + u_dimg, dimgs.data(), sizeof(SiftdImg) * (size_t)ni);
+                memcpy(dstage.p + u_need, need.data(), sizeof(int32_t) * need.size());
+                memcpy(dstage.p + u_lev, levels.data(), sizeof(SiftdLevel) * levels.size());
+                if (hipMemcpyAsync(db + d_up, dstage.p, u_total, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+                const SiftdImg* dv_img = (const SiftdImg*)(db + d_up + u_dimg);
+                const int32_t* dv_need = (const int32_t*)(db + d_up + u_need);
+                const SiftdLevel* dv_lev = (const SiftdLevel*)(db + d_up + u_lev);
+                SiftdRec* dv_rec = (SiftdRec*)(db + d_rec);
+                for (int o = 0; o < oct_most && !e; ++o) {
+                    bool any = false;
+                    for (int q = 0; q < ni; ++q)
+                        for (int j = 0; j < xsift::kKeyLevels; ++j) any = any || need[(size_t)q * NL + (size_t)(o * xsift::kKeyLevels + j)];
+                    if (!any) continue;
+                    const unsigned nt = (unsigned)(tile_first[o + 1] - tile_first[o]);
+                    timed(kTGrad, [&] { hipLaunchKernelGGL(k_siftd_grad, dim3(nt, xsift::kKeyLevels), dim3(kSiftThreads), 0, st, d_img, dv_img, d_tile + tile_first[o],
+                                                           (const float*)d_planes, d_grad, dv_need, o, NL); });
+                }
+                if (!e) timed(kTRecord, [&] { hipLaunchKernelGGL(k_siftd_record, dim3((unsigned)levels.size()), dim3(kSiftThreads), 0, st, dv_lev, (const int4*)(kb + k_loc),
+                                                                 (const float4*)(kb + k_off), dv_rec); });
+                if (!e && !dq->upright)
+                    timed(kTOrient, [&] { hipLaunchKernelGGL(k_siftd_orient, dim3((unsigned)((nk + kSiftdOrientKeys - 1) / kSiftdOrientKeys)), dim3(kSiftThreads), 0, st, dv_rec,
+                                                             (int64_t)n_keys, (const float2*)d_grad); });
+                if (!e) timed(kTDesc, [&] { hipLaunchKernelGGL(k_siftd_desc, dim3((unsigned)((nk + kSiftdDescKeys - 1) / kSiftdDescKeys)), dim3(kSiftThreads), 0, st,
+                                                               (const SiftdRec*)dv_rec, (int64_t)n_keys, (const float2*)d_grad, (int)dq->upright, (float4*)(db + d_okey), db + d_desc,
+                                                               dq->floats ? (float*)(db + d_float) : (float*)nullptr, dq->stages ? (float*)(db + d_raw) : (float*)nullptr,
+                                                               dq->stages ? (float*)(db + d_unit) : (float*)nullptr); });
+                if (e) { (void)hipStreamSynchronize(st); break; }
+                if (hipMemcpyAsync(dback.p, db, d_out, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            }
+            const unsigned char* hd = dq ? dback.p : back.p;          // (without the second half none of these is read)
+            const float* h_ok = (const float*)(hd + d_okey); const uint8_t* h_ds = hd + d_desc; const float* h_fl = (const float*)(hd + d_float);
+            const float* h_raw = (const float*)(hd + d_raw); const float* h_un = (const float*)(hd + d_unit);
             // every level into row-major order (the tiles wrote theirs in no fixed order)
             const float* hk = (const float*)(back.p + k_keys); const int32_t* hl = (const int32_t*)(back.p + k_loc); const float* ho = (const float*)(back.p + k_off);
             std::vector<std::pair<int64_t, int64_t>> order;
@@ -4638,6 +4714,14 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                         K.insert(K.end(), hk + 4 * pr.second, hk + 4 * pr.second + 4);
                         O.insert(O.end(), ho + 4 * pr.second, ho + 4 * pr.second + 4);
                         L.insert(L.end(), hl + 4 * pr.second, hl + 4 * pr.second + 4);
+                        if (!dq) continue;
+                        R->okeys[img].insert(R->okeys[img].end(), h_ok + 4 * pr.second, h_ok + 4 * pr.second + 4);
+                        R->desc[img].insert(R->desc[img].end(), h_ds + 128 * pr.second, h_ds + 128 * pr.second + 128);
+                        if (dq->floats) R->desc_float[img].insert(R->desc_float[img].end(), h_fl + 128 * pr.second, h_fl + 128 * pr.second + 128);
+                        if (dq->stages) {
+                            R->raw[img].insert(R->raw[img].end(), h_raw + 128 * pr.second, h_raw + 128 * pr.second + 128);
+                            R->unit[img].insert(R->unit[img].end(), h_un + 128 * pr.second, h_un + 128 * pr.second + 128);
+                        }
                     }
                 }
             }
@@ -4646,8 +4730,26 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
             const SiftImg& im = imgs[(size_t)(want->image - i0)];
             const size_t n = (size_t)im.w[want->octave] * (size_t)im.h[want->octave];
             const float* src = d_planes + im.plane[want->octave];
-            if (hipMemcpy(want->gauss, src, sizeof(float) * n * xsift::kGauss, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(want->dog, src + n * xsift::kGauss, sizeof(float) * n * xsift::kDog, hipMemcpyDeviceToHost) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (want->gauss && (hipMemcpy(want->gauss, src, sizeof(float) * n * xsift::kGauss, hipMemcpyDeviceToHost) != hipSuccess ||
+                                hipMemcpy(want->dog, src + n * xsift::kGauss, sizeof(float) * n * xsift::kDog, hipMemcpyDeviceToHost) != hipSuccess)) { e = XRSFM_BA_ENODEV; break; }
+            if (want->grad) {                                   // all three planes of the octave, whether a keypoint needs them or not
+                const int oc = want->octave;
+                std::vector<int32_t> all((size_t)ni * NL, 1);
+                Dev gd;
+                const size_t g_need = al(sizeof(SiftdImg) * (size_t)ni), g_total = g_need + al(sizeof(int32_t) * all.size());
+                gd.p = g_cache.get(0, g_total, &gd.cls);
+                if (!gd.p) { e = XRSFM_BA_ENOMEM; break; }
+                unsigned char* gb = (unsigned char*)gd.p;
+                if (hipMemcpy(gb, dimgs.data(), sizeof(SiftdImg) * (size_t)ni, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(gb + g_need, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+                const unsigned nt = (unsigned)(tile_first[oc + 1] - tile_first[oc]);
+                hipLaunchKernelGGL(k_siftd_grad, dim3(nt, xsift::kKeyLevels), dim3(kSiftThreads), 0, st, d_img, (const SiftdImg*)gb, d_tile + tile_first[oc], (const float*)d_planes,
+                                   d_grad, (const int32_t*)(gb + g_need), oc, NL);
+                if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+                    hipMemcpy(want->grad, d_grad + dimgs[(size_t)(want->image - i0)].grad[oc], sizeof(float2) * n * kSiftdGradPlanes, hipMemcpyDeviceToHost) != hipSuccess) {
+                    e = XRSFM_BA_ENODEV; break;
+                }
+            }
         }
     }
     if (e) (void)hipStreamSynchronize(st);
@@ -4658,6 +4760,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         }
         fprintf(stderr, "[xrsfm_ba] sift timing: base %.4f ms, init %.4f ms, filter %.4f %.4f %.4f %.4f %.4f ms, down %.4f ms, count %.4f ms, emit %.4f ms, chunks %zu\n",
                 ms[kTBase], ms[kTInit], ms[kTFilter0], ms[kTFilter0 + 1], ms[kTFilter0 + 2], ms[kTFilter0 + 3], ms[kTFilter0 + 4], ms[kTDown], ms[kTCount], ms[kTEmit], chunks.size());
+        if (dq) fprintf(stderr, "[xrsfm_ba] sift descriptor timing: grad %.4f ms, record %.4f ms, orient %.4f ms, desc %.4f ms\n", ms[kTGrad], ms[kTRecord], ms[kTOrient], ms[kTDesc]);
     }
     g_bundles.put(0, hb);
     return e;
@@ -4696,18 +4799,23 @@ int sift_check(const char* who, const xrsfm_ba_sift_options* opt, int32_t n_imag
     return XRSFM_BA_OK;
 }
 
-int detect_keypoints_impl(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
-                          const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign, int32_t* level_count) {
-    const char* who = "xrsfm_ba_detect_keypoints";
+// xrsfm_ba_detect_keypoints (dopt, desc and desc_float null, with_desc false) and xrsfm_ba_extract_features: one body
+int sift_features_impl(const char* who, bool with_desc, const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width,
+                       const int32_t* height, const int64_t* pixel_ptr, const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign,
+                       uint8_t* desc, float* desc_float, int32_t* level_count) {
     auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
     if (opt && capacity < 0) return bad("negative count");
+    if (opt && with_desc && !dopt) return bad("NULL descriptor options");
+    if (opt && with_desc && dopt->upright != 0 && dopt->upright != 1) return bad("upright outside {0, 1}");
     if (int e = sift_check(who, opt, n_images, width, height, pixel_ptr, pixels)) return e;
     if (n_images == 0) return XRSFM_BA_OK;
     if (!key_ptr) return bad("NULL key_ptr");
     if (capacity > 0 && (!keys || !loc || !sign)) return bad("NULL keys, loc or sign");
+    if (capacity > 0 && with_desc && !desc) return bad("NULL desc");
     if (int e = sift_no_device()) return e;
     SiftResult R;
-    if (int e = sift_run(opt, n_images, width, height, pixel_ptr, pixels, nullptr, &R)) return e;
+    const SiftDescRequest dq{with_desc ? (int)dopt->upright : 0, desc_float != nullptr, false};
+    if (int e = sift_run(opt, n_images, width, height, pixel_ptr, pixels, nullptr, &R, with_desc ? &dq : nullptr)) return e;
     key_ptr[0] = 0;
     for (int i = 0; i < n_images; ++i) key_ptr[i + 1] = key_ptr[i] + R.count[(size_t)i];
     if (level_count) memcpy(level_count, R.level_count.data(), sizeof(int32_t) * R.level_count.size());
@@ -4721,6 +4829,42 @@ int detect_keypoints_impl(const xrsfm_ba_sift_options* opt, int32_t n_images, co
         memcpy(keys + 4 * key_ptr[i], R.keys[(size_t)i].data(), sizeof(float) * 4 * c);
         memcpy(loc + 4 * key_ptr[i], R.loc[(size_t)i].data(), sizeof(int32_t) * 4 * c);
         for (size_t k = 0; k < c; ++k) sign[key_ptr[i] + (int64_t)k] = (int8_t)R.off[(size_t)i][4 * k];
+        if (!with_desc) continue;
+        for (size_t k = 0; k < c; ++k) keys[4 * (key_ptr[i] + (int64_t)k) + 3] = xsiftd::mirror(R.okeys[(size_t)i][4 * k + 3]);          // DownloadKeypoints
+        memcpy(desc + 128 * key_ptr[i], R.desc[(size_t)i].data(), 128 * c);
+        if (desc_float) memcpy(desc_float + 128 * key_ptr[i], R.desc_float[(size_t)i].data(), sizeof(float) * 128 * c);
+    }
+    return XRSFM_BA_OK;
+}
+
+int debug_sift_gradient_impl(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int32_t octave, float* grad) {
+    const int64_t ptr[2] = {0, (int64_t)width * height};
+    if (int e = sift_check("xrsfm_ba_debug_sift_gradient", opt, 1, &width, &height, ptr, pixels)) return e;
+    if (!grad || octave < 0 || octave >= xsift::geometry(width, height, opt->first_octave, opt->num_octaves).n_oct) return XRSFM_BA_EINVAL;
+    if (int e = sift_no_device()) return e;
+    const SiftLevelsRequest want{0, octave, nullptr, nullptr, grad};
+    SiftResult R;
+    return sift_run(opt, 1, &width, &height, ptr, pixels, &want, &R);
+}
+
+int debug_sift_describe_impl(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t width, int32_t height, const uint8_t* pixels,
+                             int64_t capacity, int64_t* n_keys, int32_t* loc, float* okeys, float* raw, float* unit) {
+    const int64_t ptr[2] = {0, (int64_t)width * height};
+    if (int e = sift_check("xrsfm_ba_debug_sift_describe", opt, 1, &width, &height, ptr, pixels)) return e;
+    if (!dopt || (dopt->upright != 0 && dopt->upright != 1)) return XRSFM_BA_EINVAL;
+    if (!n_keys || capacity < 0 || (capacity > 0 && (!loc || !okeys || !raw || !unit))) return XRSFM_BA_EINVAL;
+    if (int e = sift_no_device()) return e;
+    SiftResult R;
+    const SiftDescRequest dq{(int)dopt->upright, false, true};
+    if (int e = sift_run(opt, 1, &width, &height, ptr, pixels, nullptr, &R, &dq)) return e;
+    *n_keys = R.count[0];
+    if (R.count[0] > capacity) return XRSFM_BA_EINVAL;
+    if (R.count[0] > 0) {
+        const size_t c = (size_t)R.count[0];
+        memcpy(loc, R.loc[0].data(), sizeof(int32_t) * 4 * c);
+        memcpy(okeys, R.okeys[0].data(), sizeof(float) * 4 * c);
+        memcpy(raw, R.raw[0].data(), sizeof(float) * 128 * c);
+        memcpy(unit, R.unit[0].data(), sizeof(float) * 128 * c);
     }
     return XRSFM_BA_OK;
 }
@@ -4755,7 +4899,29 @@ int debug_sift_offsets_impl(const xrsfm_ba_sift_options* opt, int32_t width, int
 
 int xrsfm_ba_detect_keypoints(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
                               const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign, int32_t* level_count) {
-    return no_throw([&] { return detect_keypoints_impl(opt, n_images, width, height, pixel_ptr, pixels, capacity, key_ptr, keys, loc, sign, level_count); });
+    return no_throw([&] { return sift_features_impl("xrsfm_ba_detect_keypoints", false, opt, nullptr, n_images, width, height, pixel_ptr, pixels, capacity, key_ptr, keys, loc, sign,
+                                                    nullptr, nullptr, level_count); });
+}
+
+void xrsfm_ba_sift_desc_options_default(xrsfm_ba_sift_desc_options* opt) {
+    if (!opt) return;
+    opt->upright = 0;                         // sift_extractor.h
+}
+
+int xrsfm_ba_extract_features(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width, const int32_t* height,
+                              const int64_t* pixel_ptr, const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign, uint8_t* desc,
+                              float* desc_float, int32_t* level_count) {
+    return no_throw([&] { return sift_features_impl("xrsfm_ba_extract_features", true, opt, dopt, n_images, width, height, pixel_ptr, pixels, capacity, key_ptr, keys, loc, sign,
+                                                    desc, desc_float, level_count); });
+}
+
+int xrsfm_ba_debug_sift_gradient(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int32_t octave, float* grad) {
+    return no_throw([&] { return debug_sift_gradient_impl(opt, width, height, pixels, octave, grad); });
+}
+
+int xrsfm_ba_debug_sift_describe(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t width, int32_t height, const uint8_t* pixels,
+                                 int64_t capacity, int64_t* n_keys, int32_t* loc, float* okeys, float* raw, float* unit) {
+    return no_throw([&] { return debug_sift_describe_impl(opt, dopt, width, height, pixels, capacity, n_keys, loc, okeys, raw, unit); });
 }
 
 int xrsfm_ba_debug_sift_levels(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int32_t octave, float* gauss, float* dog) {
