@@ -923,6 +923,59 @@ int xrsfm_ba_debug_sift_describe(const xrsfm_ba_sift_options *opt, const xrsfm_b
                                  const uint8_t *pixels, int64_t capacity, int64_t *n_keys, int32_t *loc /* [capacity][4] */,
                                  float *okeys /* [capacity][4] */, float *raw /* [capacity][128] */, float *unit /* [capacity][128] */);
 
+/* Device-resident frame sets: the features of n frames held on device 0, filled from pixels or from existing features, on which
+ * FeatureMatching (match, gather of the matched key points, verification, acceptance) runs any number of times with only pair
+ * lists going up and matches and verdicts coming down (reference FeatureExtract + FeatureMatching + ExpansionAndMatching,
+ * src/feature/feature_processing.cc:118-377).  Every output equals, bit for bit, what the chain
+ * xrsfm_ba_extract_features -> xrsfm_ba_match_descriptors -> gather on the host -> xrsfm_ba_verify_pairs gives.
+ *
+ * A set is immutable after its creation.  It may be used from one thread at a time (two threads may use two sets).  Its device
+ * memory comes from the library's allocation cache and returns to it with xrsfm_ba_frames_destroy; xrsfm_ba_quiesce does not free
+ * live sets.  A set holds, per key point, the 16 bytes of its key, its 128 descriptor bytes and 4 bytes of the matching kernels'
+ * per-descriptor term, computed once at creation; a set made from images holds 21 bytes more (loc, sign, the orientation).
+ *
+ * The coordinate of key point k in the verification is ((double) keys[k][0], (double) keys[k][1]).  opt->max_features of the match
+ * options clips a frame at match time as in xrsfm_ba_match_descriptors; the set stores every key point.
+ *
+ * Errors: every argument check runs on the host before the device is touched and prints one line on stderr that names the entry;
+ * on any negative code no output is touched, and the creators do not write *out.  n_frames == 0 gives a valid empty set without a
+ * device, and so does a set without key points; n_pairs == 0 is success.  Without a device the creators with work to do and
+ * xrsfm_ba_frames_match return XRSFM_BA_ENODEV: there is no CPU path.  A frame above INT32_MAX key points, or a call whose matches
+ * exceed INT32_MAX, is XRSFM_BA_ETOOBIG. */
+typedef struct xrsfm_ba_frames xrsfm_ba_frames;   /* opaque */
+
+/* From existing features: keys [n][4] float as xrsfm_ba_extract_features returns them (x, y, scale, orientation; the matching reads
+ * x and y, which must be finite), desc [n][128]; frame f owns rows key_ptr[f] .. key_ptr[f+1]. */
+int xrsfm_ba_frames_create(int32_t n_frames, const int64_t *key_ptr, const float *keys, const uint8_t *desc, xrsfm_ba_frames **out);
+
+/* From pixels: xrsfm_ba_extract_features straight into a set, with the arguments and argument checks of that call and no capacity.
+ * The key points are put into the interface's order on the device (k_frames_order) and never visit the host. */
+int xrsfm_ba_frames_from_images(const xrsfm_ba_sift_options *opt, const xrsfm_ba_sift_desc_options *dopt, int32_t n_images,
+                                const int32_t *width, const int32_t *height, const int64_t *pixel_ptr, const uint8_t *pixels,
+                                xrsfm_ba_frames **out);
+
+int xrsfm_ba_frames_info(const xrsfm_ba_frames *fs, int32_t *n_frames, int64_t *key_ptr /* [n_frames+1], may be NULL */,
+                         uint64_t *device_bytes /* may be NULL: bytes held from the allocation cache */);
+
+/* What xrsfm_ba_extract_features would have returned (each output may be NULL: not wanted).  loc, sign and level_count exist only
+ * for sets made from images (they must be NULL otherwise: XRSFM_BA_EINVAL); a capacity below key_ptr[n_frames] is XRSFM_BA_EINVAL,
+ * outputs untouched. */
+int xrsfm_ba_frames_download(const xrsfm_ba_frames *fs, int64_t capacity, float *keys, uint8_t *desc, int32_t *loc, int8_t *sign,
+                             int32_t *level_count);
+
+/* FeatureMatching on resident frames: xrsfm_ba_match_descriptors, the gather of the matched key points, and, with vopt != NULL,
+ * xrsfm_ba_verify_pairs on them.  Outputs and their meaning are those of the two calls (match_ptr [n_pairs+1], matches
+ * [matches_capacity][2]; a capacity below the matches of the call is XRSFM_BA_EINVAL and the line on stderr names the need); the
+ * verification outputs must be NULL when vopt is NULL. */
+int xrsfm_ba_frames_match(const xrsfm_ba_frames *fs, const xrsfm_ba_match_options *mopt, const xrsfm_ba_fund_options *vopt,
+                          int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                          const double *pair_max_error, const uint32_t *pair_seed, int64_t matches_capacity,
+                          int64_t *match_ptr, int32_t *matches, int32_t *num_row, int32_t *num_col,
+                          uint8_t *status, double *F, uint8_t *inlier_mask, int32_t *num_inliers, int32_t *num_trials,
+                          int32_t *best_trial, uint8_t *accepted);
+
+void xrsfm_ba_frames_destroy(xrsfm_ba_frames *fs);   /* NULL is fine */
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

@@ -136,6 +136,8 @@ EXPORTS = [
     "xrsfm_ba_sift_options_default", "xrsfm_ba_detect_keypoints", "xrsfm_ba_debug_sift_taps", "xrsfm_ba_debug_sift_levels",
     "xrsfm_ba_debug_sift_offsets",
     "xrsfm_ba_sift_desc_options_default", "xrsfm_ba_extract_features", "xrsfm_ba_debug_sift_gradient", "xrsfm_ba_debug_sift_describe",
+    "xrsfm_ba_frames_create", "xrsfm_ba_frames_from_images", "xrsfm_ba_frames_info", "xrsfm_ba_frames_download", "xrsfm_ba_frames_match",
+    "xrsfm_ba_frames_destroy",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -332,6 +334,21 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_sift_gradient.restype = C.c_int
     lib.xrsfm_ba_debug_sift_describe.argtypes = [_so, _sd, C.c_int32, C.c_int32, _c_uint8_p, C.c_int64, _c_int64_p, _c_int32_p, _c_float_p, _c_float_p, _c_float_p]
     lib.xrsfm_ba_debug_sift_describe.restype = C.c_int
+    _u32_p, _u64_p, _i8_p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int8)
+    lib.xrsfm_ba_frames_create.argtypes = [C.c_int32, _c_int64_p, _c_float_p, _c_uint8_p, C.POINTER(vp)]
+    lib.xrsfm_ba_frames_create.restype = C.c_int
+    lib.xrsfm_ba_frames_from_images.argtypes = [_so, _sd, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_uint8_p, C.POINTER(vp)]
+    lib.xrsfm_ba_frames_from_images.restype = C.c_int
+    lib.xrsfm_ba_frames_info.argtypes = [vp, _c_int32_p, _c_int64_p, _u64_p]
+    lib.xrsfm_ba_frames_info.restype = C.c_int
+    lib.xrsfm_ba_frames_download.argtypes = [vp, C.c_int64, _c_float_p, _c_uint8_p, _c_int32_p, _i8_p, _c_int32_p]
+    lib.xrsfm_ba_frames_download.restype = C.c_int
+    lib.xrsfm_ba_frames_match.argtypes = [vp, C.POINTER(CMatchOptions), C.POINTER(CFundOptions), C.c_int32, _c_int32_p, _c_int32_p, _c_double_p, _u32_p, C.c_int64,
+                                          _c_int64_p, _c_int32_p, _c_int32_p, _c_int32_p, _c_uint8_p, _c_double_p, _c_uint8_p, _c_int32_p, _c_int32_p, _c_int32_p,
+                                          _c_uint8_p]
+    lib.xrsfm_ba_frames_match.restype = C.c_int
+    lib.xrsfm_ba_frames_destroy.argtypes = [vp]
+    lib.xrsfm_ba_frames_destroy.restype = None
     _lib = lib
     return lib
 
@@ -1428,6 +1445,155 @@ def feature_frames(results) -> tuple:
     desc = np.concatenate([r["desc"] for r in results]) if results else np.zeros((0, 128), np.uint8)
     xy = np.concatenate([r["keys"][:, :2] for r in results]) if results else np.zeros((0, 2), np.float32)
     return np.ascontiguousarray(desc.reshape(-1, 128)), ptr, np.ascontiguousarray(xy.reshape(-1, 2).astype(np.float32))
+
+
+_default_match_options = match_options      # (frames_match has a parameter of that name)
+
+
+class Frames:
+    """A device-resident frame set (xrsfm_ba_frames): the features of n frames on device 0, immutable, for one thread at a time.
+    A context manager; close() and __del__ give its device memory back."""
+
+    def __init__(self, handle, from_images: bool, num_levels: int = 0):
+        self.handle, self.from_images, self.num_levels = handle, from_images, num_levels
+
+    def close(self):
+        if getattr(self, "handle", None):
+            load().xrsfm_ba_frames_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _h(self):
+        if not self.handle:
+            raise RuntimeError("the frame set is closed")
+        return self.handle
+
+
+def frames_create(key_ptr, keys, desc) -> Frames:
+    """xrsfm_ba_frames_create: a set from existing features (keys [N][4] float32 as extract_features returns them, or [N][2]: x, y;
+    desc [N][128] uint8; frame f owns rows key_ptr[f] .. key_ptr[f+1])."""
+    key_ptr = np.ascontiguousarray(key_ptr, np.int64)
+    k = np.asarray(keys, np.float32)
+    k = k.reshape(-1, 4) if k.ndim == 1 else k
+    if k.ndim != 2 or k.shape[1] not in (2, 4) or key_ptr.ndim != 1 or len(key_ptr) < 1:
+        raise ValueError("frames_create: inconsistent array shapes")
+    if k.shape[1] == 2:
+        k = np.concatenate([k, np.zeros((len(k), 2), np.float32)], axis=1)
+    k = np.ascontiguousarray(k, np.float32)
+    d = _desc2d(desc)
+    if len(k) != len(d) or key_ptr[-1] != len(d):
+        raise ValueError("frames_create: key_ptr[-1] must be the number of key points and of descriptors")
+    h = C.c_void_p()
+    check(load().xrsfm_ba_frames_create(len(key_ptr) - 1, key_ptr.ctypes.data_as(C.POINTER(C.c_int64)), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                        d.ctypes.data_as(_c_uint8_p), C.byref(h)), "xrsfm_ba_frames_create")
+    return Frames(h, False)
+
+
+def frames_from_images(images, options: CSiftOptions | None = None, desc_options: CSiftDescOptions | None = None) -> Frames:
+    """xrsfm_ba_frames_from_images: extract_features on a list of 2-D uint8 arrays straight into a set."""
+    o = options if options is not None else sift_options()
+    do = desc_options if desc_options is not None else sift_desc_options()
+    imgs = [_grey(a) for a in images]
+    n = len(imgs)
+    w = np.array([a.shape[1] for a in imgs], np.int32); h = np.array([a.shape[0] for a in imgs], np.int32)
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:] = np.cumsum([a.size for a in imgs])
+    pix = np.concatenate([a.ravel() for a in imgs]) if n else np.zeros(0, np.uint8)
+    hd = C.c_void_p()
+    check(load().xrsfm_ba_frames_from_images(C.byref(o), C.byref(do), n, w.ctypes.data_as(_c_int32_p), h.ctypes.data_as(_c_int32_p),
+                                             ptr.ctypes.data_as(C.POINTER(C.c_int64)), pix.ctypes.data_as(_c_uint8_p), C.byref(hd)), "xrsfm_ba_frames_from_images")
+    return Frames(hd, True, max(int(o.num_octaves), 0) * 3)
+
+
+def frames_info(frames: Frames) -> dict:
+    """xrsfm_ba_frames_info: n_frames, key_ptr [n_frames + 1] and the device bytes the set holds."""
+    n = C.c_int32(0); b = C.c_uint64(0)
+    lib = load()
+    check(lib.xrsfm_ba_frames_info(frames._h(), C.byref(n), None, C.byref(b)), "xrsfm_ba_frames_info")
+    kp = np.zeros(n.value + 1, np.int64)
+    check(lib.xrsfm_ba_frames_info(frames._h(), None, kp.ctypes.data_as(C.POINTER(C.c_int64)), None), "xrsfm_ba_frames_info")
+    return dict(n_frames=int(n.value), key_ptr=kp, device_bytes=int(b.value))
+
+
+def frames_download(frames: Frames) -> list:
+    """xrsfm_ba_frames_download: per frame the dict of extract_features (keys, desc; for a set made from images also loc, sign and
+    level_count; desc_float is not held: None)."""
+    info = frames_info(frames)
+    kp, n = info["key_ptr"], info["n_frames"]
+    cap = int(kp[-1])
+    k = np.zeros((cap, 4), np.float32); d = np.zeros((cap, 128), np.uint8)
+    img = frames.from_images
+    l = np.zeros((cap, 4), np.int32) if img else None
+    s = np.zeros(cap, np.int8) if img else None
+    lc = np.zeros((n, frames.num_levels), np.int32) if img else None
+    check(load().xrsfm_ba_frames_download(frames._h(), cap, k.ctypes.data_as(C.POINTER(C.c_float)), d.ctypes.data_as(_c_uint8_p),
+                                          l.ctypes.data_as(_c_int32_p) if img else None, s.ctypes.data_as(C.POINTER(C.c_int8)) if img else None,
+                                          lc.ctypes.data_as(_c_int32_p) if img else None), "xrsfm_ba_frames_download")
+    out = []
+    for i in range(n):
+        r = dict(keys=k[kp[i]:kp[i + 1]].copy(), desc=d[kp[i]:kp[i + 1]].copy())
+        if img:
+            r.update(loc=l[kp[i]:kp[i + 1]].copy(), sign=s[kp[i]:kp[i + 1]].copy(), level_count=lc[i].copy(), desc_float=None)
+        out.append(r)
+    return out
+
+
+def frames_match(frames: Frames, pair_a, pair_b, match_options: CMatchOptions | None = None, fund_options: CFundOptions | None = None,
+                 pair_max_error=None, pair_seed=None) -> dict:
+    """xrsfm_ba_frames_match: FeatureMatching on a resident set.  Returns the dict of match_descriptors (match_ptr, matches, num_row,
+    num_col) and, with fund_options, the keys of verify_pairs (status, F, inlier_mask, num_inliers, num_trials, best_trial,
+    accepted) on the matched key points: verified_matches takes it with its own match_ptr and matches."""
+    mo = match_options if match_options is not None else _default_match_options()
+    pair_a = np.ascontiguousarray(pair_a, np.int32); pair_b = np.ascontiguousarray(pair_b, np.int32)
+    if pair_a.ndim != 1 or pair_a.shape != pair_b.shape:
+        raise ValueError("frames_match: inconsistent array shapes")
+    info = frames_info(frames)
+    nf, npair = info["n_frames"], len(pair_a)
+    n = np.minimum(np.diff(info["key_ptr"]), max(int(mo.max_features), 0))
+    ok = npair > 0 and nf > 0 and pair_a.min() >= 0 and pair_a.max() < nf
+    cap = int(n[pair_a].sum()) if ok else 0                  # (an index out of range is the library's to refuse)
+    mp = np.zeros(npair + 1, np.int64); m = np.zeros((cap, 2), np.int32)
+    r = dict(num_row=np.zeros(npair, np.int32), num_col=np.zeros(npair, np.int32))
+    ip = lambda a: a.ctypes.data_as(_c_int32_p)
+    up = lambda a: a.ctypes.data_as(_c_uint8_p)
+    pme = psd = None
+    v = None
+    if fund_options is not None:
+        if pair_max_error is not None:
+            pme = np.ascontiguousarray(pair_max_error, np.float64)
+            if pme.shape != (npair,):
+                raise ValueError("frames_match: pair_max_error must have one entry per pair")
+        if pair_seed is not None:
+            psd = np.ascontiguousarray(pair_seed, np.uint32)
+            if psd.shape != (npair,):
+                raise ValueError("frames_match: pair_seed must have one entry per pair")
+        v = dict(status=np.zeros(npair, np.uint8), F=np.zeros((npair, 9)), inlier_mask=np.zeros(cap, np.uint8), num_inliers=np.zeros(npair, np.int32),
+                 num_trials=np.zeros(npair, np.int32), best_trial=np.full(npair, -1, np.int32), accepted=np.zeros(npair, np.uint8))
+    elif pair_max_error is not None or pair_seed is not None:
+        raise ValueError("frames_match: pair_max_error and pair_seed belong to the verification (fund_options)")
+    check(load().xrsfm_ba_frames_match(frames._h(), C.byref(mo), C.byref(fund_options) if v is not None else None, npair, ip(pair_a), ip(pair_b),
+                                       _dp(pme), psd.ctypes.data_as(C.POINTER(C.c_uint32)) if psd is not None else None, cap,
+                                       mp.ctypes.data_as(C.POINTER(C.c_int64)), ip(m), ip(r["num_row"]), ip(r["num_col"]),
+                                       up(v["status"]) if v else None, _dp(v["F"]) if v else None, up(v["inlier_mask"]) if v else None,
+                                       ip(v["num_inliers"]) if v else None, ip(v["num_trials"]) if v else None, ip(v["best_trial"]) if v else None,
+                                       up(v["accepted"]) if v else None), "xrsfm_ba_frames_match")
+    r["match_ptr"] = mp
+    r["matches"] = m[:int(mp[-1])].copy()
+    if v:
+        v["inlier_mask"] = v["inlier_mask"][:int(mp[-1])].copy()
+        r.update(v)
+    return r
 
 
 def debug_sift_gradient(image, octave: int, options: CSiftOptions | None = None) -> np.ndarray:

@@ -14,11 +14,13 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <type_traits>
@@ -35,6 +37,7 @@
 #include "ba_pnp.h"
 #include "ba_init.h"
 #include "ba_fund.h"
+#include "ba_frames.h"
 #include "ba_match.h"
 #include "ba_refine.h"
 #include "ba_sift.h"
@@ -3998,10 +4001,10 @@ int xrsfm_ba_debug_fund_samples(uint32_t seed, int32_t n, int32_t n_trials, int3
     });
 }
 
-static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
-                             const double* pair_max_error, const uint32_t* pair_seed, uint8_t* status, double* F, uint8_t* inlier_mask,
-                             int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_verify_pairs: %s\n", what); return XRSFM_BA_EINVAL; };
+// ---- the host steps that xrsfm_ba_verify_pairs and xrsfm_ba_frames_match share
+// the checks of the options and of the count; who: the entry's name
+static int fund_check_options(const char* who, const xrsfm_ba_fund_options* opt, int32_t n_pairs) {
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
     if (!opt) return bad("NULL options");
     if (n_pairs < 0) return bad("negative count");
     if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio) || !std::isfinite(opt->min_accept_ratio))
@@ -4016,6 +4019,66 @@ static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, 
     if (opt->min_matches < xfund::kSample) return bad("min_matches < 7");
     if (opt->min_num_inliers < 0) return bad("min_num_inliers < 0");
     if (opt->min_accept_ratio < 0.0) return bad("min_accept_ratio < 0");
+    return XRSFM_BA_OK;
+}
+
+static int fund_check_pair_errors(const char* who, int32_t n_pairs, const double* pair_max_error) {
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (pair_max_error)
+        for (int j = 0; j < n_pairs; ++j) {
+            if (!std::isfinite(pair_max_error[j])) return bad("non-finite max_error");
+            if (pair_max_error[j] <= 0.0) return bad("max_error <= 0");
+        }
+    return XRSFM_BA_OK;
+}
+
+static FundParams fund_params(const xrsfm_ba_fund_options* opt) {
+    FundParams prm;
+    prm.trial_cap = std::min(opt->max_num_trials, xfund::fund_ratio_trials(opt->min_inlier_ratio, opt->confidence));
+    prm.min_trials = opt->min_num_trials;
+    return prm;
+}
+
+// the rows dyn(k, n) of one launch, shared by the pairs of one n
+struct FundDyn { std::vector<int32_t> rows; std::map<int, int> of; };
+
+// the record of the pair with matches beg .. beg + n; max_error, seed: the pair's own, or null
+static FundPair fund_pair_record(const xrsfm_ba_fund_options* opt, int32_t beg, int32_t n, const double* max_error, const uint32_t* seed, FundDyn& dyn) {
+    FundPair pr;
+    pr.beg = beg; pr.n = n;
+    const double me = max_error ? *max_error : opt->max_error;
+    pr.max_residual = me * me; pr.dyn_off = 0; pr.pad = 0;
+    pr.seed = seed ? *seed : opt->seed;
+    pr.skip_status = pr.n < opt->min_matches ? 2 : (pr.n > XRSFM_BA_FUND_MAX_MATCHES ? 3 : 0);
+    if (pr.skip_status) return pr;
+    auto it = dyn.of.find(pr.n);
+    if (it == dyn.of.end()) {
+        it = dyn.of.emplace(pr.n, (int)dyn.rows.size()).first;
+        for (int k = 0; k <= pr.n; ++k) dyn.rows.push_back(xfund::fund_dyn_trials(k, pr.n, opt->confidence));
+    }
+    pr.dyn_off = it->second;
+    return pr;
+}
+
+static void fund_kernel_setup() {
+    static std::once_flag lds_once;
+    std::call_once(lds_once, [] { (void)hipFuncSetAttribute((const void*)k_verify_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FundShared)); });
+}
+
+// status, F and accepted of one pair from what the kernel wrote for it (n: its matches)
+static void fund_publish_pair(const xrsfm_ba_fund_options* opt, unsigned char stat, const double* Fs, int ninl, int32_t n, uint8_t* status, double* F, uint8_t* accepted) {
+    *status = stat;
+    if (stat == 1) for (int k2 = 0; k2 < 9; ++k2) F[k2] = Fs[k2];
+    if (accepted)                                              // feature_processing.cc:284-290
+        *accepted = (stat == 1 && ninl >= xframes::accept_threshold(opt->min_num_inliers, opt->min_accept_ratio, n)) ? 1 : 0;
+}
+
+static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
+                             const double* pair_max_error, const uint32_t* pair_seed, uint8_t* status, double* F, uint8_t* inlier_mask,
+                             int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
+    const char* who = "xrsfm_ba_verify_pairs";
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (int e = fund_check_options(who, opt, n_pairs)) return e;
     if (n_pairs == 0) return XRSFM_BA_OK;
     if (!status || !F || !inlier_mask) return bad("NULL status, F or inlier_mask");
     if (!match_ptr) return bad("NULL match_ptr");
@@ -4025,41 +4088,22 @@ static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, 
     const int Nm = match_ptr[n_pairs], Np = n_pairs;
     if (Nm > 0 && (!xy_a || !xy_b)) return bad("NULL xy_a or xy_b");
     for (size_t i = 0; i < 2 * (size_t)Nm; ++i) if (!std::isfinite(xy_a[i]) || !std::isfinite(xy_b[i])) return bad("non-finite coordinate");
-    if (pair_max_error)
-        for (int j = 0; j < Np; ++j) {
-            if (!std::isfinite(pair_max_error[j])) return bad("non-finite max_error");
-            if (pair_max_error[j] <= 0.0) return bad("max_error <= 0");
-        }
+    if (int e = fund_check_pair_errors(who, Np, pair_max_error)) return e;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         fprintf(stderr, "[xrsfm_ba] no HIP device visible: the pair verification has no CPU fallback\n");
         return XRSFM_BA_ENODEV;
     }
-    FundParams prm;
-    prm.trial_cap = std::min(opt->max_num_trials, xfund::fund_ratio_trials(opt->min_inlier_ratio, opt->confidence));
-    prm.min_trials = opt->min_num_trials;
+    const FundParams prm = fund_params(opt);
     // per pair: the row dyn(k, n), shared by the pairs of one n; the septuples are drawn on the device
     std::vector<FundPair> pairs((size_t)Np);
-    std::vector<int32_t> dyn;
-    std::map<int, int> dyn_of;
-    for (int j = 0; j < Np; ++j) {
-        FundPair& pr = pairs[(size_t)j];
-        pr.beg = match_ptr[j]; pr.n = match_ptr[j + 1] - match_ptr[j];
-        const double me = pair_max_error ? pair_max_error[j] : opt->max_error;
-        pr.max_residual = me * me; pr.dyn_off = 0; pr.pad = 0;
-        pr.seed = pair_seed ? pair_seed[j] : opt->seed;
-        pr.skip_status = pr.n < opt->min_matches ? 2 : (pr.n > XRSFM_BA_FUND_MAX_MATCHES ? 3 : 0);
-        if (pr.skip_status) continue;
-        auto it = dyn_of.find(pr.n);
-        if (it == dyn_of.end()) {
-            it = dyn_of.emplace(pr.n, (int)dyn.size()).first;
-            for (int k = 0; k <= pr.n; ++k) dyn.push_back(xfund::fund_dyn_trials(k, pr.n, opt->confidence));
-        }
-        pr.dyn_off = it->second;
-    }
+    FundDyn dyn_rows;
+    for (int j = 0; j < Np; ++j)
+        pairs[(size_t)j] = fund_pair_record(opt, match_ptr[j], match_ptr[j + 1] - match_ptr[j], pair_max_error ? pair_max_error + j : nullptr,
+                                            pair_seed ? pair_seed + j : nullptr, dyn_rows);
+    const std::vector<int32_t>& dyn = dyn_rows.rows;
     HIPCHK(hipSetDevice(0));
-    static std::once_flag lds_once;
-    std::call_once(lds_once, [] { (void)hipFuncSetAttribute((const void*)k_verify_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FundShared)); });
+    fund_kernel_setup();
     // one block from the allocation cache, one upload, one launch, one read-back (the layout of absolute_pose_impl)
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t off = 0;
@@ -4098,14 +4142,8 @@ static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, 
             const double* Fs = (const double*)(o + o_F);
             const unsigned char* stat = o + o_stat;
             const int* ninl = (const int*)(o + o_ninl);
-            for (int j = 0; j < Np; ++j) {
-                status[j] = stat[j];
-                if (stat[j] == 1) for (int k2 = 0; k2 < 9; ++k2) F[9 * (size_t)j + k2] = Fs[9 * (size_t)j + k2];
-                if (accepted) {                                        // feature_processing.cc:284-290
-                    const int thr = std::max(opt->min_num_inliers, (int)(opt->min_accept_ratio * (double)pairs[(size_t)j].n));
-                    accepted[j] = (stat[j] == 1 && ninl[j] >= thr) ? 1 : 0;
-                }
-            }
+            for (int j = 0; j < Np; ++j)
+                fund_publish_pair(opt, stat[j], Fs + 9 * (size_t)j, ninl[j], pairs[(size_t)j].n, status + j, F + 9 * (size_t)j, accepted ? accepted + j : nullptr);
             if (Nm) memcpy(inlier_mask, o + o_mask, (size_t)Nm);
             if (num_inliers) memcpy(num_inliers, ninl, sizeof(int) * (size_t)Np);
             if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Np);
@@ -4166,6 +4204,87 @@ struct MatchResult {                          // of the whole call, held back un
     std::vector<int32_t> row_top, col_top;              // debug: of pair 0
 };
 
+// ---- the host steps that xrsfm_ba_match_descriptors and xrsfm_ba_frames_match share
+// the workspace of one sub-batch: [pairs | items] uploaded, [counts | matches (| row and column triples: debug)] read back, the rest
+struct MatchLayout { size_t o_pr, o_it, in_bytes, o_cnt, o_m, o_rt, o_ct, back_bytes, o_cm, o_part, total; int64_t items; };
+MatchLayout match_layout(const xframes::BatchSize& s, bool debug) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    MatchLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    L.o_pr = take(sizeof(MatchPair) * (size_t)s.pairs); L.o_it = take(sizeof(MatchItem) * (size_t)s.items); L.in_bytes = off;
+    L.o_cnt = take(sizeof(int32_t) * 4 * (size_t)s.pairs); L.o_m = take(sizeof(int32_t) * 2 * (size_t)s.rows);
+    if (!debug) L.back_bytes = off - L.o_cnt;
+    L.o_rt = take(sizeof(int32_t) * 3 * (size_t)s.rows); L.o_ct = take(sizeof(int32_t) * 3 * (size_t)s.cols);
+    if (debug) L.back_bytes = off - L.o_cnt;
+    L.o_cm = take(sizeof(int32_t) * (size_t)s.cols); L.o_part = take(sizeof(int32_t) * 3 * (size_t)s.parts);
+    L.total = off; L.items = s.items;
+    return L;
+}
+
+// the pairs with rows and columns, and their sub-batches under the workspace budget (XRSFM_BA_MATCH_WORKSPACE_MB, default 1024)
+// less the resident descriptor bytes
+struct MatchBatch { size_t first, last; MatchLayout L; };          // pairs live[first .. last - 1]
+struct MatchPlan {
+    std::vector<int32_t> live;
+    std::vector<MatchBatch> batches;
+    size_t ws_bytes = 0, in_max = 0, back_max = 0;
+};
+void match_plan(const std::vector<int32_t>& clip, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, size_t desc_bytes, bool debug, MatchPlan* P) {
+    std::vector<int32_t> na, nb;
+    xframes::plan_live(n_pairs, pair_a, pair_b, clip.data(), &P->live, &na, &nb);
+    size_t budget = (size_t)1024 << 20;
+    if (const char* s = getenv("XRSFM_BA_MATCH_WORKSPACE_MB")) { const long long mb = atoll(s); if (mb >= 0) budget = (size_t)mb << 20; }
+    budget = budget > desc_bytes ? budget - desc_bytes : 0;
+    for (const xframes::Batch& b : xframes::plan_split(P->live.size(), na.data(), nb.data(), kMatchStrip, budget,
+                                                       [&](const xframes::BatchSize& s) { return match_layout(s, debug).total; }))
+        P->batches.push_back(MatchBatch{b.first, b.last, match_layout(b.size, debug)});
+    for (const MatchBatch& b : P->batches) { P->ws_bytes = std::max(P->ws_bytes, b.L.total); P->in_max = std::max(P->in_max, b.L.in_bytes); P->back_max = std::max(P->back_max, b.L.back_bytes); }
+}
+
+// the records of a sub-batch into its staging block; frame_of(q, &pr) sets a_off, b_off, n_a, n_b of its q-th pair
+void match_fill_records(unsigned char* stage, const MatchLayout& L, int np, const std::function<void(int, MatchPair*)>& frame_of) {
+    MatchPair* prs = (MatchPair*)(stage + L.o_pr);
+    MatchItem* its = (MatchItem*)(stage + L.o_it);
+    xframes::BatchSize size;
+    for (int q = 0; q < np; ++q) {
+        MatchPair& pr = prs[q];
+        frame_of(q, &pr);
+        const xframes::PairSpan sp = xframes::plan_append(size, pr.n_a, pr.n_b, kMatchStrip);
+        pr.strips = sp.strips; pr.pad = 0;
+        pr.part_off = sp.part_off; pr.row_off = sp.row_off; pr.col_off = sp.col_off;
+        for (int s = 0; s < sp.strips; ++s) its[sp.item_off + s] = MatchItem{q, s};
+    }
+}
+
+// the two kernels of a sub-batch on descriptors that k_match_prep has seen; ev: three events around them, or null
+int match_launch(hipStream_t st, unsigned char* base, const MatchLayout& L, int np, const uint8_t* desc, const int32_t* prep, const MatchParams& prm, const float* tab,
+                 hipEvent_t* ev) {
+    if (ev) (void)hipEventRecord(ev[0], st);
+    hipLaunchKernelGGL(k_match_dots, dim3((unsigned)L.items), dim3(kMatchThreads), 0, st, (const MatchItem*)(base + L.o_it), (const MatchPair*)(base + L.o_pr),
+                       desc, prep, (int32_t*)(base + L.o_part), (int32_t*)(base + L.o_rt));
+    if (hipGetLastError() != hipSuccess) return XRSFM_BA_ENODEV;
+    if (ev) (void)hipEventRecord(ev[1], st);
+    hipLaunchKernelGGL(k_match_select, dim3((unsigned)np), dim3(kMatchThreads), 0, st, (const MatchPair*)(base + L.o_pr), prm, tab, (const int32_t*)(base + L.o_part),
+                       (const int32_t*)(base + L.o_rt), (int32_t*)(base + L.o_ct), (int32_t*)(base + L.o_cm), (int32_t*)(base + L.o_m), (int32_t*)(base + L.o_cnt));
+    if (hipGetLastError() != hipSuccess) return XRSFM_BA_ENODEV;
+    if (ev) (void)hipEventRecord(ev[2], st);
+    return XRSFM_BA_OK;
+}
+
+// the counts of a sub-batch (and, with mm, its matches at their upper-bound offsets) into the call's result; pairs: the caller's
+// indices of its np pairs.  false: a count outside its pair
+bool match_collect(const int32_t* cnt, const int32_t* mm, const MatchPair* prs, int np, const int32_t* pairs, MatchResult* R) {
+    for (int q = 0; q < np; ++q) {
+        const int p = pairs[q];
+        const int32_t c = cnt[4 * q];
+        if (c < 0 || c > prs[q].n_a) return false;
+        R->count[(size_t)p] = c; R->num_row[(size_t)p] = cnt[4 * q + 1]; R->num_col[(size_t)p] = cnt[4 * q + 2];
+        if (mm) R->rows[(size_t)p].assign(mm + 2 * prs[q].row_off, mm + 2 * (prs[q].row_off + c));
+    }
+    return true;
+}
+
 // Everything after the argument checks.  clip[f]: descriptors of frame f that take part.
 int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, const std::vector<int32_t>& clip,
               int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, bool debug, MatchResult* R) {
@@ -4174,48 +4293,17 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
     R->rows.assign((size_t)n_pairs, std::vector<int32_t>());
     // the frames that occur in a pair with work, each once
     std::vector<int64_t> dev_off((size_t)n_frames, -1);
-    std::vector<int32_t> live;                           // pairs with rows and columns
     for (int p = 0; p < n_pairs; ++p)
-        if (clip[(size_t)pair_a[p]] > 0 && clip[(size_t)pair_b[p]] > 0) { live.push_back(p); dev_off[(size_t)pair_a[p]] = dev_off[(size_t)pair_b[p]] = 0; }
-    if (live.empty()) return XRSFM_BA_OK;
+        if (clip[(size_t)pair_a[p]] > 0 && clip[(size_t)pair_b[p]] > 0) dev_off[(size_t)pair_a[p]] = dev_off[(size_t)pair_b[p]] = 0;
     int64_t D = 0;
     for (int f = 0; f < n_frames; ++f) if (dev_off[(size_t)f] == 0) { dev_off[(size_t)f] = D; D += clip[(size_t)f]; }
+    if (D == 0) return XRSFM_BA_OK;
     const size_t o_off = al((size_t)D * xmatch::kDim), desc_bytes = o_off + al(sizeof(int32_t) * (size_t)D);
-    // sub-batches of pairs under the workspace budget
-    size_t budget = (size_t)1024 << 20;
-    if (const char* s = getenv("XRSFM_BA_MATCH_WORKSPACE_MB")) { const long long mb = atoll(s); if (mb >= 0) budget = (size_t)mb << 20; }
-    budget = budget > desc_bytes ? budget - desc_bytes : 0;
-    struct Layout { size_t o_pr, o_it, in_bytes, o_cnt, o_m, o_rt, o_ct, back_bytes, o_cm, o_part, total; int64_t rows, cols, parts, items; };
-    auto layout = [&](int64_t np, int64_t rows, int64_t cols, int64_t parts, int64_t items) {
-        Layout L{};
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-        L.o_pr = take(sizeof(MatchPair) * (size_t)np); L.o_it = take(sizeof(MatchItem) * (size_t)items); L.in_bytes = off;
-        L.o_cnt = take(sizeof(int32_t) * 4 * (size_t)np); L.o_m = take(sizeof(int32_t) * 2 * (size_t)rows);
-        if (!debug) L.back_bytes = off - L.o_cnt;
-        L.o_rt = take(sizeof(int32_t) * 3 * (size_t)rows); L.o_ct = take(sizeof(int32_t) * 3 * (size_t)cols);
-        if (debug) L.back_bytes = off - L.o_cnt;
-        L.o_cm = take(sizeof(int32_t) * (size_t)cols); L.o_part = take(sizeof(int32_t) * 3 * (size_t)parts);
-        L.total = off; L.rows = rows; L.cols = cols; L.parts = parts; L.items = items;
-        return L;
-    };
-    struct Batch { size_t first, last; Layout L; };
-    std::vector<Batch> batches;
-    {
-        size_t first = 0;
-        int64_t rows = 0, cols = 0, parts = 0, items = 0;
-        for (size_t k = 0; k < live.size(); ++k) {
-            const int64_t na = clip[(size_t)pair_a[live[k]]], nb = clip[(size_t)pair_b[live[k]]], strips = (na + kMatchStrip - 1) / kMatchStrip;
-            if (k > first && layout((int64_t)(k - first) + 1, rows + na, cols + nb, parts + strips * nb, items + strips).total > budget) {
-                batches.push_back({first, k, layout((int64_t)(k - first), rows, cols, parts, items)});
-                first = k; rows = cols = parts = items = 0;
-            }
-            rows += na; cols += nb; parts += strips * nb; items += strips;
-        }
-        batches.push_back({first, live.size(), layout((int64_t)(live.size() - first), rows, cols, parts, items)});
-    }
-    size_t ws_bytes = 0, in_max = 0, back_max = 0;
-    for (const Batch& b : batches) { ws_bytes = std::max(ws_bytes, b.L.total); in_max = std::max(in_max, b.L.in_bytes); back_max = std::max(back_max, b.L.back_bytes); }
+    MatchPlan plan;
+    match_plan(clip, n_pairs, pair_a, pair_b, desc_bytes, debug, &plan);
+    const std::vector<int32_t>& live = plan.live;
+    const std::vector<MatchBatch>& batches = plan.batches;
+    const size_t ws_bytes = plan.ws_bytes, in_max = plan.in_max, back_max = plan.back_max;
 
     HIPCHK(hipSetDevice(0));
     const float* tab = match_table_device();
@@ -4249,32 +4337,17 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
         }
         const MatchParams prm{opt->max_distance, opt->max_ratio, opt->mutual_best ? 1 : 0};
         for (size_t bi = 0; bi < batches.size() && !e; ++bi) {
-            const Batch& b = batches[bi];
-            const Layout& L = b.L;
+            const MatchBatch& b = batches[bi];
+            const MatchLayout& L = b.L;
             const int np = (int)(b.last - b.first);
-            MatchPair* prs = (MatchPair*)(stage.data() + L.o_pr);
-            MatchItem* its = (MatchItem*)(stage.data() + L.o_it);
-            int64_t rows = 0, cols = 0, parts = 0, items = 0;
-            for (int q = 0; q < np; ++q) {
+            const MatchPair* prs = (const MatchPair*)(stage.data() + L.o_pr);
+            match_fill_records(stage.data(), L, np, [&](int q, MatchPair* pr) {
                 const int p = live[b.first + (size_t)q];
-                MatchPair& pr = prs[q];
-                pr.a_off = dev_off[(size_t)pair_a[p]]; pr.b_off = dev_off[(size_t)pair_b[p]];
-                pr.n_a = clip[(size_t)pair_a[p]]; pr.n_b = clip[(size_t)pair_b[p]];
-                pr.strips = (pr.n_a + kMatchStrip - 1) / kMatchStrip; pr.pad = 0;
-                pr.part_off = parts; pr.row_off = rows; pr.col_off = cols;
-                for (int s = 0; s < pr.strips; ++s) its[items++] = MatchItem{q, s};
-                rows += pr.n_a; cols += pr.n_b; parts += (int64_t)pr.strips * pr.n_b;
-            }
+                pr->a_off = dev_off[(size_t)pair_a[p]]; pr->b_off = dev_off[(size_t)pair_b[p]];
+                pr->n_a = clip[(size_t)pair_a[p]]; pr->n_b = clip[(size_t)pair_b[p]];
+            });
             if (hipMemcpyAsync(base, stage.data(), L.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
-            if (tm.on) (void)hipEventRecord(tm.ev[2], st);
-            hipLaunchKernelGGL(k_match_dots, dim3((unsigned)L.items), dim3(kMatchThreads), 0, st, (const MatchItem*)(base + L.o_it), (const MatchPair*)(base + L.o_pr),
-                               (const uint8_t*)dbase, (const int32_t*)(dbase + o_off), (int32_t*)(base + L.o_part), (int32_t*)(base + L.o_rt));
-            if (hipGetLastError() != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
-            if (tm.on) (void)hipEventRecord(tm.ev[3], st);
-            hipLaunchKernelGGL(k_match_select, dim3((unsigned)np), dim3(kMatchThreads), 0, st, (const MatchPair*)(base + L.o_pr), prm, tab, (const int32_t*)(base + L.o_part),
-                               (const int32_t*)(base + L.o_rt), (int32_t*)(base + L.o_ct), (int32_t*)(base + L.o_cm), (int32_t*)(base + L.o_m), (int32_t*)(base + L.o_cnt));
-            if (hipGetLastError() != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
-            if (tm.on) (void)hipEventRecord(tm.ev[4], st);
+            if ((e = match_launch(st, base, L, np, (const uint8_t*)dbase, (const int32_t*)(dbase + o_off), prm, tab, tm.on ? tm.ev + 2 : nullptr))) break;
             if (hipMemcpyAsync(back.data(), base + L.o_cnt, L.back_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             if (hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             if (tm.on) {
@@ -4286,13 +4359,7 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
             const unsigned char* o = back.data() - L.o_cnt;          // (offsets above are relative to the block)
             const int32_t* cnt = (const int32_t*)(o + L.o_cnt);
             const int32_t* mm = (const int32_t*)(o + L.o_m);
-            for (int q = 0; q < np; ++q) {
-                const int p = live[b.first + (size_t)q];
-                const int32_t c = cnt[4 * q];
-                if (c < 0 || c > prs[q].n_a) { e = XRSFM_BA_EINTERNAL; break; }
-                R->count[(size_t)p] = c; R->num_row[(size_t)p] = cnt[4 * q + 1]; R->num_col[(size_t)p] = cnt[4 * q + 2];
-                R->rows[(size_t)p].assign(mm + 2 * prs[q].row_off, mm + 2 * (prs[q].row_off + c));
-            }
+            if (!match_collect(cnt, mm, prs, np, live.data() + b.first, R)) e = XRSFM_BA_EINTERNAL;
             if (debug && !e) {
                 R->row_top.assign((const int32_t*)(o + L.o_rt), (const int32_t*)(o + L.o_rt) + 3 * (size_t)prs[0].n_a);
                 R->col_top.assign((const int32_t*)(o + L.o_ct), (const int32_t*)(o + L.o_ct) + 3 * (size_t)prs[0].n_b);
@@ -4307,6 +4374,18 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
     return e;
 }
 
+// the checks of the options and of the counts; who: the entry's name
+int match_check_options(const char* who, const xrsfm_ba_match_options* opt, int32_t n_pairs, int32_t n_frames, int64_t matches_capacity) {
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (!opt) return bad("NULL options");
+    if (n_pairs < 0 || n_frames < 0 || matches_capacity < 0) return bad("negative count");
+    if (!std::isfinite(opt->max_distance) || !std::isfinite(opt->max_ratio)) return bad("non-finite option");
+    if (opt->max_distance <= 0.0f) return bad("max_distance <= 0");
+    if (!(opt->max_ratio > 0.0f && opt->max_ratio <= 1.0f)) return bad("max_ratio outside (0, 1]");
+    if (opt->max_features < 1 || opt->max_features > XRSFM_BA_MATCH_MAX_FEATURES) return bad("max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES");
+    return XRSFM_BA_OK;
+}
+
 int match_no_device() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -4319,13 +4398,9 @@ int match_no_device() {
 int match_descriptors_impl(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, int32_t n_pairs,
                            const int32_t* pair_a, const int32_t* pair_b, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
                            int32_t* num_row, int32_t* num_col) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_match_descriptors: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_pairs < 0 || n_frames < 0 || matches_capacity < 0) return bad("negative count");
-    if (!std::isfinite(opt->max_distance) || !std::isfinite(opt->max_ratio)) return bad("non-finite option");
-    if (opt->max_distance <= 0.0f) return bad("max_distance <= 0");
-    if (!(opt->max_ratio > 0.0f && opt->max_ratio <= 1.0f)) return bad("max_ratio outside (0, 1]");
-    if (opt->max_features < 1 || opt->max_features > XRSFM_BA_MATCH_MAX_FEATURES) return bad("max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES");
+    const char* who = "xrsfm_ba_match_descriptors";
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (int e = match_check_options(who, opt, n_pairs, n_frames, matches_capacity)) return e;
     if (n_pairs == 0) return XRSFM_BA_OK;
     if (!match_ptr) return bad("NULL match_ptr");
     if (!pair_a || !pair_b) return bad("NULL pair_a or pair_b");
@@ -4428,9 +4503,34 @@ struct SiftResult {                           // of the whole call, held back un
     std::vector<std::vector<float>> desc_float, raw, unit;
 };
 
-// Everything after the argument checks.
+// The device arrays of a frame set (ba_frames.h): per key point its key, its descriptor bytes as k_match_prep leaves them and that
+// kernel's term; for a set made from images also loc, sign and the float w of the orientation.
+struct FramesLayout { size_t o_keys, o_desc, o_prep, o_loc, o_sign, o_w, total; };
+FramesLayout frames_layout(int64_t n, bool image_fields) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    FramesLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    L.o_keys = take(16 * (size_t)n); L.o_desc = take(128 * (size_t)n); L.o_prep = take(4 * (size_t)n);
+    if (image_fields) { L.o_loc = take(16 * (size_t)n); L.o_sign = take((size_t)n); L.o_w = take(4 * (size_t)n); }
+    L.total = off;
+    return L;
+}
+struct FramesBlock {
+    void* p = nullptr; size_t cls = 0; int64_t n = 0; FramesLayout L{};
+    unsigned char* at(size_t o) const { return (unsigned char*)p + o; }
+    void release() { if (p) g_cache.put(0, p, cls); p = nullptr; }
+};
+// where sift_run leaves the ordered key points of its chunks instead of reading them back: one block per chunk with key points
+struct SiftSink {
+    std::vector<FramesBlock> chunks;
+    ~SiftSink() { for (FramesBlock& b : chunks) b.release(); }
+};
+
+// Everything after the argument checks.  With a sink (and dq) the key points stay on the device: k_frames_order puts every chunk's
+// into the interface's order in a block of the sink, and R carries level_count and count only.
 int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
-             const uint8_t* pixels, const SiftLevelsRequest* want, SiftResult* R, const SiftDescRequest* dq = nullptr) {
+             const uint8_t* pixels, const SiftLevelsRequest* want, SiftResult* R, const SiftDescRequest* dq = nullptr, SiftSink* sink = nullptr) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int NL = opt->num_octaves * xsift::kKeyLevels;
     R->level_count.assign((size_t)n_images * NL, 0); R->count.assign((size_t)n_images, 0);
@@ -4471,7 +4571,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
     struct Span { hipEvent_t a, b; int what; };
     struct Events { std::vector<Span> ev; bool on = false; ~Events() { for (const Span& x : ev) { (void)hipEventDestroy(x.a); (void)hipEventDestroy(x.b); } } } tm;
     tm.on = getenv("XRSFM_BA_SIFT_TIMING") != nullptr;
-    enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTGrad, kTRecord, kTOrient, kTDesc, kTN };
+    enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTGrad, kTRecord, kTOrient, kTDesc, kTOrder, kTN };
     double ms[kTN] = {};
     int e = 0;
     struct Dev { void* p = nullptr; size_t cls = 0; ~Dev() { if (p) g_cache.put(0, p, cls); } };
@@ -4613,8 +4713,8 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
             Dev kd;
             kd.p = g_cache.get(0, k_total, &kd.cls);
             Pin back;
-            back.p = (unsigned char*)g_pinned.get(k_total, &back.cap);
-            if (!kd.p || !back.p) { e = XRSFM_BA_ENOMEM; break; }
+            if (!sink) back.p = (unsigned char*)g_pinned.get(k_total, &back.cap);
+            if (!kd.p || (!sink && !back.p)) { e = XRSFM_BA_ENOMEM; break; }
             unsigned char* kb = (unsigned char*)kd.p;
             if (hipMemcpyAsync(d_first, sl_first, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             for (int o = 0; o < oct_most && !e; ++o) {
@@ -4624,7 +4724,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                                                        (int4*)(kb + k_loc), (float4*)(kb + k_off)); });
             }
             if (e) { (void)hipStreamSynchronize(st); break; }
-            if (hipMemcpyAsync(back.p, kb, k_total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            if ((!sink && hipMemcpyAsync(back.p, kb, k_total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
                 hipMemcpyAsync(slots.p + 2 * slot_bytes, d_emit, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             // the two passes are separate instantiations of one decision: a tile that emitted another number than it counted would
@@ -4660,9 +4760,9 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                              u_total = u_lev + al(sizeof(SiftdLevel) * levels.size());
                 const size_t d_up = d_rec + al(sizeof(SiftdRec) * nk);
                 dd.p = g_cache.get(0, d_up + u_total, &dd.cls);
-                dback.p = (unsigned char*)g_pinned.get(d_out, &dback.cap);
+                if (!sink) dback.p = (unsigned char*)g_pinned.get(d_out, &dback.cap);
                 dstage.p = (unsigned char*)g_pinned.get(u_total, &dstage.cap);
-                if (!dd.p || !dback.p || !dstage.p) { e = XRSFM_BA_ENOMEM; break; }
+                if (!dd.p || (!sink && !dback.p) || !dstage.p) { e = XRSFM_BA_ENOMEM; break; }
                 unsigned char* db = (unsigned char*)dd.p;
                 memcpy(dstage.p + u_dimg, dimgs.data(), sizeof(SiftdImg) * (size_t)ni);
                 memcpy(dstage.p + u_need, need.data(), sizeof(int32_t) * need.size());
@@ -4691,8 +4791,38 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                                                                dq->floats ? (float*)(db + d_float) : (float*)nullptr, dq->stages ? (float*)(db + d_raw) : (float*)nullptr,
                                                                dq->stages ? (float*)(db + d_unit) : (float*)nullptr); });
                 if (e) { (void)hipStreamSynchronize(st); break; }
-                if (hipMemcpyAsync(dback.p, db, d_out, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+                if (sink) {
+                    // the order of the interface on the device (k_frames_order): every level with key points is a segment, cut into work
+                    // items of kFramesThreads key points; the chunk's block joins the sink once the stream has drained
+                    std::vector<FramesSeg> segs;
+                    std::vector<FramesOrderItem> items;
+                    for (const SiftdLevel& lv : levels) {
+                        for (int s = 0; s < (lv.count + kFramesThreads - 1) / kFramesThreads; ++s) items.push_back(FramesOrderItem{(int32_t)segs.size(), s});
+                        segs.push_back(FramesSeg{lv.first, lv.count, lv.w});
+                    }
+                    FramesBlock blk;
+                    blk.n = n_keys; blk.L = frames_layout(n_keys, true);
+                    blk.p = g_cache.get(0, blk.L.total, &blk.cls);
+                    Dev od;
+                    Pin ostage;
+                    const size_t s_item = al(sizeof(FramesSeg) * segs.size()), s_total = s_item + al(sizeof(FramesOrderItem) * items.size());
+                    od.p = g_cache.get(0, s_total, &od.cls);
+                    ostage.p = (unsigned char*)g_pinned.get(s_total, &ostage.cap);
+                    if (!blk.p || !od.p || !ostage.p) { blk.release(); e = XRSFM_BA_ENOMEM; break; }
+                    memcpy(ostage.p, segs.data(), sizeof(FramesSeg) * segs.size());
+                    memcpy(ostage.p + s_item, items.data(), sizeof(FramesOrderItem) * items.size());
+                    if (hipMemcpyAsync(od.p, ostage.p, s_total, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+                    if (!e) timed(kTOrder, [&] { hipLaunchKernelGGL(k_frames_order, dim3((unsigned)items.size()), dim3(kFramesThreads), 0, st,
+                                                                    (const FramesOrderItem*)((unsigned char*)od.p + s_item), (const FramesSeg*)od.p, (const float4*)(kb + k_keys),
+                                                                    (const int4*)(kb + k_loc), (const float4*)(kb + k_off), (const float4*)(db + d_okey), (const uint8_t*)(db + d_desc),
+                                                                    (float4*)blk.at(blk.L.o_keys), (int4*)blk.at(blk.L.o_loc), (int8_t*)blk.at(blk.L.o_sign), (float*)blk.at(blk.L.o_w),
+                                                                    (uint8_t*)blk.at(blk.L.o_desc)); });
+                    if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+                    if (e) { blk.release(); break; }
+                    sink->chunks.push_back(blk);
+                } else if (hipMemcpyAsync(dback.p, db, d_out, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             }
+            if (sink) continue;
             const unsigned char* hd = dq ? dback.p : back.p;          // (without the second half none of these is read)
             const float* h_ok = (const float*)(hd + d_okey); const uint8_t* h_ds = hd + d_desc; const float* h_fl = (const float*)(hd + d_float);
             const float* h_raw = (const float*)(hd + d_raw); const float* h_un = (const float*)(hd + d_unit);
@@ -4761,6 +4891,7 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         fprintf(stderr, "[xrsfm_ba] sift timing: base %.4f ms, init %.4f ms, filter %.4f %.4f %.4f %.4f %.4f ms, down %.4f ms, count %.4f ms, emit %.4f ms, chunks %zu\n",
                 ms[kTBase], ms[kTInit], ms[kTFilter0], ms[kTFilter0 + 1], ms[kTFilter0 + 2], ms[kTFilter0 + 3], ms[kTFilter0 + 4], ms[kTDown], ms[kTCount], ms[kTEmit], chunks.size());
         if (dq) fprintf(stderr, "[xrsfm_ba] sift descriptor timing: grad %.4f ms, record %.4f ms, orient %.4f ms, desc %.4f ms\n", ms[kTGrad], ms[kTRecord], ms[kTOrient], ms[kTDesc]);
+        if (sink) fprintf(stderr, "[xrsfm_ba] frames timing: order %.4f ms\n", ms[kTOrder]);
     }
     g_bundles.put(0, hb);
     return e;
@@ -4931,6 +5062,431 @@ int xrsfm_ba_debug_sift_levels(const xrsfm_ba_sift_options* opt, int32_t width, 
 int xrsfm_ba_debug_sift_offsets(const xrsfm_ba_sift_options* opt, int32_t width, int32_t height, const uint8_t* pixels, int64_t capacity, int64_t* n_keys,
                                 int32_t* loc, float* offsets) {
     return no_throw([&] { return debug_sift_offsets_impl(opt, width, height, pixels, capacity, n_keys, loc, offsets); });
+}
+
+// ---------------------------------------------------------------- device-resident frame sets (ba_frames.h)
+struct xrsfm_ba_frames {
+    int32_t n_frames = 0, nl = 0;                       // nl: levels per image of level_count
+    bool from_images = false;
+    std::vector<int64_t> key_ptr = std::vector<int64_t>(1, 0);
+    std::vector<int32_t> level_count;                   // [n_frames][nl], sets made from images
+    FramesBlock blk;                                    // null without key points
+    ~xrsfm_ba_frames() { blk.release(); }
+};
+
+namespace {
+struct FramesPin { unsigned char* p = nullptr; size_t cap = 0; ~FramesPin() { if (p) g_pinned.put(p, cap); } bool get(size_t bytes) { p = (unsigned char*)g_pinned.get(bytes ? bytes : 8, &cap); return p != nullptr; } };
+struct FramesDev { void* p = nullptr; size_t cls = 0; ~FramesDev() { if (p) g_cache.put(0, p, cls); } bool get(size_t bytes) { p = g_cache.get(0, bytes, &cls); return p != nullptr; } };
+struct FramesStream { HostBundle hb; bool ok; FramesStream() { ok = g_bundles.get(0, &hb); } ~FramesStream() { if (ok) g_bundles.put(0, hb); } };
+
+int frames_no_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the frame sets have no CPU fallback\n");
+        return XRSFM_BA_ENODEV;
+    }
+    return 0;
+}
+
+// k_match_prep, once per set: the descriptor bytes as the matching kernels read them, and their per-descriptor term
+int frames_prep(hipStream_t st, const FramesBlock& b) {
+    hipLaunchKernelGGL(k_match_prep, dim3((unsigned)((b.n * 8 + kMatchThreads - 1) / kMatchThreads)), dim3(kMatchThreads), 0, st, (uint8_t*)b.at(b.L.o_desc),
+                       (int32_t*)b.at(b.L.o_prep), b.n);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return XRSFM_BA_ENODEV;
+    return XRSFM_BA_OK;
+}
+
+int frames_create_impl(int32_t n_frames, const int64_t* key_ptr, const float* keys, const uint8_t* desc, xrsfm_ba_frames** out) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_create: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!out) return bad("NULL out");
+    if (n_frames < 0) return bad("negative count");
+    if (n_frames > 0 && !key_ptr) return bad("NULL key_ptr");
+    if (n_frames > 0 && key_ptr[0] != 0) return bad("key_ptr does not start at 0");
+    for (int f = 0; f < n_frames; ++f)
+        if (key_ptr[f + 1] < key_ptr[f]) return bad("key_ptr decreases");
+    for (int f = 0; f < n_frames; ++f)
+        if (key_ptr[f + 1] - key_ptr[f] > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_create: a frame above INT32_MAX key points\n"); return XRSFM_BA_ETOOBIG; }
+    const int64_t N = n_frames > 0 ? key_ptr[n_frames] : 0;
+    if (N > 0 && (!keys || !desc)) return bad("NULL keys or desc");
+    for (int64_t k = 0; k < N; ++k)
+        if (!std::isfinite(keys[4 * k]) || !std::isfinite(keys[4 * k + 1])) return bad("non-finite coordinate");
+    std::unique_ptr<xrsfm_ba_frames> fs(new xrsfm_ba_frames);
+    fs->n_frames = n_frames;
+    if (n_frames > 0) fs->key_ptr.assign(key_ptr, key_ptr + n_frames + 1);
+    if (N > 0) {
+        if (int e = frames_no_device()) return e;
+        HIPCHK(hipSetDevice(0));
+        FramesStream s;
+        if (!s.ok) return XRSFM_BA_ENODEV;
+        FramesBlock& b = fs->blk;
+        b.n = N; b.L = frames_layout(N, false);
+        b.p = g_cache.get(0, b.L.total, &b.cls);
+        FramesPin stage;
+        if (!b.p || !stage.get(144 * (size_t)N)) return XRSFM_BA_ENOMEM;
+        memcpy(stage.p, keys, 16 * (size_t)N);
+        memcpy(stage.p + 16 * (size_t)N, desc, 128 * (size_t)N);
+        if (hipMemcpyAsync(b.at(b.L.o_keys), stage.p, 16 * (size_t)N, hipMemcpyHostToDevice, s.hb.stream) != hipSuccess ||
+            hipMemcpyAsync(b.at(b.L.o_desc), stage.p + 16 * (size_t)N, 128 * (size_t)N, hipMemcpyHostToDevice, s.hb.stream) != hipSuccess) {
+            (void)hipStreamSynchronize(s.hb.stream);
+            return XRSFM_BA_ENODEV;
+        }
+        if (int e = frames_prep(s.hb.stream, b)) { (void)hipStreamSynchronize(s.hb.stream); return e; }
+    }
+    *out = fs.release();
+    return XRSFM_BA_OK;
+}
+
+int frames_from_images_impl(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width, const int32_t* height,
+                            const int64_t* pixel_ptr, const uint8_t* pixels, xrsfm_ba_frames** out) {
+    const char* who = "xrsfm_ba_frames_from_images";
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (opt && !dopt) return bad("NULL descriptor options");
+    if (opt && dopt->upright != 0 && dopt->upright != 1) return bad("upright outside {0, 1}");
+    if (int e = sift_check(who, opt, n_images, width, height, pixel_ptr, pixels)) return e;
+    if (!out) return bad("NULL out");
+    std::unique_ptr<xrsfm_ba_frames> fs(new xrsfm_ba_frames);
+    fs->n_frames = n_images; fs->from_images = true; fs->nl = opt->num_octaves * xsift::kKeyLevels;
+    if (n_images > 0) {
+        if (int e = sift_no_device()) return e;
+        SiftResult R;
+        SiftSink sink;
+        const SiftDescRequest dq{(int)dopt->upright, false, false};
+        if (int e = sift_run(opt, n_images, width, height, pixel_ptr, pixels, nullptr, &R, &dq, &sink)) return e;
+        fs->key_ptr.resize((size_t)n_images + 1);
+        for (int i = 0; i < n_images; ++i) fs->key_ptr[(size_t)i + 1] = fs->key_ptr[(size_t)i] + R.count[(size_t)i];
+        fs->level_count = R.level_count;
+        const int64_t N = fs->key_ptr[(size_t)n_images];
+        int64_t held = 0;
+        for (const FramesBlock& c : sink.chunks) held += c.n;
+        if (held != N) return XRSFM_BA_EINTERNAL;
+        if (N > 0) {
+            FramesStream s;
+            if (!s.ok) return XRSFM_BA_ENODEV;
+            hipStream_t st = s.hb.stream;
+            FramesBlock& b = fs->blk;
+            if (sink.chunks.size() == 1) {
+                b = sink.chunks[0];
+                sink.chunks.clear();
+            } else {                                           // the set grew across chunks: their arrays into one block
+                b.n = N; b.L = frames_layout(N, true);
+                b.p = g_cache.get(0, b.L.total, &b.cls);
+                if (!b.p) return XRSFM_BA_ENOMEM;
+                size_t at = 0;
+                bool ok = true;
+                for (const FramesBlock& c : sink.chunks) {
+                    const size_t n = (size_t)c.n;
+                    ok = ok && hipMemcpyAsync(b.at(b.L.o_keys) + 16 * at, c.at(c.L.o_keys), 16 * n, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                         hipMemcpyAsync(b.at(b.L.o_desc) + 128 * at, c.at(c.L.o_desc), 128 * n, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                         hipMemcpyAsync(b.at(b.L.o_loc) + 16 * at, c.at(c.L.o_loc), 16 * n, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                         hipMemcpyAsync(b.at(b.L.o_sign) + at, c.at(c.L.o_sign), n, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                         hipMemcpyAsync(b.at(b.L.o_w) + 4 * at, c.at(c.L.o_w), 4 * n, hipMemcpyDeviceToDevice, st) == hipSuccess;
+                    at += n;
+                }
+                if (hipStreamSynchronize(st) != hipSuccess || !ok) return XRSFM_BA_ENODEV;
+            }
+            if (int e = frames_prep(st, b)) { (void)hipStreamSynchronize(st); return e; }
+        }
+    }
+    *out = fs.release();
+    return XRSFM_BA_OK;
+}
+
+int frames_info_impl(const xrsfm_ba_frames* fs, int32_t* n_frames, int64_t* key_ptr, uint64_t* device_bytes) {
+    if (!fs) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_info: NULL frame set\n"); return XRSFM_BA_EINVAL; }
+    if (n_frames) *n_frames = fs->n_frames;
+    if (key_ptr) memcpy(key_ptr, fs->key_ptr.data(), sizeof(int64_t) * fs->key_ptr.size());
+    if (device_bytes) *device_bytes = fs->blk.p ? (uint64_t)fs->blk.cls : 0;
+    return XRSFM_BA_OK;
+}
+
+int frames_download_impl(const xrsfm_ba_frames* fs, int64_t capacity, float* keys, uint8_t* desc, int32_t* loc, int8_t* sign, int32_t* level_count) {
+    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_download: %s\n", what); return XRSFM_BA_EINVAL; };
+    if (!fs) return bad("NULL frame set");
+    if (!fs->from_images && (loc || sign || level_count)) return bad("loc, sign and level_count exist only for sets made from images");
+    const int64_t N = fs->key_ptr.back();
+    if (capacity < N) {
+        fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_download: capacity %lld is below the %lld keypoints of the set\n", (long long)capacity, (long long)N);
+        return XRSFM_BA_EINVAL;
+    }
+    if (N > 0 && (keys || desc || loc || sign)) {
+        HIPCHK(hipSetDevice(0));
+        FramesStream s;
+        if (!s.ok) return XRSFM_BA_ENODEV;
+        hipStream_t st = s.hb.stream;
+        const FramesBlock& b = fs->blk;
+        const size_t n = (size_t)N, h_keys = 0, h_desc = 16 * n, h_loc = h_desc + 128 * n, h_sign = h_loc + 16 * n, h_w = h_sign + ((n + 15) & ~(size_t)15), h_total = h_w + 4 * n;
+        FramesPin back;
+        if (!back.get(h_total)) return XRSFM_BA_ENOMEM;
+        bool ok = true;
+        if (keys) ok = ok && hipMemcpyAsync(back.p + h_keys, b.at(b.L.o_keys), 16 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (desc) ok = ok && hipMemcpyAsync(back.p + h_desc, b.at(b.L.o_desc), 128 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (loc) ok = ok && hipMemcpyAsync(back.p + h_loc, b.at(b.L.o_loc), 16 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (sign) ok = ok && hipMemcpyAsync(back.p + h_sign, b.at(b.L.o_sign), n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (keys && fs->from_images) ok = ok && hipMemcpyAsync(back.p + h_w, b.at(b.L.o_w), 4 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (hipStreamSynchronize(st) != hipSuccess || !ok) return XRSFM_BA_ENODEV;
+        if (keys) {
+            memcpy(keys, back.p + h_keys, 16 * n);
+            const float* w = (const float*)(back.p + h_w);
+            if (fs->from_images) for (size_t k = 0; k < n; ++k) keys[4 * k + 3] = xsiftd::mirror(w[k]);          // DownloadKeypoints
+        }
+        if (desc) for (size_t i = 0; i < 128 * n; ++i) desc[i] = (uint8_t)(back.p[h_desc + i] ^ 0x80u);             // (k_match_prep flipped them)
+        if (loc) memcpy(loc, back.p + h_loc, 16 * n);
+        if (sign) memcpy(sign, back.p + h_sign, n);
+    }
+    if (level_count && !fs->level_count.empty()) memcpy(level_count, fs->level_count.data(), sizeof(int32_t) * fs->level_count.size());
+    return XRSFM_BA_OK;
+}
+
+// The verification half of xrsfm_ba_frames_match.  Every sub-batch of the matching leaves its matches in the workspace the next one
+// overwrites, so frames_gather moves them out at once, compacted and with their coordinates (k_frames_gather), into a block of the
+// sub-batch's own; frames_verify then puts the blocks behind one another and runs k_verify_pairs ONCE on every pair of the call: a
+// pair keeps a workgroup busy for its whole scan, and a launch per sub-batch would leave most of the device idle for that long.
+struct FramesGathered {                        // of one sub-batch
+    FramesDev blk;                             // [records | coordinates double[4] per match | matches]
+    FramesPin stage;
+    size_t o_m = 0, o_mt = 0;
+    int64_t first = 0, n = 0;                  // its matches in the call's arrays
+};
+struct FramesVerdict {                         // of the whole call, held back until nothing can fail any more
+    std::vector<int32_t> beg;                  // [n_pairs] first match of the pair in the call's gathered arrays
+    std::vector<unsigned char> stat, mask;
+    std::vector<double> F;                     // [n_pairs][9]
+    std::vector<int32_t> ninl, ntr, best, matches;
+};
+
+// after match_collect: the matches of the sub-batch's np pairs (prs their records, mm_dev their matches on the device) gathered
+// behind the `total` matches of the sub-batches before
+int frames_gather(hipStream_t st, const xrsfm_ba_frames* fs, int np, const int32_t* pairs, const MatchPair* prs, const int32_t* mm_dev, const MatchResult& R,
+                  int64_t* total, FramesVerdict* V, std::vector<std::unique_ptr<FramesGathered>>* held) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    std::vector<int32_t> count((size_t)np), beg((size_t)np);
+    for (int q = 0; q < np; ++q) count[(size_t)q] = R.count[(size_t)pairs[q]];
+    int64_t Nm = 0;
+    if (!xframes::plan_gather((size_t)np, count.data(), beg.data(), &Nm) || *total + Nm > 0x7fffffff) return XRSFM_BA_ETOOBIG;
+    std::unique_ptr<FramesGathered> g(new FramesGathered);
+    g->first = *total; g->n = Nm;
+    for (int q = 0; q < np; ++q) V->beg[(size_t)pairs[q]] = (int32_t)(*total + beg[(size_t)q]);
+    *total += Nm;
+    if (Nm == 0) return XRSFM_BA_OK;
+    const size_t rec_bytes = sizeof(FramesGatherPair) * (size_t)np;
+    g->o_m = al(rec_bytes); g->o_mt = g->o_m + al(sizeof(double) * 4 * (size_t)Nm);
+    if (!g->blk.get(g->o_mt + al(sizeof(int32_t) * 2 * (size_t)Nm)) || !g->stage.get(rec_bytes)) return XRSFM_BA_ENOMEM;
+    FramesGatherPair* gp = (FramesGatherPair*)g->stage.p;
+    for (int q = 0; q < np; ++q)
+        gp[q] = FramesGatherPair{prs[q].row_off, prs[q].a_off, prs[q].b_off, beg[(size_t)q], count[(size_t)q], prs[q].n_a, prs[q].n_b};
+    unsigned char* base = (unsigned char*)g->blk.p;
+    if (hipMemcpyAsync(base, g->stage.p, rec_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipStreamSynchronize(st); return XRSFM_BA_ENODEV; }
+    hipLaunchKernelGGL(k_frames_gather, dim3((unsigned)np), dim3(kFramesThreads), 0, st, (const FramesGatherPair*)base, mm_dev, (const float4*)fs->blk.at(fs->blk.L.o_keys),
+                       (double2*)(base + g->o_m), (int2*)(base + g->o_mt));
+    if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(st); return XRSFM_BA_ENODEV; }
+    held->push_back(std::move(g));              // (block and staging stay until the stream has drained)
+    return XRSFM_BA_OK;
+}
+
+// every pair of the call, in the caller's order (a pair without rows or columns has no matches and gets its verdict like any other):
+// records and dyn rows up, the gathered blocks into place, k_verify_pairs, one read-back of matches, masks and per-pair results
+int frames_verify(hipStream_t st, const xrsfm_ba_fund_options* vopt, int32_t n_pairs, const double* pair_max_error, const uint32_t* pair_seed, int64_t Nm,
+                  const std::vector<std::unique_ptr<FramesGathered>>& held, hipEvent_t* ev, const MatchResult& R, FramesVerdict* V) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int Np = n_pairs;
+    std::vector<FundPair> fp((size_t)Np);
+    FundDyn dyn;
+    for (int j = 0; j < Np; ++j)
+        fp[(size_t)j] = fund_pair_record(vopt, V->beg[(size_t)j], R.count[(size_t)j], pair_max_error ? pair_max_error + j : nullptr, pair_seed ? pair_seed + j : nullptr, dyn);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
+    const size_t o_pr = take(sizeof(FundPair) * (size_t)Np), o_dyn = take(sizeof(int32_t) * dyn.rows.size());
+    const size_t in_bytes = off, o_m = take(sizeof(double) * 4 * (size_t)Nm), out0 = off;
+    const size_t o_F = take(sizeof(double) * 9 * (size_t)Np), o_ninl = take(sizeof(int) * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
+                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_mask = take((size_t)Nm), o_mt = take(sizeof(int32_t) * 2 * (size_t)Nm);
+    const size_t out_bytes = off - out0;
+    FramesDev blk;
+    FramesPin stage, back;
+    if (!blk.get(off) || !stage.get(in_bytes) || !back.get(out_bytes)) return XRSFM_BA_ENOMEM;
+    unsigned char* base = (unsigned char*)blk.p;
+    memcpy(stage.p + o_pr, fp.data(), sizeof(FundPair) * (size_t)Np);
+    if (!dyn.rows.empty()) memcpy(stage.p + o_dyn, dyn.rows.data(), sizeof(int32_t) * dyn.rows.size());
+    int e = 0;
+    if (hipMemcpyAsync(base, stage.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    for (const auto& g : held) {
+        if (e) break;
+        const unsigned char* src = (const unsigned char*)g->blk.p;
+        if (hipMemcpyAsync(base + o_m + 32 * (size_t)g->first, src + g->o_m, 32 * (size_t)g->n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(base + o_mt + 8 * (size_t)g->first, src + g->o_mt, 8 * (size_t)g->n, hipMemcpyDeviceToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    }
+    if (ev) (void)hipEventRecord(ev[0], st);
+    if (!e) {
+        hipLaunchKernelGGL(k_verify_pairs, dim3(Np), dim3(kFundThreads), sizeof(FundShared), st, (const FundPair*)(base + o_pr), Np, fund_params(vopt),
+                           (const double*)(base + o_m), (const int32_t*)(base + o_dyn), (double*)(base + o_F), (unsigned char*)(base + o_stat), (unsigned char*)(base + o_mask),
+                           (int*)(base + o_ninl), (int*)(base + o_ntr), (int*)(base + o_best));
+        if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+    }
+    if (ev) (void)hipEventRecord(ev[1], st);
+    if (!e && hipMemcpyAsync(back.p, base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (e) return e;
+    const unsigned char* o = back.p - out0;                // (offsets above are relative to the block)
+    V->stat.assign(o + o_stat, o + o_stat + Np);
+    V->F.assign((const double*)(o + o_F), (const double*)(o + o_F) + 9 * (size_t)Np);
+    V->ninl.assign((const int32_t*)(o + o_ninl), (const int32_t*)(o + o_ninl) + Np);
+    V->ntr.assign((const int32_t*)(o + o_ntr), (const int32_t*)(o + o_ntr) + Np);
+    V->best.assign((const int32_t*)(o + o_best), (const int32_t*)(o + o_best) + Np);
+    V->mask.assign(o + o_mask, o + o_mask + (size_t)Nm);
+    V->matches.assign((const int32_t*)(o + o_mt), (const int32_t*)(o + o_mt) + 2 * (size_t)Nm);
+    return XRSFM_BA_OK;
+}
+
+int frames_match_impl(const xrsfm_ba_frames* fs, const xrsfm_ba_match_options* mopt, const xrsfm_ba_fund_options* vopt, int32_t n_pairs, const int32_t* pair_a,
+                      const int32_t* pair_b, const double* pair_max_error, const uint32_t* pair_seed, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
+                      int32_t* num_row, int32_t* num_col, uint8_t* status, double* F, uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial,
+                      uint8_t* accepted) {
+    const char* who = "xrsfm_ba_frames_match";
+    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
+    if (!fs) return bad("NULL frame set");
+    if (int e = match_check_options(who, mopt, n_pairs, fs->n_frames, matches_capacity)) return e;
+    if (vopt) { if (int e = fund_check_options(who, vopt, n_pairs)) return e; }
+    else if (status || F || inlier_mask || num_inliers || num_trials || best_trial || accepted) return bad("verification outputs without verification options");
+    if (n_pairs == 0) return XRSFM_BA_OK;
+    if (!match_ptr) return bad("NULL match_ptr");
+    if (!pair_a || !pair_b) return bad("NULL pair_a or pair_b");
+    for (int p = 0; p < n_pairs; ++p)
+        if (pair_a[p] < 0 || pair_a[p] >= fs->n_frames || pair_b[p] < 0 || pair_b[p] >= fs->n_frames) return bad("frame index out of range");
+    if (matches_capacity > 0 && !matches) return bad("NULL matches");
+    if (vopt && (!status || !F || !inlier_mask)) return bad("NULL status, F or inlier_mask");
+    if (vopt) if (int e = fund_check_pair_errors(who, n_pairs, pair_max_error)) return e;
+    if (int e = frames_no_device()) return e;
+    const int n_frames = fs->n_frames;
+    std::vector<int32_t> clip((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) clip[(size_t)f] = (int32_t)std::min<int64_t>(fs->key_ptr[(size_t)f + 1] - fs->key_ptr[(size_t)f], mopt->max_features);
+    MatchResult R;
+    R.count.assign((size_t)n_pairs, 0); R.num_row.assign((size_t)n_pairs, 0); R.num_col.assign((size_t)n_pairs, 0);
+    R.rows.assign((size_t)n_pairs, std::vector<int32_t>());
+    FramesVerdict V;
+    V.beg.assign((size_t)n_pairs, 0);
+    MatchPlan plan;
+    match_plan(clip, n_pairs, pair_a, pair_b, fs->blk.p ? fs->blk.L.total : 0, false, &plan);
+    int64_t gathered = 0;
+    if (!plan.live.empty() || vopt) {
+        HIPCHK(hipSetDevice(0));
+        const float* tab = match_table_device();
+        if (!tab) return XRSFM_BA_ENOMEM;
+        FramesStream s;
+        if (!s.ok) return XRSFM_BA_ENODEV;
+        hipStream_t st = s.hb.stream;
+        FramesDev ws;
+        FramesPin stage, back;
+        if (!plan.live.empty() && (!ws.get(plan.ws_bytes) || !stage.get(plan.in_max) || !back.get(plan.back_max))) return XRSFM_BA_ENOMEM;
+        // XRSFM_BA_MATCH_TIMING: the kernels' times from events on the stream, one line on stderr (tools/frame_set_timing.py)
+        struct Events { hipEvent_t ev[7] = {}; bool on = false; ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); } } tm;
+        if (getenv("XRSFM_BA_MATCH_TIMING")) { tm.on = true; for (hipEvent_t& x : tm.ev) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; tm.on = false; } }
+        float ms_dots = 0.f, ms_select = 0.f, ms_gather = 0.f, ms_verify = 0.f;
+        const MatchParams prm{mopt->max_distance, mopt->max_ratio, mopt->mutual_best ? 1 : 0};
+        if (vopt) fund_kernel_setup();
+        const FramesBlock& fb = fs->blk;
+        std::vector<std::unique_ptr<FramesGathered>> held;
+        int e = 0;
+        for (size_t bi = 0; bi < plan.batches.size() && !e; ++bi) {
+            const MatchBatch& b = plan.batches[bi];
+            const MatchLayout& L = b.L;
+            const int np = (int)(b.last - b.first);
+            unsigned char* base = (unsigned char*)ws.p;
+            const MatchPair* prs = (const MatchPair*)(stage.p + L.o_pr);
+            match_fill_records(stage.p, L, np, [&](int q, MatchPair* pr) {
+                const int p = plan.live[b.first + (size_t)q];
+                pr->a_off = fs->key_ptr[(size_t)pair_a[p]]; pr->b_off = fs->key_ptr[(size_t)pair_b[p]];
+                pr->n_a = clip[(size_t)pair_a[p]]; pr->n_b = clip[(size_t)pair_b[p]];
+            });
+            if (hipMemcpyAsync(base, stage.p, L.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if ((e = match_launch(st, base, L, np, (const uint8_t*)fb.at(fb.L.o_desc), (const int32_t*)fb.at(fb.L.o_prep), prm, tab, tm.on ? tm.ev : nullptr))) break;
+            // without the verification the matches come back with the counts; with it only the counts do
+            const size_t back_bytes = vopt ? sizeof(int32_t) * 4 * (size_t)np : L.back_bytes;
+            if (hipMemcpyAsync(back.p, base + L.o_cnt, back_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            if (hipStreamSynchronize(st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
+            const int32_t* cnt = (const int32_t*)back.p;
+            const int32_t* mm = vopt ? nullptr : (const int32_t*)(back.p + (L.o_m - L.o_cnt));
+            if (!match_collect(cnt, mm, prs, np, plan.live.data() + b.first, &R)) { e = XRSFM_BA_EINTERNAL; break; }
+            if (tm.on) {
+                float a = 0.f;
+                if (hipEventElapsedTime(&a, tm.ev[0], tm.ev[1]) == hipSuccess) ms_dots += a;
+                if (hipEventElapsedTime(&a, tm.ev[1], tm.ev[2]) == hipSuccess) ms_select += a;
+            }
+            if (!vopt) continue;
+            if (tm.on) (void)hipEventRecord(tm.ev[3], st);
+            if ((e = frames_gather(st, fs, np, plan.live.data() + b.first, prs, (const int32_t*)(base + L.o_m), R, &gathered, &V, &held))) break;
+            if (tm.on) {                                   // (waits for the gather: only when the times are asked for)
+                float a = 0.f;
+                (void)hipEventRecord(tm.ev[4], st);
+                if (hipEventSynchronize(tm.ev[4]) == hipSuccess && hipEventElapsedTime(&a, tm.ev[3], tm.ev[4]) == hipSuccess) ms_gather += a;
+            }
+        }
+        if (!e && vopt) {
+            e = frames_verify(st, vopt, n_pairs, pair_max_error, pair_seed, gathered, held, tm.on ? tm.ev + 5 : nullptr, R, &V);
+            float a = 0.f;
+            if (tm.on && !e && hipEventElapsedTime(&a, tm.ev[5], tm.ev[6]) == hipSuccess) ms_verify = a;
+        }
+        if (e) { (void)hipStreamSynchronize(st); return e; }
+        if (tm.on) fprintf(stderr, "[xrsfm_ba] frames match timing: dots %.4f ms, select %.4f ms, gather %.4f ms, verify %.4f ms, launches %zu\n", ms_dots, ms_select,
+                           ms_gather, ms_verify, plan.batches.size());
+    }
+    int64_t need = 0;
+    for (int p = 0; p < n_pairs; ++p) need += R.count[(size_t)p];
+    if (need > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] %s: %lld matches, above INT32_MAX\n", who, (long long)need); return XRSFM_BA_ETOOBIG; }
+    if (need > matches_capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: matches_capacity %lld is below the %lld matches of the call\n", who, (long long)matches_capacity, (long long)need);
+        return XRSFM_BA_EINVAL;
+    }
+    match_ptr[0] = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const size_t c = (size_t)R.count[(size_t)p];
+        if (vopt) {                                    // (the gathered arrays are in the caller's order: beg[p] is match_ptr[p])
+            const size_t b0 = (size_t)V.beg[(size_t)p];
+            if (c) memcpy(matches + 2 * match_ptr[p], V.matches.data() + 2 * b0, sizeof(int32_t) * 2 * c);
+            if (c) memcpy(inlier_mask + match_ptr[p], V.mask.data() + b0, c);
+            fund_publish_pair(vopt, V.stat[(size_t)p], &V.F[9 * (size_t)p], V.ninl[(size_t)p], R.count[(size_t)p], status + p, F + 9 * (size_t)p, accepted ? accepted + p : nullptr);
+        } else if (c) {
+            memcpy(matches + 2 * match_ptr[p], R.rows[(size_t)p].data(), sizeof(int32_t) * 2 * c);
+        }
+        match_ptr[p + 1] = match_ptr[p] + R.count[(size_t)p];
+    }
+    if (num_row) memcpy(num_row, R.num_row.data(), sizeof(int32_t) * (size_t)n_pairs);
+    if (num_col) memcpy(num_col, R.num_col.data(), sizeof(int32_t) * (size_t)n_pairs);
+    if (vopt) {
+        if (num_inliers) memcpy(num_inliers, V.ninl.data(), sizeof(int32_t) * (size_t)n_pairs);
+        if (num_trials) memcpy(num_trials, V.ntr.data(), sizeof(int32_t) * (size_t)n_pairs);
+        if (best_trial) memcpy(best_trial, V.best.data(), sizeof(int32_t) * (size_t)n_pairs);
+    }
+    return XRSFM_BA_OK;
+}
+}  // namespace
+
+int xrsfm_ba_frames_create(int32_t n_frames, const int64_t* key_ptr, const float* keys, const uint8_t* desc, xrsfm_ba_frames** out) {
+    return no_throw([&] { return frames_create_impl(n_frames, key_ptr, keys, desc, out); });
+}
+
+int xrsfm_ba_frames_from_images(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width, const int32_t* height,
+                                const int64_t* pixel_ptr, const uint8_t* pixels, xrsfm_ba_frames** out) {
+    return no_throw([&] { return frames_from_images_impl(opt, dopt, n_images, width, height, pixel_ptr, pixels, out); });
+}
+
+int xrsfm_ba_frames_info(const xrsfm_ba_frames* fs, int32_t* n_frames, int64_t* key_ptr, uint64_t* device_bytes) {
+    return no_throw([&] { return frames_info_impl(fs, n_frames, key_ptr, device_bytes); });
+}
+
+int xrsfm_ba_frames_download(const xrsfm_ba_frames* fs, int64_t capacity, float* keys, uint8_t* desc, int32_t* loc, int8_t* sign, int32_t* level_count) {
+    return no_throw([&] { return frames_download_impl(fs, capacity, keys, desc, loc, sign, level_count); });
+}
+
+int xrsfm_ba_frames_match(const xrsfm_ba_frames* fs, const xrsfm_ba_match_options* mopt, const xrsfm_ba_fund_options* vopt, int32_t n_pairs, const int32_t* pair_a,
+                          const int32_t* pair_b, const double* pair_max_error, const uint32_t* pair_seed, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
+                          int32_t* num_row, int32_t* num_col, uint8_t* status, double* F, uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials,
+                          int32_t* best_trial, uint8_t* accepted) {
+    return no_throw([&] { return frames_match_impl(fs, mopt, vopt, n_pairs, pair_a, pair_b, pair_max_error, pair_seed, matches_capacity, match_ptr, matches, num_row,
+                                                   num_col, status, F, inlier_mask, num_inliers, num_trials, best_trial, accepted); });
+}
+
+void xrsfm_ba_frames_destroy(xrsfm_ba_frames* fs) {
+    if (!fs) return;
+    (void)no_throw([&] { if (fs->blk.p) (void)hipSetDevice(0); delete fs; return XRSFM_BA_OK; });
 }
 
 // ---------------------------------------------------------------- diagnostics
