@@ -42,6 +42,7 @@
 #include "ba_refine.h"
 #include "ba_sift.h"
 #include "ba_sift_desc.h"
+#include "ba_stage.h"
 #include "ba_tri.h"
 #include "ba_trust_region.h"
 #include "ba_wide.h"
@@ -335,6 +336,101 @@ struct PinnedPool {
     }
 };
 PinnedPool g_pinned;
+
+// What a one-shot call holds of the three pools above goes back on every way out of it, an exception included.
+struct PinLease {                             // a block of g_pinned
+    unsigned char* p = nullptr; size_t cap = 0;
+    PinLease() = default;
+    PinLease(const PinLease&) = delete;
+    PinLease& operator=(const PinLease&) = delete;
+    ~PinLease() { if (p) g_pinned.put(p, cap); }
+    bool get(size_t bytes) { p = static_cast<unsigned char*>(g_pinned.get(bytes ? bytes : 8, &cap)); return p != nullptr; }
+    unsigned char* data() const { return p; }
+};
+struct DevLease {                             // a block of g_cache
+    unsigned char* p = nullptr; size_t cls = 0; int dev = 0;
+    DevLease() = default;
+    DevLease(const DevLease&) = delete;
+    DevLease& operator=(const DevLease&) = delete;
+    ~DevLease() { if (p) g_cache.put(dev, p, cls); }
+    bool get(int device, size_t bytes) { dev = device; p = static_cast<unsigned char*>(g_cache.get(device, bytes, &cls)); return p != nullptr; }
+    unsigned char* data() const { return p; }
+};
+struct StreamLease {                          // a stream bundle of g_bundles
+    HostBundle hb; bool ok; int dev;
+    explicit StreamLease(int device) : dev(device) { ok = g_bundles.get(device, &hb); }
+    StreamLease(const StreamLease&) = delete;
+    StreamLease& operator=(const StreamLease&) = delete;
+    ~StreamLease() { if (ok) g_bundles.put(dev, hb); }
+    hipStream_t stream() const { return hb.stream; }
+};
+
+// The one-shot call on device 0 for a finished layout: leases, fill(stage) into the pinned input block, ONE upload of the inputs,
+// launch(stream, base) (kernels, and what goes with them: a memset, events, small copies; nonzero: its error), ONE read-back of the
+// outputs, and publish(view) once the stream has drained and nothing has failed.  The stream is drained on every way out.
+template <typename Fill, typename Launch, typename Publish>
+int staged_call(const xstage::Layout& L, Fill&& fill, Launch&& launch, Publish&& publish) {
+    StreamLease s(0);
+    if (!s.ok) return XRSFM_BA_ENODEV;
+    DevLease blk;
+    if (!blk.get(0, L.total())) return XRSFM_BA_ENOMEM;
+    PinLease stage, back;             // (pinned staging from a recycled pool: see PinnedPool)
+    const bool have_stage = stage.get(L.in_bytes), have_back = back.get(L.out_bytes);
+    if (!have_stage || !have_back) return XRSFM_BA_ENOMEM;
+    unsigned char* const base = blk.data();
+    const hipStream_t st = s.stream();
+    int e = fill(stage.data());
+    if (!e && hipMemcpyAsync(base, stage.data(), L.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (!e) {
+        e = launch(st, base);
+        if (!e && hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
+    }
+    if (!e && hipMemcpyAsync(back.data(), base + L.out0, L.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (!e) publish(xstage::View{back.data(), L.out0});
+    return e;
+}
+
+// ---- the argument checks that the one-shot entries share; who: the entry's name
+int complain(const char* who, const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; }
+
+template <typename T> int check_offsets(const char* who, const char* name, const T* ptr, int64_t n) {
+    const char* fault = xstage::offsets_fault(ptr, n);
+    if (fault) { fprintf(stderr, "[xrsfm_ba] %s: %s %s\n", who, name, fault); return XRSFM_BA_EINVAL; }
+    return XRSFM_BA_OK;
+}
+
+bool all_finite(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int check_confidence(const char* who, double v) { return v < 0.0 || v > 1.0 ? complain(who, "confidence outside [0, 1]") : XRSFM_BA_OK; }
+int check_inlier_ratio(const char* who, double v) { return v < 0.0 || v > 1.0 ? complain(who, "min_inlier_ratio outside [0, 1]") : XRSFM_BA_OK; }
+
+int require_device(const char* what) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the %s has no CPU fallback\n", what);
+        return XRSFM_BA_ENODEV;
+    }
+    return XRSFM_BA_OK;
+}
+
+// the camera record of a pose; intr: its eight intrinsics, or null (zeros)
+CamRec cam_record(const double* q, const double* t, const double* intr) {
+    CamRec c;
+    for (int k = 0; k < 4; ++k) c.q[k] = q[k];
+    for (int k = 0; k < 3; ++k) c.t[k] = t[k];
+    c.pad = 0.0;
+    for (int k = 0; k < 8; ++k) c.intr[k] = intr ? intr[k] : 0.0;
+    return c;
+}
+
+// n matches as the kernels read them: (xa, ya, xb, yb) per match
+void interleave_matches(const double* xy_a, const double* xy_b, size_t n, double* out) {
+    for (size_t i = 0; i < n; ++i) { out[4 * i] = xy_a[2 * i]; out[4 * i + 1] = xy_a[2 * i + 1]; out[4 * i + 2] = xy_b[2 * i]; out[4 * i + 3] = xy_b[2 * i + 1]; }
+}
 
 // Deferred release of the host side of large contexts (xrsfm_ba_destroy).  One joinable thread, started on first use.
 struct Reaper {
@@ -2355,21 +2451,19 @@ int xrsfm_ba_warmup(int device, int64_t n_obs_hint, int64_t n_points_hint, int64
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return XRSFM_BA_ENODEV;
         if (device < 0 || device >= ndev) return XRSFM_BA_EINVAL;
         HIPCHK(hipSetDevice(device));
-        HostBundle hb;
-        if (!g_bundles.get(device, &hb)) return XRSFM_BA_ENODEV;
-        set_kernel_attributes(device);
-        // the first launch loads the code object; device packing and the key generation bring rocPRIM's kernels with them (same object)
-        double* probe = nullptr;
-        size_t cls = 0;
-        probe = (double*)g_cache.get(device, 256 * sizeof(double), &cls);
         int rc = XRSFM_BA_OK;
-        if (!probe) rc = XRSFM_BA_ENOMEM;
-        else {
-            hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, hb.stream, probe, 0.0, (size_t)256);
-            if (hipStreamSynchronize(hb.stream) != hipSuccess) rc = XRSFM_BA_ENODEV;
-            g_cache.put(device, probe, cls);
+        {
+            StreamLease s(device);
+            if (!s.ok) return XRSFM_BA_ENODEV;
+            set_kernel_attributes(device);
+            // the first launch loads the code object; device packing and the key generation bring rocPRIM's kernels with them (same object)
+            DevLease probe;
+            if (!probe.get(device, 256 * sizeof(double))) rc = XRSFM_BA_ENOMEM;
+            else {
+                hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, s.stream(), (double*)probe.data(), 0.0, (size_t)256);
+                if (hipStreamSynchronize(s.stream()) != hipSuccess) rc = XRSFM_BA_ENODEV;
+            }
         }
-        g_bundles.put(device, hb);
         if (rc != XRSFM_BA_OK || n_obs_hint <= 0) return rc;
         // Device buffers of a problem of about this size: the sizes xrsfm_ba_create / the Cholesky set-up ask for, in units of the
         // slot count (observations + tile padding), the point and the camera count; every block goes straight back to the cache.
@@ -2689,9 +2783,9 @@ int xrsfm_ba_download(xrsfm_ba_context* c, double* cam_q, double* cam_t, double*
     const size_t cam_bytes = (cam_q || cam_t) ? sizeof(CamRec) * (size_t)k.n_cams : 0;
     const size_t off_P = (cam_bytes + 255) & ~(size_t)255, pt_bytes = points ? sizeof(double) * 3 * (size_t)k.n_pts : 0;
     if (cam_bytes + pt_bytes == 0) return 0;
-    size_t cap = 0;
-    unsigned char* host = static_cast<unsigned char*>(g_pinned.get(off_P + pt_bytes, &cap));
-    if (!host) return XRSFM_BA_ENOMEM;
+    PinLease pin;
+    if (!pin.get(off_P + pt_bytes)) return XRSFM_BA_ENOMEM;
+    unsigned char* const host = pin.data();
     bool ok = true;
     if (cam_bytes) ok = hipMemcpyAsync(host, c->d.cam, cam_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
     if (ok && pt_bytes) ok = hipMemcpyAsync(host + off_P, c->d.P, pt_bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
@@ -2710,7 +2804,6 @@ int xrsfm_ba_download(xrsfm_ba_context* c, double* cam_q, double* cam_t, double*
                 for (int a = 0; a < 3; ++a) points[3 * (size_t)k.pt_orig[j] + a] = P[3 * (size_t)j + a];
         });
     }
-    g_pinned.put(host, cap);
     return ok ? 0 : XRSFM_BA_ENODEV;
 }
 
@@ -2781,9 +2874,9 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     c->recs.clear(); c->ev_used = 0;
     const size_t n_rows_max = opt.verbose ? (size_t)opt.max_iterations + 1 : 0;
     const size_t bytes = sizeof(LbaResult) + sizeof(LbaRow) * n_rows_max;
-    size_t cap = 0;
-    unsigned char* host = static_cast<unsigned char*>(g_pinned.get(bytes, &cap));
-    if (!host) { c->profiling = false; return XRSFM_BA_ENOMEM; }
+    PinLease pin;
+    if (!pin.get(bytes)) { c->profiling = false; return XRSFM_BA_ENOMEM; }
+    unsigned char* const host = pin.data();
     LbaResult* res = reinterpret_cast<LbaResult*>(host);
     LbaRow* rows = reinterpret_cast<LbaRow*>(host + sizeof(LbaResult));
     memset(res, 0, sizeof(*res));
@@ -2812,7 +2905,6 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     }
     c->recs.clear(); c->ev_used = 0;
     c->profiling = false;
-    g_pinned.put(host, cap);
     return e;
 }
 
@@ -2870,12 +2962,11 @@ static int lba_run_batch(int32_t n, xrsfm_ba_context* const* ctxs, const xrsfm_b
     const size_t off_res = (off_order + sizeof(int) * (size_t)n + 255) & ~(size_t)255;
     const size_t off_rows = off_res + sizeof(LbaResult) * (size_t)n;
     const size_t total = off_rows + sizeof(LbaRow) * (size_t)rows_stride * (size_t)n;
-    struct Pin { unsigned char* p = nullptr; size_t cap = 0; ~Pin() { if (p) g_pinned.put(p, cap); } } stage;
-    stage.p = static_cast<unsigned char*>(g_pinned.get(total, &stage.cap));
-    if (!stage.p) return XRSFM_BA_ENOMEM;
-    size_t cls = 0;
-    unsigned char* dev = static_cast<unsigned char*>(g_cache.get(device, off_res, &cls));
-    if (!dev) return XRSFM_BA_ENOMEM;
+    PinLease stage;
+    if (!stage.get(total)) return XRSFM_BA_ENOMEM;
+    DevLease blk;
+    if (!blk.get(device, off_res)) return XRSFM_BA_ENOMEM;
+    unsigned char* const dev = blk.data();
     LbaDev* h_devs = reinterpret_cast<LbaDev*>(stage.p);
     int* h_order = reinterpret_cast<int*>(stage.p + off_order);
     LbaResult* res = reinterpret_cast<LbaResult*>(stage.p + off_res);
@@ -2903,7 +2994,6 @@ static int lba_run_batch(int32_t n, xrsfm_ba_context* const* ctxs, const xrsfm_b
            res, rows, rows_stride);
     bool ok = hipGetLastError() == hipSuccess;
     ok = (hipStreamSynchronize(c0->stream) == hipSuccess) && ok;
-    g_cache.put(device, dev, cls);
     for (int i = 0; ok && i < n; ++i) ok = res[i].status >= 0;
     int e = ok ? XRSFM_BA_OK : XRSFM_BA_ENODEV;
     if (!e) {
@@ -3238,11 +3328,7 @@ static int refine_poses_kernel(const xrsfm_ba_options& o, int32_t n_frames, cons
                                const int32_t* corr_ptr, const double* points3d, const double* uv, const uint8_t* inlier_mask,
                                double* q, double* t, xrsfm_ba_summary* summaries) {
     const auto t_begin = std::chrono::steady_clock::now();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the BA path has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (int e = require_device("BA path")) return e;
     const int device = 0;
     HIPCHK(hipSetDevice(device));
     std::vector<int> m(n_frames, 0), first(n_frames + 1, 0);
@@ -3256,20 +3342,20 @@ static int refine_poses_kernel(const xrsfm_ba_options& o, int32_t n_frames, cons
     const size_t off_P = (sizeof(RefineJob) * (size_t)n_frames + 255) & ~(size_t)255, off_uv = off_P + sizeof(double) * 3 * M;
     const size_t off_res = (off_uv + sizeof(double) * 2 * M + 255) & ~(size_t)255;
     const size_t total = off_res + sizeof(RefineResult) * (size_t)n_frames;
-    size_t cls = 0;
     static const bool trace_phases = std::getenv("XRSFM_BA_TRACE_CALLS") != nullptr;
     const auto t_a = std::chrono::steady_clock::now();
-    unsigned char* dev = static_cast<unsigned char*>(g_cache.get(device, total, &cls));
-    if (!dev) return XRSFM_BA_ENOMEM;
-    HostBundle hb;
-    if (!g_bundles.get(device, &hb)) { g_cache.put(device, dev, cls); return XRSFM_BA_ENODEV; }
+    DevLease blk;
+    if (!blk.get(device, total)) return XRSFM_BA_ENOMEM;
+    unsigned char* const dev = blk.data();
+    StreamLease s(device);
+    if (!s.ok) return XRSFM_BA_ENODEV;
+    const HostBundle& hb = s.hb;
     const auto t_b = std::chrono::steady_clock::now();
     // (round 6) staging in PINNED memory from the recycled pool, results included: the hipMemcpyAsync of the 112-byte result into a
     // pageable vector was where the mapper replay's slow pose refinements sat — 20-28 ms inside that one call, each time right after a
     // KGBA + whole-map filter had released tens of MB of host memory (the runtime pins pageable pages on the fly; tools/runs/r06_call12.sh)
-    struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage;
-    stage.p = (unsigned char*)g_pinned.get(total, &stage.cap);
-    if (!stage.p) { g_bundles.put(device, hb); g_cache.put(device, dev, cls); return XRSFM_BA_ENOMEM; }
+    PinLease stage;
+    if (!stage.get(total)) return XRSFM_BA_ENOMEM;
     double* hP = reinterpret_cast<double*>(stage.data() + off_P);
     double* hU = reinterpret_cast<double*>(stage.data() + off_uv);
     for (int f = 0; f < n_frames; ++f) {
@@ -3323,8 +3409,6 @@ static int refine_poses_kernel(const xrsfm_ba_options& o, int32_t n_frames, cons
     }
     if (hipStreamSynchronize(hb.stream) != hipSuccess) e = XRSFM_BA_ENODEV;
     const auto t_g = std::chrono::steady_clock::now();
-    g_bundles.put(device, hb);
-    g_cache.put(device, dev, cls);
     if (e) return e;
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (trace_phases && secs > 2e-3) {          // (the poll above is part of `sync` in trace mode)
@@ -3408,11 +3492,7 @@ static int filter_tracks_impl(const xrsfm_ba_problem* p, double max_reproj_error
     if (p->n_cams > 0 && (!p->cam_q || !p->cam_t || !p->cam_intr)) return XRSFM_BA_EINVAL;
     if (p->n_points > 0 && !p->points) return XRSFM_BA_EINVAL;
     if (p->n_intr > 0 && (!p->intr_model || !p->intr_params)) return XRSFM_BA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the track filter has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (int e = require_device("track filter")) return e;
     const int Nc = p->n_cams, Np = p->n_points, No = p->n_obs;
     if (Nc < 0 || Np < 0 || No < 0) return XRSFM_BA_EINVAL;
     for (int c2 = 0; c2 < Nc; ++c2) {
@@ -3435,69 +3515,50 @@ static int filter_tracks_impl(const xrsfm_ba_problem* p, double max_reproj_error
     for (int k2 = 0; k2 < No; ++k2) { ocam[k2] = p->obs_cam[order[k2]]; ouv[2 * (size_t)k2] = p->obs_uv[2 * (size_t)order[k2]]; ouv[2 * (size_t)k2 + 1] = p->obs_uv[2 * (size_t)order[k2] + 1]; }
     std::vector<CamRec> cams(Nc);
     for (int i = 0; i < Nc; ++i) {
-        for (int k2 = 0; k2 < 4; ++k2) cams[i].q[k2] = p->cam_q[4 * (size_t)i + k2];
-        for (int k2 = 0; k2 < 3; ++k2) cams[i].t[k2] = p->cam_t[3 * (size_t)i + k2];
-        cams[i].pad = 0.0;
-        for (int k2 = 0; k2 < 8; ++k2) cams[i].intr[k2] = p->intr_params[8 * (size_t)p->cam_intr[i] + k2];
+        cams[i] = cam_record(p->cam_q + 4 * (size_t)i, p->cam_t + 3 * (size_t)i, p->intr_params + 8 * (size_t)p->cam_intr[i]);
         model[i] = p->intr_model[p->cam_intr[i]];
     }
     HIPCHK(hipSetDevice(0));
-    // (round 6) ONE device block from the allocation cache, ONE upload, the two kernels on a recycled stream, ONE download: until
-    // round 5 a call cost 12 hipMalloc + 7 blocking uploads + 5 downloads + 12 hipFree — 0.31 ms for the 2 000 tracks of a frame,
-    // 600 times per 300-frame reconstruction (the mapper replay's "filters" total was larger than its BA total).
-    // Layout: inputs | outputs, every array 256-byte aligned; the outputs travel back as one contiguous range.
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_cam = take(sizeof(CamRec) * (size_t)Nc), o_model = take(sizeof(int) * (size_t)Nc), o_P = take(sizeof(double) * 3 * (size_t)Np),
-                 o_ptr = take(sizeof(int) * ((size_t)Np + 1)), o_ocam = take(sizeof(int) * (size_t)No), o_ouv = take(sizeof(double) * 2 * (size_t)No);
-    const size_t in_bytes = off;
-    const size_t o_centre = take(sizeof(double) * 3 * (size_t)Nc);
-    const size_t out0 = off;
-    const size_t o_cnt = take(sizeof(int) * 2), o_del = take((size_t)No), o_out = take((size_t)Np), o_err = take(sizeof(double) * (size_t)Np),
-                 o_ang = take(sizeof(double) * (size_t)Np);
-    const size_t out_bytes = off - out0;
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls = 0;
-    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
-    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-    int e = 0;
-    {
-        // (pinned staging from a recycled pool: see PinnedPool)
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
-        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-        auto put = [&](size_t o, const void* h, size_t bytes) { if (bytes) memcpy(stage.data() + o, h, bytes); };
-        put(o_cam, cams.data(), sizeof(CamRec) * (size_t)Nc); put(o_model, model.data(), sizeof(int) * (size_t)Nc);
-        put(o_P, p->points, sizeof(double) * 3 * (size_t)Np); put(o_ptr, ptr.data(), sizeof(int) * ((size_t)Np + 1));
-        put(o_ocam, ocam.data(), sizeof(int) * (size_t)No); put(o_ouv, ouv.data(), sizeof(double) * 2 * (size_t)No);
-        hipStream_t st = hb.stream;
-        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e && hipMemsetAsync(base + o_cnt, 0, sizeof(int) * 2, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
+    // (round 6) ONE device block from the allocation cache, ONE upload, the two kernels on a recycled stream, ONE download
+    // (staged_call): until round 5 a call cost 12 hipMalloc + 7 blocking uploads + 5 downloads + 12 hipFree — 0.31 ms for the 2 000
+    // tracks of a frame, 600 times per 300-frame reconstruction (the mapper replay's "filters" total was larger than its BA total).
+    xstage::Layout L;
+    const size_t o_cam = L.take(sizeof(CamRec) * (size_t)Nc), o_model = L.take(sizeof(int) * (size_t)Nc), o_P = L.take(sizeof(double) * 3 * (size_t)Np),
+                 o_ptr = L.take(sizeof(int) * ((size_t)Np + 1)), o_ocam = L.take(sizeof(int) * (size_t)No), o_ouv = L.take(sizeof(double) * 2 * (size_t)No);
+    L.end_inputs();
+    const size_t o_centre = L.take(sizeof(double) * 3 * (size_t)Nc);
+    L.begin_outputs();
+    const size_t o_cnt = L.take(sizeof(int) * 2), o_del = L.take((size_t)No), o_out = L.take((size_t)Np), o_err = L.take(sizeof(double) * (size_t)Np),
+                 o_ang = L.take(sizeof(double) * (size_t)Np);
+    L.end_outputs();
+    return staged_call(L,
+        [&](unsigned char* stage) {
+            auto put = [&](size_t o, const void* h, size_t bytes) { if (bytes) memcpy(stage + o, h, bytes); };
+            put(o_cam, cams.data(), sizeof(CamRec) * (size_t)Nc); put(o_model, model.data(), sizeof(int) * (size_t)Nc);
+            put(o_P, p->points, sizeof(double) * 3 * (size_t)Np); put(o_ptr, ptr.data(), sizeof(int) * ((size_t)Np + 1));
+            put(o_ocam, ocam.data(), sizeof(int) * (size_t)No); put(o_ouv, ouv.data(), sizeof(double) * 2 * (size_t)No);
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
+            if (hipMemsetAsync(base + o_cnt, 0, sizeof(int) * 2, st) != hipSuccess) return XRSFM_BA_ENODEV;
             if (Nc > 0) hipLaunchKernelGGL(k_cam_centres, dim3(cdiv(Nc, 256)), dim3(256), 0, st, (const CamRec*)(base + o_cam), Nc, (double*)(base + o_centre));
             if (Np > 0) hipLaunchKernelGGL(k_filter_tracks, dim3(cdiv(Np, 128)), dim3(128), 0, st, (const CamRec*)(base + o_cam), (const int*)(base + o_model),
                                            (const double*)(base + o_centre), (const double*)(base + o_P), (const int*)(base + o_ptr), (const int*)(base + o_ocam),
                                            (const double*)(base + o_ouv), Np, max_reproj_error, min_tri_angle_rad, (unsigned char*)(base + o_del),
                                            (unsigned char*)(base + o_out), (double*)(base + o_err), (double*)(base + o_ang), (int*)(base + o_cnt));
-            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
-        }
-        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
-            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
-            const unsigned char* del = o + o_del;
-            for (int k2 = 0; k2 < No; ++k2) obs_delete[order[k2]] = del[k2];
-            if (Np) memcpy(track_outlier, o + o_out, (size_t)Np);
-            if (Np && track_error) memcpy(track_error, o + o_err, sizeof(double) * (size_t)Np);
-            if (Np && track_angle) memcpy(track_angle, o + o_ang, sizeof(double) * (size_t)Np);
-            if (num_filtered) { int cnt[2]; memcpy(cnt, o + o_cnt, sizeof(cnt)); num_filtered[0] = cnt[0]; num_filtered[1] = cnt[1]; }
-        }
-    }
-    g_cache.put(0, base, cls);
-    g_bundles.put(0, hb);
-    return e;
+            return 0;
+        },
+        [&](const xstage::View& o) {
+            // (locals: a byte store may alias what the closure refers to, and the loop would reload all three per observation)
+            const unsigned char* del = o.at<unsigned char>(o_del);
+            const int* const ord = order.data();
+            uint8_t* const out = obs_delete;
+            for (int k2 = 0, n = No; k2 < n; ++k2) out[ord[k2]] = del[k2];
+            if (Np) memcpy(track_outlier, o.at<unsigned char>(o_out), (size_t)Np);
+            if (Np && track_error) memcpy(track_error, o.at<double>(o_err), sizeof(double) * (size_t)Np);
+            if (Np && track_angle) memcpy(track_angle, o.at<double>(o_ang), sizeof(double) * (size_t)Np);
+            if (num_filtered) { const int* cnt = o.at<int>(o_cnt); num_filtered[0] = cnt[0]; num_filtered[1] = cnt[1]; }
+        });
 }
 
 int xrsfm_ba_filter_tracks(const xrsfm_ba_problem* p, double max_reproj_error, double min_tri_angle_rad, uint8_t* obs_delete,
@@ -3537,37 +3598,30 @@ static const int32_t* tri_dyn_table(double confidence) {
 static int triangulate_tracks_impl(const xrsfm_ba_tri_options* opt, int32_t n_cams, const double* cam_q, const double* cam_t, int32_t n_tracks,
                                    const int32_t* trk_ptr, const int32_t* obs_cam, const double* obs_xy, double* points, uint8_t* status,
                                    uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_triangulate_tracks: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_cams < 0 || n_tracks < 0) return bad("negative count");
+    const char* who = "xrsfm_ba_triangulate_tracks";
+    if (!opt) return complain(who, "NULL options");
+    if (n_cams < 0 || n_tracks < 0) return complain(who, "negative count");
     if (!std::isfinite(opt->min_tri_angle_rad) || !std::isfinite(opt->max_error_rad) || !std::isfinite(opt->confidence) ||
-        !std::isfinite(opt->min_inlier_ratio)) return bad("non-finite option");
-    if (opt->max_error_rad <= 0.0) return bad("max_error_rad <= 0");
-    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
-    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
-    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
-    if (opt->exhaustive_threshold < 0) return bad("exhaustive_threshold < 0");
-    if (opt->min_tri_angle_rad < 0.0) return bad("min_tri_angle_rad < 0");
+        !std::isfinite(opt->min_inlier_ratio)) return complain(who, "non-finite option");
+    if (opt->max_error_rad <= 0.0) return complain(who, "max_error_rad <= 0");
+    if (int e = check_confidence(who, opt->confidence)) return e;
+    if (int e = check_inlier_ratio(who, opt->min_inlier_ratio)) return e;
+    if (opt->max_num_trials < 1) return complain(who, "max_num_trials < 1");
+    if (opt->exhaustive_threshold < 0) return complain(who, "exhaustive_threshold < 0");
+    if (opt->min_tri_angle_rad < 0.0) return complain(who, "min_tri_angle_rad < 0");
     if (n_tracks == 0) return XRSFM_BA_OK;
-    if (!points || !status || !inlier_mask) return bad("NULL points, status or inlier_mask");
-    if (!trk_ptr) return bad("NULL trk_ptr");
-    if (trk_ptr[0] != 0) return bad("trk_ptr does not start at 0");
-    for (int j = 0; j < n_tracks; ++j)
-        if (trk_ptr[j + 1] < trk_ptr[j]) return bad("trk_ptr decreases");
+    if (!points || !status || !inlier_mask) return complain(who, "NULL points, status or inlier_mask");
+    if (!trk_ptr) return complain(who, "NULL trk_ptr");
+    if (int e = check_offsets(who, "trk_ptr", trk_ptr, n_tracks)) return e;
     const int No = trk_ptr[n_tracks], Nc = n_cams, Nt = n_tracks;
-    if (No > 0 && (!obs_cam || !obs_xy)) return bad("NULL obs_cam or obs_xy");
-    if (Nc > 0 && (!cam_q || !cam_t)) return bad("NULL cam_q or cam_t");
+    if (No > 0 && (!obs_cam || !obs_xy)) return complain(who, "NULL obs_cam or obs_xy");
+    if (Nc > 0 && (!cam_q || !cam_t)) return complain(who, "NULL cam_q or cam_t");
     for (int i = 0; i < No; ++i) {
-        if (obs_cam[i] < 0 || obs_cam[i] >= Nc) return bad("obs_cam out of range");
-        if (!std::isfinite(obs_xy[2 * (size_t)i]) || !std::isfinite(obs_xy[2 * (size_t)i + 1])) return bad("non-finite coordinate");
+        if (obs_cam[i] < 0 || obs_cam[i] >= Nc) return complain(who, "obs_cam out of range");
+        if (!std::isfinite(obs_xy[2 * (size_t)i]) || !std::isfinite(obs_xy[2 * (size_t)i + 1])) return complain(who, "non-finite coordinate");
     }
-    for (size_t i = 0; i < 4 * (size_t)Nc; ++i) if (!std::isfinite(cam_q[i])) return bad("non-finite pose");
-    for (size_t i = 0; i < 3 * (size_t)Nc; ++i) if (!std::isfinite(cam_t[i])) return bad("non-finite pose");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the triangulation has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (!all_finite(cam_q, 4 * (size_t)Nc) || !all_finite(cam_t, 3 * (size_t)Nc)) return complain(who, "non-finite pose");
+    if (int e = require_device("triangulation")) return e;
     TriParams prm;
     prm.min_angle = opt->min_tri_angle_rad;
     prm.max_residual = opt->max_error_rad * opt->max_error_rad;
@@ -3576,86 +3630,60 @@ static int triangulate_tracks_impl(const xrsfm_ba_tri_options* opt, int32_t n_ca
     const int32_t* dyn = tri_dyn_table(opt->confidence);
     const size_t dyn_bytes = sizeof(int32_t) * (size_t)(xtri::kMaxObs + 1) * (xtri::kMaxObs + 1);
     HIPCHK(hipSetDevice(0));
-    // one block from the allocation cache, one upload, two launches, one read-back (the layout of filter_tracks_impl)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_cam = take(sizeof(CamRec) * (size_t)Nc), o_ptr = take(sizeof(int) * ((size_t)Nt + 1)), o_ocam = take(sizeof(int) * (size_t)No),
-                 o_oxy = take(sizeof(double) * 2 * (size_t)No), o_dyn = take(dyn_bytes);
-    const size_t in_bytes = off;
-    const size_t o_centre = take(sizeof(double) * 3 * (size_t)Nc);
-    const size_t out0 = off;
-    const size_t o_pts = take(sizeof(double) * 3 * (size_t)Nt), o_ninl = take(sizeof(int) * (size_t)Nt), o_ntr = take(sizeof(int) * (size_t)Nt),
-                 o_best = take(sizeof(int) * (size_t)Nt), o_stat = take((size_t)Nt), o_mask = take((size_t)No);
-    const size_t out_bytes = off - out0;
+    // one block, one upload, two launches, one read-back (staged_call)
+    xstage::Layout L;
+    const size_t o_cam = L.take(sizeof(CamRec) * (size_t)Nc), o_ptr = L.take(sizeof(int) * ((size_t)Nt + 1)), o_ocam = L.take(sizeof(int) * (size_t)No),
+                 o_oxy = L.take(sizeof(double) * 2 * (size_t)No), o_dyn = L.take(dyn_bytes);
+    L.end_inputs();
+    const size_t o_centre = L.take(sizeof(double) * 3 * (size_t)Nc);
+    L.begin_outputs();
+    const size_t o_pts = L.take(sizeof(double) * 3 * (size_t)Nt), o_ninl = L.take(sizeof(int) * (size_t)Nt), o_ntr = L.take(sizeof(int) * (size_t)Nt),
+                 o_best = L.take(sizeof(int) * (size_t)Nt), o_stat = L.take((size_t)Nt), o_mask = L.take((size_t)No);
+    L.end_outputs();
     // developer aid (tools/triangulate_timing.py): HIP events around the kernel and, in the "tri_phases" build, its phase ticks
     const bool timing = std::getenv("XRSFM_BA_TRI_TIMING") != nullptr;
-    const size_t o_phase = take(4 * sizeof(unsigned long long));
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls = 0;
-    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
-    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-    int e = 0;
-    {
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
-        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-        CamRec* cams = (CamRec*)(stage.data() + o_cam);
-        for (int i = 0; i < Nc; ++i) {
-            for (int k2 = 0; k2 < 4; ++k2) cams[i].q[k2] = cam_q[4 * (size_t)i + k2];
-            for (int k2 = 0; k2 < 3; ++k2) cams[i].t[k2] = cam_t[3 * (size_t)i + k2];
-            cams[i].pad = 0.0;
-            for (int k2 = 0; k2 < 8; ++k2) cams[i].intr[k2] = 0.0;
-        }
-        memcpy(stage.data() + o_ptr, trk_ptr, sizeof(int) * ((size_t)Nt + 1));
-        if (No) { memcpy(stage.data() + o_ocam, obs_cam, sizeof(int) * (size_t)No); memcpy(stage.data() + o_oxy, obs_xy, sizeof(double) * 2 * (size_t)No); }
-        memcpy(stage.data() + o_dyn, dyn, dyn_bytes);
-        hipStream_t st = hb.stream;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (timing && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) e = XRSFM_BA_ENODEV;
-        if (!e && hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e && timing && hipMemsetAsync(base + o_phase, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
+    const size_t o_phase = L.take(4 * sizeof(unsigned long long));
+    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) hipEventDestroy(ev0); if (ev1) hipEventDestroy(ev1); } } tm;
+    unsigned long long ticks[4] = {0, 0, 0, 0};
+    return staged_call(L,
+        [&](unsigned char* stage) {
+            CamRec* cams = (CamRec*)(stage + o_cam);
+            for (int i = 0; i < Nc; ++i) cams[i] = cam_record(cam_q + 4 * (size_t)i, cam_t + 3 * (size_t)i, nullptr);
+            memcpy(stage + o_ptr, trk_ptr, sizeof(int) * ((size_t)Nt + 1));
+            if (No) { memcpy(stage + o_ocam, obs_cam, sizeof(int) * (size_t)No); memcpy(stage + o_oxy, obs_xy, sizeof(double) * 2 * (size_t)No); }
+            memcpy(stage + o_dyn, dyn, dyn_bytes);
+            return timing && (hipEventCreate(&tm.ev0) != hipSuccess || hipEventCreate(&tm.ev1) != hipSuccess) ? XRSFM_BA_ENODEV : 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
+            if (timing && hipMemsetAsync(base + o_phase, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return XRSFM_BA_ENODEV;
             if (Nc > 0) hipLaunchKernelGGL(k_cam_centres, dim3(cdiv(Nc, 256)), dim3(256), 0, st, (const CamRec*)(base + o_cam), Nc, (double*)(base + o_centre));
-            if (timing) hipEventRecord(ev0, st);
+            if (timing) hipEventRecord(tm.ev0, st);
             hipLaunchKernelGGL(k_tri_tracks, dim3(cdiv(Nt, kTriWaves)), dim3(kTriWave * kTriWaves), 0, st, (const CamRec*)(base + o_cam),
                                (const double*)(base + o_centre), (const int*)(base + o_ptr), (const int*)(base + o_ocam), (const double*)(base + o_oxy), Nt, prm,
                                (const int32_t*)(base + o_dyn), (double*)(base + o_pts), (unsigned char*)(base + o_stat), (unsigned char*)(base + o_mask),
                                (int*)(base + o_ninl), (int*)(base + o_ntr), (int*)(base + o_best),
                                timing ? (unsigned long long*)(base + o_phase) : (unsigned long long*)nullptr);
-            if (timing) hipEventRecord(ev1, st);
-            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
-        }
-        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        unsigned long long ticks[4] = {0, 0, 0, 0};
-        if (!e && timing && hipMemcpyAsync(ticks, base + o_phase, sizeof(ticks), hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (timing) {
+            if (timing) hipEventRecord(tm.ev1, st);
+            // (with the timing aid the ticks come back ahead of the outputs)
+            if (timing && hipMemcpyAsync(ticks, base + o_phase, sizeof(ticks), hipMemcpyDeviceToHost, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            return 0;
+        },
+        [&](const xstage::View& o) {
             float ms = 0.0f;
-            if (!e && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
+            if (timing && hipEventElapsedTime(&ms, tm.ev0, tm.ev1) == hipSuccess)
                 fprintf(stderr, "[xrsfm_ba] triangulate: kernel_ms %.4f ticks_a %llu ticks_b %llu ticks_c %llu ticks_d %llu\n", ms, ticks[0], ticks[1],
                         ticks[2], ticks[3]);
-            if (ev0) hipEventDestroy(ev0);
-            if (ev1) hipEventDestroy(ev1);
-        }
-        if (!e) {
-            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
-            const double* pts = (const double*)(o + o_pts);
-            const unsigned char* stat = o + o_stat;
+            const double* pts = o.at<double>(o_pts);
+            const unsigned char* stat = o.at<unsigned char>(o_stat);
             for (int j = 0; j < Nt; ++j) {
                 status[j] = stat[j];
                 if (stat[j] == 1) for (int k2 = 0; k2 < 3; ++k2) points[3 * (size_t)j + k2] = pts[3 * (size_t)j + k2];
             }
-            if (No) memcpy(inlier_mask, o + o_mask, (size_t)No);
-            if (num_inliers) memcpy(num_inliers, o + o_ninl, sizeof(int) * (size_t)Nt);
-            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Nt);
-            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Nt);
-        }
-    }
-    g_cache.put(0, base, cls);
-    g_bundles.put(0, hb);
-    return e;
+            if (No) memcpy(inlier_mask, o.at<unsigned char>(o_mask), (size_t)No);
+            if (num_inliers) memcpy(num_inliers, o.at<int>(o_ninl), sizeof(int) * (size_t)Nt);
+            if (num_trials) memcpy(num_trials, o.at<int>(o_ntr), sizeof(int) * (size_t)Nt);
+            if (best_trial) memcpy(best_trial, o.at<int>(o_best), sizeof(int) * (size_t)Nt);
+        });
 }
 
 int xrsfm_ba_triangulate_tracks(const xrsfm_ba_tri_options* opt, int32_t n_cams, const double* cam_q, const double* cam_t, int32_t n_tracks,
@@ -3688,117 +3716,90 @@ int xrsfm_ba_debug_pose_samples(uint32_t seed, int32_t n, int32_t n_trials, int3
 static int absolute_pose_impl(const xrsfm_ba_pose_options* opt, int32_t n_frames, const int32_t* corr_ptr, const double* xy, const double* points3d,
                               const double* frame_max_error, const uint32_t* frame_seed, double* q, double* t, uint8_t* status,
                               uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_absolute_pose: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_frames < 0) return bad("negative count");
-    if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio)) return bad("non-finite option");
-    if (opt->max_error <= 0.0) return bad("max_error <= 0");
-    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
-    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
-    if (opt->min_num_trials < 0) return bad("min_num_trials < 0");
-    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
-    if (opt->max_num_trials > XRSFM_BA_POSE_MAX_TRIALS) return bad("max_num_trials above XRSFM_BA_POSE_MAX_TRIALS");
-    if (opt->min_num_trials > opt->max_num_trials) return bad("min_num_trials > max_num_trials");
+    const char* who = "xrsfm_ba_absolute_pose";
+    if (!opt) return complain(who, "NULL options");
+    if (n_frames < 0) return complain(who, "negative count");
+    if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio)) return complain(who, "non-finite option");
+    if (opt->max_error <= 0.0) return complain(who, "max_error <= 0");
+    if (int e = check_confidence(who, opt->confidence)) return e;
+    if (int e = check_inlier_ratio(who, opt->min_inlier_ratio)) return e;
+    if (opt->min_num_trials < 0) return complain(who, "min_num_trials < 0");
+    if (opt->max_num_trials < 1) return complain(who, "max_num_trials < 1");
+    if (opt->max_num_trials > XRSFM_BA_POSE_MAX_TRIALS) return complain(who, "max_num_trials above XRSFM_BA_POSE_MAX_TRIALS");
+    if (opt->min_num_trials > opt->max_num_trials) return complain(who, "min_num_trials > max_num_trials");
     if (n_frames == 0) return XRSFM_BA_OK;
-    if (!q || !t || !status || !inlier_mask) return bad("NULL q, t, status or inlier_mask");
-    if (!corr_ptr) return bad("NULL corr_ptr");
-    if (corr_ptr[0] != 0) return bad("corr_ptr does not start at 0");
-    for (int j = 0; j < n_frames; ++j)
-        if (corr_ptr[j + 1] < corr_ptr[j]) return bad("corr_ptr decreases");
+    if (!q || !t || !status || !inlier_mask) return complain(who, "NULL q, t, status or inlier_mask");
+    if (!corr_ptr) return complain(who, "NULL corr_ptr");
+    if (int e = check_offsets(who, "corr_ptr", corr_ptr, n_frames)) return e;
     const int Nc = corr_ptr[n_frames], Nf = n_frames;
-    if (Nc > 0 && (!xy || !points3d)) return bad("NULL xy or points3d");
-    for (size_t i = 0; i < 2 * (size_t)Nc; ++i) if (!std::isfinite(xy[i])) return bad("non-finite coordinate");
-    for (size_t i = 0; i < 3 * (size_t)Nc; ++i) if (!std::isfinite(points3d[i])) return bad("non-finite coordinate");
+    if (Nc > 0 && (!xy || !points3d)) return complain(who, "NULL xy or points3d");
+    if (!all_finite(xy, 2 * (size_t)Nc) || !all_finite(points3d, 3 * (size_t)Nc)) return complain(who, "non-finite coordinate");
     if (frame_max_error)
         for (int j = 0; j < Nf; ++j) {
-            if (!std::isfinite(frame_max_error[j])) return bad("non-finite max_error");
-            if (frame_max_error[j] <= 0.0) return bad("max_error <= 0");
+            if (!std::isfinite(frame_max_error[j])) return complain(who, "non-finite max_error");
+            if (frame_max_error[j] <= 0.0) return complain(who, "max_error <= 0");
         }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the absolute pose has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (int e = require_device("absolute pose")) return e;
     PnpParams prm;
     prm.trial_cap = std::min(opt->max_num_trials, xpnp::pnp_ratio_trials(opt->min_inlier_ratio, opt->confidence));
     prm.min_trials = opt->min_num_trials;
     // per frame: the row dyn(k, n) (shared by the frames of one n) and the sample triples of the effective trial cap (deviation 1)
     std::vector<PnpFrame> frames((size_t)Nf);
-    std::vector<int32_t> dyn, triples, idx;
-    std::map<int, int> dyn_of;
+    std::vector<int32_t> triples, idx;
+    xstage::TrialRows dyn_rows;
     for (int j = 0; j < Nf; ++j) {
         PnpFrame& fr = frames[(size_t)j];
         fr.beg = corr_ptr[j]; fr.n = corr_ptr[j + 1] - corr_ptr[j];
         const double me = frame_max_error ? frame_max_error[j] : opt->max_error;
         fr.max_residual = me * me; fr.tri_off = -1; fr.dyn_off = 0;
         if (fr.n < 3 || fr.n > XRSFM_BA_POSE_MAX_CORR) continue;
-        auto it = dyn_of.find(fr.n);
-        if (it == dyn_of.end()) {
-            it = dyn_of.emplace(fr.n, (int)dyn.size()).first;
-            for (int k = 0; k <= fr.n; ++k) dyn.push_back(xpnp::pnp_dyn_trials(k, fr.n, opt->confidence));
-        }
-        fr.dyn_off = it->second;
+        fr.dyn_off = dyn_rows.offset_for(fr.n, [&](int n, int32_t* row) { for (int k = 0; k <= n; ++k) row[k] = xpnp::pnp_dyn_trials(k, n, opt->confidence); });
         fr.tri_off = (int32_t)(triples.size() / 3);
         triples.resize(triples.size() + 3 * (size_t)prm.trial_cap);
         idx.resize((size_t)fr.n);
         xpnp::pnp_sample_triples(frame_seed ? frame_seed[j] : opt->seed, fr.n, prm.trial_cap, idx.data(), triples.data() + 3 * (size_t)fr.tri_off);
     }
     HIPCHK(hipSetDevice(0));
-    // one block from the allocation cache, one upload, one launch, one read-back (the layout of triangulate_tracks_impl)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_fr = take(sizeof(PnpFrame) * (size_t)Nf), o_xy = take(sizeof(double) * 2 * (size_t)Nc), o_X = take(sizeof(double) * 3 * (size_t)Nc),
-                 o_tri = take(sizeof(int32_t) * triples.size()), o_dyn = take(sizeof(int32_t) * dyn.size());
-    const size_t in_bytes = off, out0 = off;
-    const size_t o_q = take(sizeof(double) * 4 * (size_t)Nf), o_t = take(sizeof(double) * 3 * (size_t)Nf), o_ninl = take(sizeof(int) * (size_t)Nf),
-                 o_ntr = take(sizeof(int) * (size_t)Nf), o_best = take(sizeof(int) * (size_t)Nf), o_stat = take((size_t)Nf), o_mask = take((size_t)Nc);
-    const size_t out_bytes = off - out0;
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls = 0;
-    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
-    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-    int e = 0;
-    {
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
-        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-        memcpy(stage.data() + o_fr, frames.data(), sizeof(PnpFrame) * (size_t)Nf);
-        if (Nc) { memcpy(stage.data() + o_xy, xy, sizeof(double) * 2 * (size_t)Nc); memcpy(stage.data() + o_X, points3d, sizeof(double) * 3 * (size_t)Nc); }
-        if (!triples.empty()) memcpy(stage.data() + o_tri, triples.data(), sizeof(int32_t) * triples.size());
-        if (!dyn.empty()) memcpy(stage.data() + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
-        hipStream_t st = hb.stream;
-        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
+    // one block, one upload, one launch, one read-back (staged_call)
+    const std::vector<int32_t>& dyn = dyn_rows.rows;
+    xstage::Layout L;
+    const size_t o_fr = L.take(sizeof(PnpFrame) * (size_t)Nf), o_xy = L.take(sizeof(double) * 2 * (size_t)Nc), o_X = L.take(sizeof(double) * 3 * (size_t)Nc),
+                 o_tri = L.take(sizeof(int32_t) * triples.size()), o_dyn = L.take(sizeof(int32_t) * dyn.size());
+    L.end_inputs();
+    L.begin_outputs();
+    const size_t o_q = L.take(sizeof(double) * 4 * (size_t)Nf), o_t = L.take(sizeof(double) * 3 * (size_t)Nf), o_ninl = L.take(sizeof(int) * (size_t)Nf),
+                 o_ntr = L.take(sizeof(int) * (size_t)Nf), o_best = L.take(sizeof(int) * (size_t)Nf), o_stat = L.take((size_t)Nf), o_mask = L.take((size_t)Nc);
+    L.end_outputs();
+    return staged_call(L,
+        [&](unsigned char* stage) {
+            memcpy(stage + o_fr, frames.data(), sizeof(PnpFrame) * (size_t)Nf);
+            if (Nc) { memcpy(stage + o_xy, xy, sizeof(double) * 2 * (size_t)Nc); memcpy(stage + o_X, points3d, sizeof(double) * 3 * (size_t)Nc); }
+            if (!triples.empty()) memcpy(stage + o_tri, triples.data(), sizeof(int32_t) * triples.size());
+            if (!dyn.empty()) memcpy(stage + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
             hipLaunchKernelGGL(k_pnp_frames, dim3(Nf), dim3(kPnpThreads), 0, st, (const PnpFrame*)(base + o_fr), Nf, prm, (const double*)(base + o_xy),
                                (const double*)(base + o_X), (const int32_t*)(base + o_tri), (const int32_t*)(base + o_dyn), (double*)(base + o_q),
                                (double*)(base + o_t), (unsigned char*)(base + o_stat), (unsigned char*)(base + o_mask), (int*)(base + o_ninl),
                                (int*)(base + o_ntr), (int*)(base + o_best));
-            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
-        }
-        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
-            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
-            const double* qs = (const double*)(o + o_q);
-            const double* ts = (const double*)(o + o_t);
-            const unsigned char* stat = o + o_stat;
+            return 0;
+        },
+        [&](const xstage::View& o) {
+            const double* qs = o.at<double>(o_q);
+            const double* ts = o.at<double>(o_t);
+            const unsigned char* stat = o.at<unsigned char>(o_stat);
             for (int j = 0; j < Nf; ++j) {
                 status[j] = stat[j];
                 if (stat[j] != 1) continue;
                 for (int k2 = 0; k2 < 4; ++k2) q[4 * (size_t)j + k2] = qs[4 * (size_t)j + k2];
                 for (int k2 = 0; k2 < 3; ++k2) t[3 * (size_t)j + k2] = ts[3 * (size_t)j + k2];
             }
-            if (Nc) memcpy(inlier_mask, o + o_mask, (size_t)Nc);
-            if (num_inliers) memcpy(num_inliers, o + o_ninl, sizeof(int) * (size_t)Nf);
-            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Nf);
-            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Nf);
-        }
-    }
-    g_cache.put(0, base, cls);
-    g_bundles.put(0, hb);
-    return e;
+            if (Nc) memcpy(inlier_mask, o.at<unsigned char>(o_mask), (size_t)Nc);
+            if (num_inliers) memcpy(num_inliers, o.at<int>(o_ninl), sizeof(int) * (size_t)Nf);
+            if (num_trials) memcpy(num_trials, o.at<int>(o_ntr), sizeof(int) * (size_t)Nf);
+            if (best_trial) memcpy(best_trial, o.at<int>(o_best), sizeof(int) * (size_t)Nf);
+        });
 }
 
 int xrsfm_ba_absolute_pose(const xrsfm_ba_pose_options* opt, int32_t n_frames, const int32_t* corr_ptr, const double* xy, const double* points3d,
@@ -3837,49 +3838,43 @@ int xrsfm_ba_debug_two_view_samples(uint32_t seed, int32_t n, int32_t n_trials, 
 static int two_view_init_impl(const xrsfm_ba_two_view_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
                               const double* pair_threshold, const uint32_t* pair_seed, uint8_t* status, double* E, double* q, double* t, double* points,
                               uint8_t* essential_mask, uint8_t* front_mask, int32_t* counts, uint8_t* accepted, int32_t* num_trials, int32_t* best_trial) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_two_view_init: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_pairs < 0) return bad("negative count");
+    const char* who = "xrsfm_ba_two_view_init";
+    if (!opt) return complain(who, "NULL options");
+    if (n_pairs < 0) return complain(who, "negative count");
     if (!std::isfinite(opt->confidence) || !std::isfinite(opt->max_depth) || !std::isfinite(opt->min_front_ratio) || !std::isfinite(opt->min_angle_ratio))
-        return bad("non-finite option");
-    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
-    if (opt->max_iterations < 1) return bad("max_iterations < 1");
-    if (opt->max_iterations > XRSFM_BA_INIT_MAX_TRIALS) return bad("max_iterations above XRSFM_BA_INIT_MAX_TRIALS");
-    if (opt->min_matches < 5) return bad("min_matches < 5");
-    if (opt->max_depth <= 0.0) return bad("max_depth <= 0");
-    if (opt->n_angles < 1 || opt->n_angles > 4) return bad("n_angles outside [1, 4]");
+        return complain(who, "non-finite option");
+    if (int e = check_confidence(who, opt->confidence)) return e;
+    if (opt->max_iterations < 1) return complain(who, "max_iterations < 1");
+    if (opt->max_iterations > XRSFM_BA_INIT_MAX_TRIALS) return complain(who, "max_iterations above XRSFM_BA_INIT_MAX_TRIALS");
+    if (opt->min_matches < 5) return complain(who, "min_matches < 5");
+    if (opt->max_depth <= 0.0) return complain(who, "max_depth <= 0");
+    if (opt->n_angles < 1 || opt->n_angles > 4) return complain(who, "n_angles outside [1, 4]");
     for (int a = 0; a < opt->n_angles; ++a) {
-        if (!std::isfinite(opt->min_angle_rad[a])) return bad("non-finite option");
-        if (opt->min_angle_rad[a] < 0.0) return bad("negative min_angle_rad");
+        if (!std::isfinite(opt->min_angle_rad[a])) return complain(who, "non-finite option");
+        if (opt->min_angle_rad[a] < 0.0) return complain(who, "negative min_angle_rad");
     }
-    if (opt->min_front_ratio < 0.0 || opt->min_angle_ratio < 0.0) return bad("negative min_front_ratio or min_angle_ratio");
-    if (opt->min_num_valid < 0) return bad("min_num_valid < 0");
+    if (opt->min_front_ratio < 0.0 || opt->min_angle_ratio < 0.0) return complain(who, "negative min_front_ratio or min_angle_ratio");
+    if (opt->min_num_valid < 0) return complain(who, "min_num_valid < 0");
     if (n_pairs == 0) return XRSFM_BA_OK;
-    if (!status || !E || !q || !t || !points || !essential_mask || !front_mask || !counts) return bad("NULL status, E, q, t, points, essential_mask, front_mask or counts");
-    if (!match_ptr || !pair_threshold) return bad("NULL match_ptr or pair_threshold");
-    if (match_ptr[0] != 0) return bad("match_ptr does not start at 0");
-    for (int j = 0; j < n_pairs; ++j)
-        if (match_ptr[j + 1] < match_ptr[j]) return bad("match_ptr decreases");
+    if (!status || !E || !q || !t || !points || !essential_mask || !front_mask || !counts) return complain(who, "NULL status, E, q, t, points, essential_mask, front_mask or counts");
+    if (!match_ptr || !pair_threshold) return complain(who, "NULL match_ptr or pair_threshold");
+    if (int e = check_offsets(who, "match_ptr", match_ptr, n_pairs)) return e;
     const int Nm = match_ptr[n_pairs], Np = n_pairs;
-    if (Nm > 0 && (!xy_a || !xy_b)) return bad("NULL xy_a or xy_b");
-    for (size_t i = 0; i < 2 * (size_t)Nm; ++i) if (!std::isfinite(xy_a[i]) || !std::isfinite(xy_b[i])) return bad("non-finite coordinate");
+    if (Nm > 0 && (!xy_a || !xy_b)) return complain(who, "NULL xy_a or xy_b");
+    if (!all_finite(xy_a, 2 * (size_t)Nm) || !all_finite(xy_b, 2 * (size_t)Nm)) return complain(who, "non-finite coordinate");
     for (int j = 0; j < Np; ++j) {
-        if (!std::isfinite(pair_threshold[j])) return bad("non-finite threshold");
-        if (pair_threshold[j] <= 0.0) return bad("threshold <= 0");
+        if (!std::isfinite(pair_threshold[j])) return complain(who, "non-finite threshold");
+        if (pair_threshold[j] <= 0.0) return complain(who, "threshold <= 0");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the two-view initialisation has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (int e = require_device("two-view initialisation")) return e;
     InitParams prm;
     prm.max_depth = opt->max_depth; prm.min_front_ratio = opt->min_front_ratio; prm.min_angle_ratio = opt->min_angle_ratio;
     for (int a = 0; a < 4; ++a) prm.min_angle[a] = a < opt->n_angles ? opt->min_angle_rad[a] : 0.0;
     prm.max_iterations = opt->max_iterations; prm.n_angles = opt->n_angles; prm.min_num_valid = opt->min_num_valid;
     // per pair: the row of the trial bound (shared by the pairs of one n) and the sample quintuples (deviation 1)
     std::vector<InitPair> pairs((size_t)Np);
-    std::vector<int32_t> rows, quint, idx;
-    std::map<int, int> row_of;
+    std::vector<int32_t> quint, idx;
+    xstage::TrialRows bound_rows;
     for (int j = 0; j < Np; ++j) {
         InitPair& pr = pairs[(size_t)j];
         pr.beg = match_ptr[j]; pr.n = match_ptr[j + 1] - match_ptr[j];
@@ -3887,13 +3882,7 @@ static int two_view_init_impl(const xrsfm_ba_two_view_options* opt, int32_t n_pa
         pr.quint_off = -1; pr.row_off = 0; pr.pad = 0;
         pr.skip_status = pr.n < opt->min_matches ? 2 : 3;
         if (pr.n < opt->min_matches || pr.n > XRSFM_BA_INIT_MAX_MATCHES) continue;
-        auto it = row_of.find(pr.n);
-        if (it == row_of.end()) {
-            it = row_of.emplace(pr.n, (int)rows.size()).first;
-            rows.resize(rows.size() + (size_t)pr.n + 1);
-            xinit::init_bound_row(pr.n, opt->confidence, rows.data() + it->second);
-        }
-        pr.row_off = it->second;
+        pr.row_off = bound_rows.offset_for(pr.n, [&](int n, int32_t* row) { xinit::init_bound_row(n, opt->confidence, row); });
         pr.quint_off = (int32_t)(quint.size() / 5);
         quint.resize(quint.size() + 5 * (size_t)prm.max_iterations);
         idx.resize((size_t)pr.n);
@@ -3902,50 +3891,37 @@ static int two_view_init_impl(const xrsfm_ba_two_view_options* opt, int32_t n_pa
     HIPCHK(hipSetDevice(0));
     static std::once_flag lds_once;
     std::call_once(lds_once, [] { (void)hipFuncSetAttribute((const void*)k_init_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InitShared)); });
-    // one block from the allocation cache, one upload, one launch, one read-back (the layout of absolute_pose_impl)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_pr = take(sizeof(InitPair) * (size_t)Np), o_m = take(sizeof(double) * 4 * (size_t)Nm), o_qt = take(sizeof(int32_t) * quint.size()),
-                 o_row = take(sizeof(int32_t) * rows.size());
-    const size_t in_bytes = off, out0 = off;
-    const size_t o_E = take(sizeof(double) * 9 * (size_t)Np), o_q = take(sizeof(double) * 4 * (size_t)Np), o_t = take(sizeof(double) * 3 * (size_t)Np),
-                 o_pts = take(sizeof(double) * 3 * (size_t)Nm), o_cnt = take(sizeof(int) * 8 * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
-                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_acc = take((size_t)Np), o_em = take((size_t)Nm), o_fm = take((size_t)Nm);
-    const size_t out_bytes = off - out0;
-    const size_t o_models = take(sizeof(double) * 9 * xinit::kMaxModels * xinit::kMaxTrials * (size_t)Np);       // device only
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls = 0;
-    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
-    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-    int e = 0;
-    {
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
-        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-        memcpy(stage.data() + o_pr, pairs.data(), sizeof(InitPair) * (size_t)Np);
-        double* mm = (double*)(stage.data() + o_m);
-        for (size_t i = 0; i < (size_t)Nm; ++i) { mm[4 * i] = xy_a[2 * i]; mm[4 * i + 1] = xy_a[2 * i + 1]; mm[4 * i + 2] = xy_b[2 * i]; mm[4 * i + 3] = xy_b[2 * i + 1]; }
-        if (!quint.empty()) memcpy(stage.data() + o_qt, quint.data(), sizeof(int32_t) * quint.size());
-        if (!rows.empty()) memcpy(stage.data() + o_row, rows.data(), sizeof(int32_t) * rows.size());
-        hipStream_t st = hb.stream;
-        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
+    // one block, one upload, one launch, one read-back (staged_call)
+    const std::vector<int32_t>& rows = bound_rows.rows;
+    xstage::Layout L;
+    const size_t o_pr = L.take(sizeof(InitPair) * (size_t)Np), o_m = L.take(sizeof(double) * 4 * (size_t)Nm), o_qt = L.take(sizeof(int32_t) * quint.size()),
+                 o_row = L.take(sizeof(int32_t) * rows.size());
+    L.end_inputs();
+    L.begin_outputs();
+    const size_t o_E = L.take(sizeof(double) * 9 * (size_t)Np), o_q = L.take(sizeof(double) * 4 * (size_t)Np), o_t = L.take(sizeof(double) * 3 * (size_t)Np),
+                 o_pts = L.take(sizeof(double) * 3 * (size_t)Nm), o_cnt = L.take(sizeof(int) * 8 * (size_t)Np), o_ntr = L.take(sizeof(int) * (size_t)Np),
+                 o_best = L.take(sizeof(int) * (size_t)Np), o_stat = L.take((size_t)Np), o_acc = L.take((size_t)Np), o_em = L.take((size_t)Nm), o_fm = L.take((size_t)Nm);
+    L.end_outputs();
+    const size_t o_models = L.take(sizeof(double) * 9 * xinit::kMaxModels * xinit::kMaxTrials * (size_t)Np);       // device only
+    return staged_call(L,
+        [&](unsigned char* stage) {
+            memcpy(stage + o_pr, pairs.data(), sizeof(InitPair) * (size_t)Np);
+            interleave_matches(xy_a, xy_b, (size_t)Nm, (double*)(stage + o_m));
+            if (!quint.empty()) memcpy(stage + o_qt, quint.data(), sizeof(int32_t) * quint.size());
+            if (!rows.empty()) memcpy(stage + o_row, rows.data(), sizeof(int32_t) * rows.size());
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
             hipLaunchKernelGGL(k_init_pairs, dim3(Np), dim3(kInitThreads), sizeof(InitShared), st, (const InitPair*)(base + o_pr), Np, prm,
                                (const double*)(base + o_m), (const int32_t*)(base + o_qt), (const int32_t*)(base + o_row), (double*)(base + o_models),
                                (unsigned char*)(base + o_stat), (double*)(base + o_E), (double*)(base + o_q), (double*)(base + o_t), (double*)(base + o_pts),
                                (unsigned char*)(base + o_em), (unsigned char*)(base + o_fm), (int*)(base + o_cnt), (unsigned char*)(base + o_acc),
                                (int*)(base + o_ntr), (int*)(base + o_best));
-            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
-        }
-        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
-            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
-            const double *Es = (const double*)(o + o_E), *qs = (const double*)(o + o_q), *ts = (const double*)(o + o_t), *ps = (const double*)(o + o_pts);
-            const unsigned char *stat = o + o_stat, *fm = o + o_fm;
-            const int* bt = (const int*)(o + o_best);
+            return 0;
+        },
+        [&](const xstage::View& o) {
+            const double *Es = o.at<double>(o_E), *qs = o.at<double>(o_q), *ts = o.at<double>(o_t), *ps = o.at<double>(o_pts);
+            const unsigned char *stat = o.at<unsigned char>(o_stat), *fm = o.at<unsigned char>(o_fm);
             for (int j = 0; j < Np; ++j) {
                 status[j] = stat[j];
                 bool have_E = false;                                    // (the kernel hands back zeros when there is no E)
@@ -3957,16 +3933,12 @@ static int two_view_init_impl(const xrsfm_ba_two_view_options* opt, int32_t n_pa
             }
             for (size_t i = 0; i < (size_t)Nm; ++i)
                 if (fm[i]) for (int k2 = 0; k2 < 3; ++k2) points[3 * i + k2] = ps[3 * i + k2];
-            if (Nm) { memcpy(essential_mask, o + o_em, (size_t)Nm); memcpy(front_mask, fm, (size_t)Nm); }
-            memcpy(counts, o + o_cnt, sizeof(int) * 8 * (size_t)Np);
-            if (accepted) memcpy(accepted, o + o_acc, (size_t)Np);
-            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Np);
-            if (best_trial) memcpy(best_trial, bt, sizeof(int) * (size_t)Np);
-        }
-    }
-    g_cache.put(0, base, cls);
-    g_bundles.put(0, hb);
-    return e;
+            if (Nm) { memcpy(essential_mask, o.at<unsigned char>(o_em), (size_t)Nm); memcpy(front_mask, fm, (size_t)Nm); }
+            memcpy(counts, o.at<int>(o_cnt), sizeof(int) * 8 * (size_t)Np);
+            if (accepted) memcpy(accepted, o.at<unsigned char>(o_acc), (size_t)Np);
+            if (num_trials) memcpy(num_trials, o.at<int>(o_ntr), sizeof(int) * (size_t)Np);
+            if (best_trial) memcpy(best_trial, o.at<int>(o_best), sizeof(int) * (size_t)Np);
+        });
 }
 
 int xrsfm_ba_two_view_init(const xrsfm_ba_two_view_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
@@ -4004,30 +3976,28 @@ int xrsfm_ba_debug_fund_samples(uint32_t seed, int32_t n, int32_t n_trials, int3
 // ---- the host steps that xrsfm_ba_verify_pairs and xrsfm_ba_frames_match share
 // the checks of the options and of the count; who: the entry's name
 static int fund_check_options(const char* who, const xrsfm_ba_fund_options* opt, int32_t n_pairs) {
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_pairs < 0) return bad("negative count");
+    if (!opt) return complain(who, "NULL options");
+    if (n_pairs < 0) return complain(who, "negative count");
     if (!std::isfinite(opt->max_error) || !std::isfinite(opt->confidence) || !std::isfinite(opt->min_inlier_ratio) || !std::isfinite(opt->min_accept_ratio))
-        return bad("non-finite option");
-    if (opt->max_error <= 0.0) return bad("max_error <= 0");
-    if (opt->confidence < 0.0 || opt->confidence > 1.0) return bad("confidence outside [0, 1]");
-    if (opt->min_inlier_ratio < 0.0 || opt->min_inlier_ratio > 1.0) return bad("min_inlier_ratio outside [0, 1]");
-    if (opt->min_num_trials < 0) return bad("min_num_trials < 0");
-    if (opt->max_num_trials < 1) return bad("max_num_trials < 1");
-    if (opt->max_num_trials > XRSFM_BA_FUND_MAX_TRIALS) return bad("max_num_trials above XRSFM_BA_FUND_MAX_TRIALS");
-    if (opt->min_num_trials > opt->max_num_trials) return bad("min_num_trials > max_num_trials");
-    if (opt->min_matches < xfund::kSample) return bad("min_matches < 7");
-    if (opt->min_num_inliers < 0) return bad("min_num_inliers < 0");
-    if (opt->min_accept_ratio < 0.0) return bad("min_accept_ratio < 0");
+        return complain(who, "non-finite option");
+    if (opt->max_error <= 0.0) return complain(who, "max_error <= 0");
+    if (int e = check_confidence(who, opt->confidence)) return e;
+    if (int e = check_inlier_ratio(who, opt->min_inlier_ratio)) return e;
+    if (opt->min_num_trials < 0) return complain(who, "min_num_trials < 0");
+    if (opt->max_num_trials < 1) return complain(who, "max_num_trials < 1");
+    if (opt->max_num_trials > XRSFM_BA_FUND_MAX_TRIALS) return complain(who, "max_num_trials above XRSFM_BA_FUND_MAX_TRIALS");
+    if (opt->min_num_trials > opt->max_num_trials) return complain(who, "min_num_trials > max_num_trials");
+    if (opt->min_matches < xfund::kSample) return complain(who, "min_matches < 7");
+    if (opt->min_num_inliers < 0) return complain(who, "min_num_inliers < 0");
+    if (opt->min_accept_ratio < 0.0) return complain(who, "min_accept_ratio < 0");
     return XRSFM_BA_OK;
 }
 
 static int fund_check_pair_errors(const char* who, int32_t n_pairs, const double* pair_max_error) {
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
     if (pair_max_error)
         for (int j = 0; j < n_pairs; ++j) {
-            if (!std::isfinite(pair_max_error[j])) return bad("non-finite max_error");
-            if (pair_max_error[j] <= 0.0) return bad("max_error <= 0");
+            if (!std::isfinite(pair_max_error[j])) return complain(who, "non-finite max_error");
+            if (pair_max_error[j] <= 0.0) return complain(who, "max_error <= 0");
         }
     return XRSFM_BA_OK;
 }
@@ -4039,11 +4009,8 @@ static FundParams fund_params(const xrsfm_ba_fund_options* opt) {
     return prm;
 }
 
-// the rows dyn(k, n) of one launch, shared by the pairs of one n
-struct FundDyn { std::vector<int32_t> rows; std::map<int, int> of; };
-
-// the record of the pair with matches beg .. beg + n; max_error, seed: the pair's own, or null
-static FundPair fund_pair_record(const xrsfm_ba_fund_options* opt, int32_t beg, int32_t n, const double* max_error, const uint32_t* seed, FundDyn& dyn) {
+// the record of the pair with matches beg .. beg + n; max_error, seed: the pair's own, or null; dyn: the rows dyn(k, n) of the launch
+static FundPair fund_pair_record(const xrsfm_ba_fund_options* opt, int32_t beg, int32_t n, const double* max_error, const uint32_t* seed, xstage::TrialRows& dyn) {
     FundPair pr;
     pr.beg = beg; pr.n = n;
     const double me = max_error ? *max_error : opt->max_error;
@@ -4051,12 +4018,7 @@ static FundPair fund_pair_record(const xrsfm_ba_fund_options* opt, int32_t beg, 
     pr.seed = seed ? *seed : opt->seed;
     pr.skip_status = pr.n < opt->min_matches ? 2 : (pr.n > XRSFM_BA_FUND_MAX_MATCHES ? 3 : 0);
     if (pr.skip_status) return pr;
-    auto it = dyn.of.find(pr.n);
-    if (it == dyn.of.end()) {
-        it = dyn.of.emplace(pr.n, (int)dyn.rows.size()).first;
-        for (int k = 0; k <= pr.n; ++k) dyn.rows.push_back(xfund::fund_dyn_trials(k, pr.n, opt->confidence));
-    }
-    pr.dyn_off = it->second;
+    pr.dyn_off = dyn.offset_for(pr.n, [&](int m, int32_t* row) { for (int k = 0; k <= m; ++k) row[k] = xfund::fund_dyn_trials(k, m, opt->confidence); });
     return pr;
 }
 
@@ -4077,82 +4039,58 @@ static int verify_pairs_impl(const xrsfm_ba_fund_options* opt, int32_t n_pairs, 
                              const double* pair_max_error, const uint32_t* pair_seed, uint8_t* status, double* F, uint8_t* inlier_mask,
                              int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, uint8_t* accepted) {
     const char* who = "xrsfm_ba_verify_pairs";
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
     if (int e = fund_check_options(who, opt, n_pairs)) return e;
     if (n_pairs == 0) return XRSFM_BA_OK;
-    if (!status || !F || !inlier_mask) return bad("NULL status, F or inlier_mask");
-    if (!match_ptr) return bad("NULL match_ptr");
-    if (match_ptr[0] != 0) return bad("match_ptr does not start at 0");
-    for (int j = 0; j < n_pairs; ++j)
-        if (match_ptr[j + 1] < match_ptr[j]) return bad("match_ptr decreases");
+    if (!status || !F || !inlier_mask) return complain(who, "NULL status, F or inlier_mask");
+    if (!match_ptr) return complain(who, "NULL match_ptr");
+    if (int e = check_offsets(who, "match_ptr", match_ptr, n_pairs)) return e;
     const int Nm = match_ptr[n_pairs], Np = n_pairs;
-    if (Nm > 0 && (!xy_a || !xy_b)) return bad("NULL xy_a or xy_b");
-    for (size_t i = 0; i < 2 * (size_t)Nm; ++i) if (!std::isfinite(xy_a[i]) || !std::isfinite(xy_b[i])) return bad("non-finite coordinate");
+    if (Nm > 0 && (!xy_a || !xy_b)) return complain(who, "NULL xy_a or xy_b");
+    if (!all_finite(xy_a, 2 * (size_t)Nm) || !all_finite(xy_b, 2 * (size_t)Nm)) return complain(who, "non-finite coordinate");
     if (int e = fund_check_pair_errors(who, Np, pair_max_error)) return e;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the pair verification has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
+    if (int e = require_device("pair verification")) return e;
     const FundParams prm = fund_params(opt);
     // per pair: the row dyn(k, n), shared by the pairs of one n; the septuples are drawn on the device
     std::vector<FundPair> pairs((size_t)Np);
-    FundDyn dyn_rows;
+    xstage::TrialRows dyn_rows;
     for (int j = 0; j < Np; ++j)
         pairs[(size_t)j] = fund_pair_record(opt, match_ptr[j], match_ptr[j + 1] - match_ptr[j], pair_max_error ? pair_max_error + j : nullptr,
                                             pair_seed ? pair_seed + j : nullptr, dyn_rows);
     const std::vector<int32_t>& dyn = dyn_rows.rows;
     HIPCHK(hipSetDevice(0));
     fund_kernel_setup();
-    // one block from the allocation cache, one upload, one launch, one read-back (the layout of absolute_pose_impl)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_pr = take(sizeof(FundPair) * (size_t)Np), o_m = take(sizeof(double) * 4 * (size_t)Nm), o_dyn = take(sizeof(int32_t) * dyn.size());
-    const size_t in_bytes = off, out0 = off;
-    const size_t o_F = take(sizeof(double) * 9 * (size_t)Np), o_ninl = take(sizeof(int) * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
-                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_mask = take((size_t)Nm);
-    const size_t out_bytes = off - out0;
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls = 0;
-    unsigned char* base = (unsigned char*)g_cache.get(0, off, &cls);
-    if (!base) { g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-    int e = 0;
-    {
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } stage, back;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap); back.p = (unsigned char*)g_pinned.get(out_bytes, &back.cap);
-        if (!stage.p || !back.p) { g_cache.put(0, base, cls); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
-        memcpy(stage.data() + o_pr, pairs.data(), sizeof(FundPair) * (size_t)Np);
-        double* mm = (double*)(stage.data() + o_m);
-        for (size_t i = 0; i < (size_t)Nm; ++i) { mm[4 * i] = xy_a[2 * i]; mm[4 * i + 1] = xy_a[2 * i + 1]; mm[4 * i + 2] = xy_b[2 * i]; mm[4 * i + 3] = xy_b[2 * i + 1]; }
-        if (!dyn.empty()) memcpy(stage.data() + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
-        hipStream_t st = hb.stream;
-        if (hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
+    // one block, one upload, one launch, one read-back (staged_call)
+    xstage::Layout L;
+    const size_t o_pr = L.take(sizeof(FundPair) * (size_t)Np), o_m = L.take(sizeof(double) * 4 * (size_t)Nm), o_dyn = L.take(sizeof(int32_t) * dyn.size());
+    L.end_inputs();
+    L.begin_outputs();
+    const size_t o_F = L.take(sizeof(double) * 9 * (size_t)Np), o_ninl = L.take(sizeof(int) * (size_t)Np), o_ntr = L.take(sizeof(int) * (size_t)Np),
+                 o_best = L.take(sizeof(int) * (size_t)Np), o_stat = L.take((size_t)Np), o_mask = L.take((size_t)Nm);
+    L.end_outputs();
+    return staged_call(L,
+        [&](unsigned char* stage) {
+            memcpy(stage + o_pr, pairs.data(), sizeof(FundPair) * (size_t)Np);
+            interleave_matches(xy_a, xy_b, (size_t)Nm, (double*)(stage + o_m));
+            if (!dyn.empty()) memcpy(stage + o_dyn, dyn.data(), sizeof(int32_t) * dyn.size());
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
             hipLaunchKernelGGL(k_verify_pairs, dim3(Np), dim3(kFundThreads), sizeof(FundShared), st, (const FundPair*)(base + o_pr), Np, prm,
                                (const double*)(base + o_m), (const int32_t*)(base + o_dyn), (double*)(base + o_F), (unsigned char*)(base + o_stat),
                                (unsigned char*)(base + o_mask), (int*)(base + o_ninl), (int*)(base + o_ntr), (int*)(base + o_best));
-            if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
-        }
-        if (!e && hipMemcpyAsync(back.data(), base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
-        if (!e) {
-            const unsigned char* o = back.data() - out0;            // (offsets above are relative to the block)
-            const double* Fs = (const double*)(o + o_F);
-            const unsigned char* stat = o + o_stat;
-            const int* ninl = (const int*)(o + o_ninl);
+            return 0;
+        },
+        [&](const xstage::View& o) {
+            const double* Fs = o.at<double>(o_F);
+            const unsigned char* stat = o.at<unsigned char>(o_stat);
+            const int* ninl = o.at<int>(o_ninl);
             for (int j = 0; j < Np; ++j)
                 fund_publish_pair(opt, stat[j], Fs + 9 * (size_t)j, ninl[j], pairs[(size_t)j].n, status + j, F + 9 * (size_t)j, accepted ? accepted + j : nullptr);
-            if (Nm) memcpy(inlier_mask, o + o_mask, (size_t)Nm);
+            if (Nm) memcpy(inlier_mask, o.at<unsigned char>(o_mask), (size_t)Nm);
             if (num_inliers) memcpy(num_inliers, ninl, sizeof(int) * (size_t)Np);
-            if (num_trials) memcpy(num_trials, o + o_ntr, sizeof(int) * (size_t)Np);
-            if (best_trial) memcpy(best_trial, o + o_best, sizeof(int) * (size_t)Np);
-        }
-    }
-    g_cache.put(0, base, cls);
-    g_bundles.put(0, hb);
-    return e;
+            if (num_trials) memcpy(num_trials, o.at<int>(o_ntr), sizeof(int) * (size_t)Np);
+            if (best_trial) memcpy(best_trial, o.at<int>(o_best), sizeof(int) * (size_t)Np);
+        });
 }
 
 int xrsfm_ba_verify_pairs(const xrsfm_ba_fund_options* opt, int32_t n_pairs, const int32_t* match_ptr, const double* xy_a, const double* xy_b,
@@ -4208,17 +4146,15 @@ struct MatchResult {                          // of the whole call, held back un
 // the workspace of one sub-batch: [pairs | items] uploaded, [counts | matches (| row and column triples: debug)] read back, the rest
 struct MatchLayout { size_t o_pr, o_it, in_bytes, o_cnt, o_m, o_rt, o_ct, back_bytes, o_cm, o_part, total; int64_t items; };
 MatchLayout match_layout(const xframes::BatchSize& s, bool debug) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     MatchLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    L.o_pr = take(sizeof(MatchPair) * (size_t)s.pairs); L.o_it = take(sizeof(MatchItem) * (size_t)s.items); L.in_bytes = off;
-    L.o_cnt = take(sizeof(int32_t) * 4 * (size_t)s.pairs); L.o_m = take(sizeof(int32_t) * 2 * (size_t)s.rows);
-    if (!debug) L.back_bytes = off - L.o_cnt;
-    L.o_rt = take(sizeof(int32_t) * 3 * (size_t)s.rows); L.o_ct = take(sizeof(int32_t) * 3 * (size_t)s.cols);
-    if (debug) L.back_bytes = off - L.o_cnt;
-    L.o_cm = take(sizeof(int32_t) * (size_t)s.cols); L.o_part = take(sizeof(int32_t) * 3 * (size_t)s.parts);
-    L.total = off; L.items = s.items;
+    xstage::Layout S;
+    L.o_pr = S.take(sizeof(MatchPair) * (size_t)s.pairs); L.o_it = S.take(sizeof(MatchItem) * (size_t)s.items); L.in_bytes = S.off;
+    L.o_cnt = S.take(sizeof(int32_t) * 4 * (size_t)s.pairs); L.o_m = S.take(sizeof(int32_t) * 2 * (size_t)s.rows);
+    if (!debug) L.back_bytes = S.off - L.o_cnt;
+    L.o_rt = S.take(sizeof(int32_t) * 3 * (size_t)s.rows); L.o_ct = S.take(sizeof(int32_t) * 3 * (size_t)s.cols);
+    if (debug) L.back_bytes = S.off - L.o_cnt;
+    L.o_cm = S.take(sizeof(int32_t) * (size_t)s.cols); L.o_part = S.take(sizeof(int32_t) * 3 * (size_t)s.parts);
+    L.total = S.off; L.items = s.items;
     return L;
 }
 
@@ -4308,22 +4244,21 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
     HIPCHK(hipSetDevice(0));
     const float* tab = match_table_device();
     if (!tab) return XRSFM_BA_ENOMEM;
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    size_t cls_d = 0, cls_w = 0;
-    unsigned char* dbase = (unsigned char*)g_cache.get(0, desc_bytes, &cls_d);
-    unsigned char* base = dbase ? (unsigned char*)g_cache.get(0, ws_bytes, &cls_w) : nullptr;
-    if (!base) { if (dbase) g_cache.put(0, dbase, cls_d); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+    StreamLease s(0);
+    if (!s.ok) return XRSFM_BA_ENODEV;
+    DevLease dblk, ws;
+    if (!dblk.get(0, desc_bytes) || !ws.get(0, ws_bytes)) return XRSFM_BA_ENOMEM;
+    unsigned char* const dbase = dblk.data();
+    unsigned char* const base = ws.data();
     int e = 0;
     {
-        struct Pin { unsigned char* p = nullptr; size_t cap = 0; unsigned char* data() const { return p; } ~Pin() { if (p) g_pinned.put(p, cap); } } dstage, stage, back;
-        dstage.p = (unsigned char*)g_pinned.get((size_t)D * xmatch::kDim, &dstage.cap);
-        stage.p = (unsigned char*)g_pinned.get(in_max, &stage.cap); back.p = (unsigned char*)g_pinned.get(back_max, &back.cap);
-        if (!dstage.p || !stage.p || !back.p) { g_cache.put(0, base, cls_w); g_cache.put(0, dbase, cls_d); g_bundles.put(0, hb); return XRSFM_BA_ENOMEM; }
+        PinLease dstage, stage, back;
+        const bool have_d = dstage.get((size_t)D * xmatch::kDim), have_s = stage.get(in_max), have_b = back.get(back_max);
+        if (!have_d || !have_s || !have_b) return XRSFM_BA_ENOMEM;
         for (int f = 0; f < n_frames; ++f)
             if (dev_off[(size_t)f] >= 0 && clip[(size_t)f] > 0)
                 memcpy(dstage.data() + (size_t)dev_off[(size_t)f] * xmatch::kDim, desc + (size_t)desc_ptr[f] * xmatch::kDim, (size_t)clip[(size_t)f] * xmatch::kDim);
-        hipStream_t st = hb.stream;
+        hipStream_t st = s.stream();
         // XRSFM_BA_MATCH_TIMING: the kernels' times from events on the stream, one line on stderr (tools/descriptor_match_timing.py)
         struct Events { hipEvent_t ev[5] = {}; bool on = false; ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); } } tm;
         if (getenv("XRSFM_BA_MATCH_TIMING")) { tm.on = true; for (hipEvent_t& x : tm.ev) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; tm.on = false; } }
@@ -4356,63 +4291,45 @@ int match_run(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t
                 if (hipEventElapsedTime(&a, tm.ev[2], tm.ev[3]) == hipSuccess) ms_dots += a;
                 if (hipEventElapsedTime(&a, tm.ev[3], tm.ev[4]) == hipSuccess) ms_select += a;
             }
-            const unsigned char* o = back.data() - L.o_cnt;          // (offsets above are relative to the block)
-            const int32_t* cnt = (const int32_t*)(o + L.o_cnt);
-            const int32_t* mm = (const int32_t*)(o + L.o_m);
-            if (!match_collect(cnt, mm, prs, np, live.data() + b.first, R)) e = XRSFM_BA_EINTERNAL;
+            const xstage::View o{back.data(), L.o_cnt};
+            if (!match_collect(o.at<int32_t>(L.o_cnt), o.at<int32_t>(L.o_m), prs, np, live.data() + b.first, R)) e = XRSFM_BA_EINTERNAL;
             if (debug && !e) {
-                R->row_top.assign((const int32_t*)(o + L.o_rt), (const int32_t*)(o + L.o_rt) + 3 * (size_t)prs[0].n_a);
-                R->col_top.assign((const int32_t*)(o + L.o_ct), (const int32_t*)(o + L.o_ct) + 3 * (size_t)prs[0].n_b);
+                R->row_top.assign(o.at<int32_t>(L.o_rt), o.at<int32_t>(L.o_rt) + 3 * (size_t)prs[0].n_a);
+                R->col_top.assign(o.at<int32_t>(L.o_ct), o.at<int32_t>(L.o_ct) + 3 * (size_t)prs[0].n_b);
             }
         }
         if (e) (void)hipStreamSynchronize(st);
         if (tm.on && !e) fprintf(stderr, "[xrsfm_ba] match timing: prep %.4f ms, dots %.4f ms, select %.4f ms, launches %zu\n", ms_prep, ms_dots, ms_select, batches.size());
     }
-    g_cache.put(0, base, cls_w);
-    g_cache.put(0, dbase, cls_d);
-    g_bundles.put(0, hb);
     return e;
 }
 
 // the checks of the options and of the counts; who: the entry's name
 int match_check_options(const char* who, const xrsfm_ba_match_options* opt, int32_t n_pairs, int32_t n_frames, int64_t matches_capacity) {
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_pairs < 0 || n_frames < 0 || matches_capacity < 0) return bad("negative count");
-    if (!std::isfinite(opt->max_distance) || !std::isfinite(opt->max_ratio)) return bad("non-finite option");
-    if (opt->max_distance <= 0.0f) return bad("max_distance <= 0");
-    if (!(opt->max_ratio > 0.0f && opt->max_ratio <= 1.0f)) return bad("max_ratio outside (0, 1]");
-    if (opt->max_features < 1 || opt->max_features > XRSFM_BA_MATCH_MAX_FEATURES) return bad("max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES");
+    if (!opt) return complain(who, "NULL options");
+    if (n_pairs < 0 || n_frames < 0 || matches_capacity < 0) return complain(who, "negative count");
+    if (!std::isfinite(opt->max_distance) || !std::isfinite(opt->max_ratio)) return complain(who, "non-finite option");
+    if (opt->max_distance <= 0.0f) return complain(who, "max_distance <= 0");
+    if (!(opt->max_ratio > 0.0f && opt->max_ratio <= 1.0f)) return complain(who, "max_ratio outside (0, 1]");
+    if (opt->max_features < 1 || opt->max_features > XRSFM_BA_MATCH_MAX_FEATURES) return complain(who, "max_features outside 1 .. XRSFM_BA_MATCH_MAX_FEATURES");
     return XRSFM_BA_OK;
-}
-
-int match_no_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the descriptor matching has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
-    return 0;
 }
 
 int match_descriptors_impl(const xrsfm_ba_match_options* opt, int32_t n_frames, const int64_t* desc_ptr, const uint8_t* desc, int32_t n_pairs,
                            const int32_t* pair_a, const int32_t* pair_b, int64_t matches_capacity, int64_t* match_ptr, int32_t* matches,
                            int32_t* num_row, int32_t* num_col) {
     const char* who = "xrsfm_ba_match_descriptors";
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
     if (int e = match_check_options(who, opt, n_pairs, n_frames, matches_capacity)) return e;
     if (n_pairs == 0) return XRSFM_BA_OK;
-    if (!match_ptr) return bad("NULL match_ptr");
-    if (!pair_a || !pair_b) return bad("NULL pair_a or pair_b");
-    if (!desc_ptr) return bad("NULL desc_ptr");
-    if (desc_ptr[0] != 0) return bad("desc_ptr does not start at 0");
-    for (int f = 0; f < n_frames; ++f)
-        if (desc_ptr[f + 1] < desc_ptr[f]) return bad("desc_ptr decreases");
-    if (desc_ptr[n_frames] > 0 && !desc) return bad("NULL desc");
+    if (!match_ptr) return complain(who, "NULL match_ptr");
+    if (!pair_a || !pair_b) return complain(who, "NULL pair_a or pair_b");
+    if (!desc_ptr) return complain(who, "NULL desc_ptr");
+    if (int e = check_offsets(who, "desc_ptr", desc_ptr, n_frames)) return e;
+    if (desc_ptr[n_frames] > 0 && !desc) return complain(who, "NULL desc");
     for (int p = 0; p < n_pairs; ++p)
-        if (pair_a[p] < 0 || pair_a[p] >= n_frames || pair_b[p] < 0 || pair_b[p] >= n_frames) return bad("frame index out of range");
-    if (matches_capacity > 0 && !matches) return bad("NULL matches");
-    if (int e = match_no_device()) return e;
+        if (pair_a[p] < 0 || pair_a[p] >= n_frames || pair_b[p] < 0 || pair_b[p] >= n_frames) return complain(who, "frame index out of range");
+    if (matches_capacity > 0 && !matches) return complain(who, "NULL matches");
+    if (int e = require_device("descriptor matching")) return e;
     std::vector<int32_t> clip((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) clip[(size_t)f] = (int32_t)std::min<int64_t>(desc_ptr[f + 1] - desc_ptr[f], opt->max_features);
     MatchResult R;
@@ -4437,7 +4354,7 @@ int match_descriptors_impl(const xrsfm_ba_match_options* opt, int32_t n_frames, 
 int debug_match_top2_impl(int32_t n_a, const uint8_t* desc_a, int32_t n_b, const uint8_t* desc_b, int32_t* row_top, int32_t* col_top) {
     if (n_a < 0 || n_b < 0 || n_a > XRSFM_BA_MATCH_MAX_FEATURES || n_b > XRSFM_BA_MATCH_MAX_FEATURES) return XRSFM_BA_EINVAL;
     if ((n_a > 0 && (!desc_a || !row_top)) || (n_b > 0 && (!desc_b || !col_top))) return XRSFM_BA_EINVAL;
-    if (int e = match_no_device()) return e;
+    if (int e = require_device("descriptor matching")) return e;
     MatchResult R;
     if (n_a > 0 && n_b > 0) {
         xrsfm_ba_match_options opt;
@@ -4507,13 +4424,11 @@ struct SiftResult {                           // of the whole call, held back un
 // kernel's term; for a set made from images also loc, sign and the float w of the orientation.
 struct FramesLayout { size_t o_keys, o_desc, o_prep, o_loc, o_sign, o_w, total; };
 FramesLayout frames_layout(int64_t n, bool image_fields) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     FramesLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    L.o_keys = take(16 * (size_t)n); L.o_desc = take(128 * (size_t)n); L.o_prep = take(4 * (size_t)n);
-    if (image_fields) { L.o_loc = take(16 * (size_t)n); L.o_sign = take((size_t)n); L.o_w = take(4 * (size_t)n); }
-    L.total = off;
+    xstage::Layout S;
+    L.o_keys = S.take(16 * (size_t)n); L.o_desc = S.take(128 * (size_t)n); L.o_prep = S.take(4 * (size_t)n);
+    if (image_fields) { L.o_loc = S.take(16 * (size_t)n); L.o_sign = S.take((size_t)n); L.o_w = S.take(4 * (size_t)n); }
+    L.total = S.off;
     return L;
 }
 struct FramesBlock {
@@ -4564,9 +4479,9 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         chunks.push_back({first, n_images});
     }
     HIPCHK(hipSetDevice(0));
-    HostBundle hb;
-    if (!g_bundles.get(0, &hb)) return XRSFM_BA_ENODEV;
-    hipStream_t st = hb.stream;
+    StreamLease lease(0);
+    if (!lease.ok) return XRSFM_BA_ENODEV;
+    hipStream_t st = lease.stream();
     // XRSFM_BA_SIFT_TIMING: the kernels' times from events on the stream, one line on stderr (tools/keypoint_timing.py)
     struct Span { hipEvent_t a, b; int what; };
     struct Events { std::vector<Span> ev; bool on = false; ~Events() { for (const Span& x : ev) { (void)hipEventDestroy(x.a); (void)hipEventDestroy(x.b); } } } tm;
@@ -4574,8 +4489,6 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
     enum { kTBase, kTInit, kTFilter0, kTDown = kTFilter0 + xsift::kDog, kTCount, kTEmit, kTGrad, kTRecord, kTOrient, kTDesc, kTOrder, kTN };
     double ms[kTN] = {};
     int e = 0;
-    struct Dev { void* p = nullptr; size_t cls = 0; ~Dev() { if (p) g_cache.put(0, p, cls); } };
-    struct Pin { unsigned char* p = nullptr; size_t cap = 0; ~Pin() { if (p) g_pinned.put(p, cap); } };
     for (size_t ci = 0; ci < chunks.size() && !e; ++ci) {
         const int i0 = chunks[ci].first, ni = chunks[ci].second - chunks[ci].first;
         // layout of the chunk: [imgs | tiles | taps] uploaded, [tile slots] both ways, pixels, planes
@@ -4613,14 +4526,11 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         const size_t o_slot = in_bytes, o_pix = o_slot + 3 * slot_bytes, o_planes = o_pix + al((size_t)pix);
         const size_t o_grad = o_planes + al((size_t)fl * sizeof(float));
         const size_t total = o_grad + (size_t)gr * sizeof(float2);
-        Dev ws;
-        ws.p = g_cache.get(0, total, &ws.cls);
-        Pin stage, pstage, slots;
-        stage.p = (unsigned char*)g_pinned.get(in_bytes, &stage.cap);
-        pstage.p = (unsigned char*)g_pinned.get((size_t)pix ? (size_t)pix : 8, &pstage.cap);
-        slots.p = (unsigned char*)g_pinned.get(3 * slot_bytes, &slots.cap);
+        DevLease ws;
+        PinLease stage, pstage, slots;
+        ws.get(0, total); stage.get(in_bytes); pstage.get((size_t)pix); slots.get(3 * slot_bytes);
         if (!ws.p || !stage.p || !pstage.p || !slots.p) { e = XRSFM_BA_ENOMEM; break; }
-        unsigned char* base = (unsigned char*)ws.p;
+        unsigned char* base = ws.p;
         memcpy(stage.p + o_img, imgs.data(), sizeof(SiftImg) * (size_t)ni);
         memcpy(stage.p + o_tile, tiles.data(), sizeof(SiftTile) * tiles.size());
         for (int i = 0; i <= xsift::kDog; ++i) memcpy(stage.p + o_taps + sizeof(float) * xsift::kMaxTaps * (size_t)i, taps[i].w, sizeof(float) * xsift::kMaxTaps);
@@ -4710,12 +4620,12 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         }
         if (n_keys > 0) {
             const size_t k_keys = 0, k_loc = al(16 * (size_t)n_keys), k_off = k_loc + al(16 * (size_t)n_keys), k_total = k_off + al(16 * (size_t)n_keys);
-            Dev kd;
-            kd.p = g_cache.get(0, k_total, &kd.cls);
-            Pin back;
-            if (!sink) back.p = (unsigned char*)g_pinned.get(k_total, &back.cap);
+            DevLease kd;
+            PinLease back;
+            kd.get(0, k_total);
+            if (!sink) back.get(k_total);
             if (!kd.p || (!sink && !back.p)) { e = XRSFM_BA_ENOMEM; break; }
-            unsigned char* kb = (unsigned char*)kd.p;
+            unsigned char* kb = kd.p;
             if (hipMemcpyAsync(d_first, sl_first, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice, st) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
             for (int o = 0; o < oct_most && !e; ++o) {
                 const unsigned nt = (unsigned)(tile_first[o + 1] - tile_first[o]);
@@ -4737,8 +4647,8 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
             if (e) break;
             // the second half on the keypoints of the chunk, while its planes are resident: gradient planes of the levels that keep a
             // keypoint, one record per keypoint, orientation, descriptor; then ONE read-back of keys, bytes and the optional floats
-            Dev dd;
-            Pin dback, dstage;
+            DevLease dd;
+            PinLease dback, dstage;
             const size_t nk = (size_t)n_keys;
             const size_t d_okey = 0, d_desc = al(16 * nk), d_float = d_desc + al(128 * nk), d_raw = d_float + (dq && dq->floats ? al(512 * nk) : 0),
                          d_unit = d_raw + (dq && dq->stages ? al(512 * nk) : 0), d_out = d_unit + (dq && dq->stages ? al(512 * nk) : 0), d_rec = d_out;
@@ -4759,11 +4669,11 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                 const size_t u_dimg = 0, u_need = al(sizeof(SiftdImg) * (size_t)ni), u_lev = u_need + al(sizeof(int32_t) * need.size()),
                              u_total = u_lev + al(sizeof(SiftdLevel) * levels.size());
                 const size_t d_up = d_rec + al(sizeof(SiftdRec) * nk);
-                dd.p = g_cache.get(0, d_up + u_total, &dd.cls);
-                if (!sink) dback.p = (unsigned char*)g_pinned.get(d_out, &dback.cap);
-                dstage.p = (unsigned char*)g_pinned.get(u_total, &dstage.cap);
+                dd.get(0, d_up + u_total);
+                if (!sink) dback.get(d_out);
+                dstage.get(u_total);
                 if (!dd.p || (!sink && !dback.p) || !dstage.p) { e = XRSFM_BA_ENOMEM; break; }
-                unsigned char* db = (unsigned char*)dd.p;
+                unsigned char* db = dd.p;
                 memcpy(dstage.p + u_dimg, dimgs.data(), sizeof(SiftdImg) * (size_t)ni);
                 memcpy(dstage.p + u_need, need.data(), sizeof(int32_t) * need.size());
                 memcpy(dstage.p + u_lev, levels.data(), sizeof(SiftdLevel) * levels.size());
@@ -4803,17 +4713,16 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
                     FramesBlock blk;
                     blk.n = n_keys; blk.L = frames_layout(n_keys, true);
                     blk.p = g_cache.get(0, blk.L.total, &blk.cls);
-                    Dev od;
-                    Pin ostage;
+                    DevLease od;
+                    PinLease ostage;
                     const size_t s_item = al(sizeof(FramesSeg) * segs.size()), s_total = s_item + al(sizeof(FramesOrderItem) * items.size());
-                    od.p = g_cache.get(0, s_total, &od.cls);
-                    ostage.p = (unsigned char*)g_pinned.get(s_total, &ostage.cap);
+                    od.get(0, s_total); ostage.get(s_total);
                     if (!blk.p || !od.p || !ostage.p) { blk.release(); e = XRSFM_BA_ENOMEM; break; }
                     memcpy(ostage.p, segs.data(), sizeof(FramesSeg) * segs.size());
                     memcpy(ostage.p + s_item, items.data(), sizeof(FramesOrderItem) * items.size());
                     if (hipMemcpyAsync(od.p, ostage.p, s_total, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
                     if (!e) timed(kTOrder, [&] { hipLaunchKernelGGL(k_frames_order, dim3((unsigned)items.size()), dim3(kFramesThreads), 0, st,
-                                                                    (const FramesOrderItem*)((unsigned char*)od.p + s_item), (const FramesSeg*)od.p, (const float4*)(kb + k_keys),
+                                                                    (const FramesOrderItem*)(od.p + s_item), (const FramesSeg*)od.p, (const float4*)(kb + k_keys),
                                                                     (const int4*)(kb + k_loc), (const float4*)(kb + k_off), (const float4*)(db + d_okey), (const uint8_t*)(db + d_desc),
                                                                     (float4*)blk.at(blk.L.o_keys), (int4*)blk.at(blk.L.o_loc), (int8_t*)blk.at(blk.L.o_sign), (float*)blk.at(blk.L.o_w),
                                                                     (uint8_t*)blk.at(blk.L.o_desc)); });
@@ -4865,11 +4774,10 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
             if (want->grad) {                                   // all three planes of the octave, whether a keypoint needs them or not
                 const int oc = want->octave;
                 std::vector<int32_t> all((size_t)ni * NL, 1);
-                Dev gd;
+                DevLease gd;
                 const size_t g_need = al(sizeof(SiftdImg) * (size_t)ni), g_total = g_need + al(sizeof(int32_t) * all.size());
-                gd.p = g_cache.get(0, g_total, &gd.cls);
-                if (!gd.p) { e = XRSFM_BA_ENOMEM; break; }
-                unsigned char* gb = (unsigned char*)gd.p;
+                if (!gd.get(0, g_total)) { e = XRSFM_BA_ENOMEM; break; }
+                unsigned char* gb = gd.p;
                 if (hipMemcpy(gb, dimgs.data(), sizeof(SiftdImg) * (size_t)ni, hipMemcpyHostToDevice) != hipSuccess ||
                     hipMemcpy(gb + g_need, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice) != hipSuccess) { e = XRSFM_BA_ENODEV; break; }
                 const unsigned nt = (unsigned)(tile_first[oc + 1] - tile_first[oc]);
@@ -4893,39 +4801,28 @@ int sift_run(const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* 
         if (dq) fprintf(stderr, "[xrsfm_ba] sift descriptor timing: grad %.4f ms, record %.4f ms, orient %.4f ms, desc %.4f ms\n", ms[kTGrad], ms[kTRecord], ms[kTOrient], ms[kTDesc]);
         if (sink) fprintf(stderr, "[xrsfm_ba] frames timing: order %.4f ms\n", ms[kTOrder]);
     }
-    g_bundles.put(0, hb);
     return e;
-}
-
-int sift_no_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[xrsfm_ba] no HIP device visible: the keypoint detection has no CPU fallback\n");
-        return XRSFM_BA_ENODEV;
-    }
-    return 0;
 }
 
 // the checks of the options and of the images; what: the entry's name
 int sift_check(const char* who, const xrsfm_ba_sift_options* opt, int32_t n_images, const int32_t* width, const int32_t* height, const int64_t* pixel_ptr,
                const uint8_t* pixels) {
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (!opt) return bad("NULL options");
-    if (n_images < 0) return bad("negative count");
-    if (opt->first_octave != -1 && opt->first_octave != 0) return bad("first_octave outside {-1, 0}");
-    if (opt->num_octaves < 1 || opt->num_octaves > XRSFM_BA_SIFT_MAX_OCTAVES) return bad("num_octaves outside 1 .. 8");
-    if (!std::isfinite(opt->peak_threshold) || !std::isfinite(opt->edge_threshold)) return bad("non-finite threshold");
-    if (opt->peak_threshold <= 0.0f || opt->edge_threshold <= 0.0f) return bad("non-positive threshold");
-    if (opt->max_num_features < 1) return bad("max_num_features < 1");
-    if (opt->max_image_size < 1) return bad("max_image_size < 1");
+    if (!opt) return complain(who, "NULL options");
+    if (n_images < 0) return complain(who, "negative count");
+    if (opt->first_octave != -1 && opt->first_octave != 0) return complain(who, "first_octave outside {-1, 0}");
+    if (opt->num_octaves < 1 || opt->num_octaves > XRSFM_BA_SIFT_MAX_OCTAVES) return complain(who, "num_octaves outside 1 .. 8");
+    if (!std::isfinite(opt->peak_threshold) || !std::isfinite(opt->edge_threshold)) return complain(who, "non-finite threshold");
+    if (opt->peak_threshold <= 0.0f || opt->edge_threshold <= 0.0f) return complain(who, "non-positive threshold");
+    if (opt->max_num_features < 1) return complain(who, "max_num_features < 1");
+    if (opt->max_image_size < 1) return complain(who, "max_image_size < 1");
     if (n_images == 0) return XRSFM_BA_OK;
-    if (!width || !height || !pixel_ptr || !pixels) return bad("NULL width, height, pixel_ptr or pixels");
-    if (pixel_ptr[0] != 0) return bad("pixel_ptr does not start at 0");
+    if (!width || !height || !pixel_ptr || !pixels) return complain(who, "NULL width, height, pixel_ptr or pixels");
+    if (pixel_ptr[0] != 0) return complain(who, "pixel_ptr does not start at 0");
     for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 0 || height[i] < 0) return bad("negative image size");
-        if (xsift::truncate_width(width[i]) < xsift::kMinSide || height[i] < xsift::kMinSide) return bad("a truncated width or a height below 16");
-        if (width[i] > opt->max_image_size || height[i] > opt->max_image_size) return bad("an image side above max_image_size (down-sampling of the input is not built)");
-        if (pixel_ptr[i + 1] - pixel_ptr[i] != (int64_t)width[i] * height[i]) return bad("pixel_ptr disagrees with width * height");
+        if (width[i] < 0 || height[i] < 0) return complain(who, "negative image size");
+        if (xsift::truncate_width(width[i]) < xsift::kMinSide || height[i] < xsift::kMinSide) return complain(who, "a truncated width or a height below 16");
+        if (width[i] > opt->max_image_size || height[i] > opt->max_image_size) return complain(who, "an image side above max_image_size (down-sampling of the input is not built)");
+        if (pixel_ptr[i + 1] - pixel_ptr[i] != (int64_t)width[i] * height[i]) return complain(who, "pixel_ptr disagrees with width * height");
     }
     return XRSFM_BA_OK;
 }
@@ -4934,16 +4831,15 @@ int sift_check(const char* who, const xrsfm_ba_sift_options* opt, int32_t n_imag
 int sift_features_impl(const char* who, bool with_desc, const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width,
                        const int32_t* height, const int64_t* pixel_ptr, const uint8_t* pixels, int64_t capacity, int64_t* key_ptr, float* keys, int32_t* loc, int8_t* sign,
                        uint8_t* desc, float* desc_float, int32_t* level_count) {
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (opt && capacity < 0) return bad("negative count");
-    if (opt && with_desc && !dopt) return bad("NULL descriptor options");
-    if (opt && with_desc && dopt->upright != 0 && dopt->upright != 1) return bad("upright outside {0, 1}");
+    if (opt && capacity < 0) return complain(who, "negative count");
+    if (opt && with_desc && !dopt) return complain(who, "NULL descriptor options");
+    if (opt && with_desc && dopt->upright != 0 && dopt->upright != 1) return complain(who, "upright outside {0, 1}");
     if (int e = sift_check(who, opt, n_images, width, height, pixel_ptr, pixels)) return e;
     if (n_images == 0) return XRSFM_BA_OK;
-    if (!key_ptr) return bad("NULL key_ptr");
-    if (capacity > 0 && (!keys || !loc || !sign)) return bad("NULL keys, loc or sign");
-    if (capacity > 0 && with_desc && !desc) return bad("NULL desc");
-    if (int e = sift_no_device()) return e;
+    if (!key_ptr) return complain(who, "NULL key_ptr");
+    if (capacity > 0 && (!keys || !loc || !sign)) return complain(who, "NULL keys, loc or sign");
+    if (capacity > 0 && with_desc && !desc) return complain(who, "NULL desc");
+    if (int e = require_device("keypoint detection")) return e;
     SiftResult R;
     const SiftDescRequest dq{with_desc ? (int)dopt->upright : 0, desc_float != nullptr, false};
     if (int e = sift_run(opt, n_images, width, height, pixel_ptr, pixels, nullptr, &R, with_desc ? &dq : nullptr)) return e;
@@ -4972,7 +4868,7 @@ int debug_sift_gradient_impl(const xrsfm_ba_sift_options* opt, int32_t width, in
     const int64_t ptr[2] = {0, (int64_t)width * height};
     if (int e = sift_check("xrsfm_ba_debug_sift_gradient", opt, 1, &width, &height, ptr, pixels)) return e;
     if (!grad || octave < 0 || octave >= xsift::geometry(width, height, opt->first_octave, opt->num_octaves).n_oct) return XRSFM_BA_EINVAL;
-    if (int e = sift_no_device()) return e;
+    if (int e = require_device("keypoint detection")) return e;
     const SiftLevelsRequest want{0, octave, nullptr, nullptr, grad};
     SiftResult R;
     return sift_run(opt, 1, &width, &height, ptr, pixels, &want, &R);
@@ -4984,7 +4880,7 @@ int debug_sift_describe_impl(const xrsfm_ba_sift_options* opt, const xrsfm_ba_si
     if (int e = sift_check("xrsfm_ba_debug_sift_describe", opt, 1, &width, &height, ptr, pixels)) return e;
     if (!dopt || (dopt->upright != 0 && dopt->upright != 1)) return XRSFM_BA_EINVAL;
     if (!n_keys || capacity < 0 || (capacity > 0 && (!loc || !okeys || !raw || !unit))) return XRSFM_BA_EINVAL;
-    if (int e = sift_no_device()) return e;
+    if (int e = require_device("keypoint detection")) return e;
     SiftResult R;
     const SiftDescRequest dq{(int)dopt->upright, false, true};
     if (int e = sift_run(opt, 1, &width, &height, ptr, pixels, nullptr, &R, &dq)) return e;
@@ -5004,7 +4900,7 @@ int debug_sift_levels_impl(const xrsfm_ba_sift_options* opt, int32_t width, int3
     const int64_t ptr[2] = {0, (int64_t)width * height};
     if (int e = sift_check("xrsfm_ba_debug_sift_levels", opt, 1, &width, &height, ptr, pixels)) return e;
     if (!gauss || !dog || octave < 0 || octave >= xsift::geometry(width, height, opt->first_octave, opt->num_octaves).n_oct) return XRSFM_BA_EINVAL;
-    if (int e = sift_no_device()) return e;
+    if (int e = require_device("keypoint detection")) return e;
     const SiftLevelsRequest want{0, octave, gauss, dog};
     SiftResult R;
     return sift_run(opt, 1, &width, &height, ptr, pixels, &want, &R);
@@ -5015,7 +4911,7 @@ int debug_sift_offsets_impl(const xrsfm_ba_sift_options* opt, int32_t width, int
     const int64_t ptr[2] = {0, (int64_t)width * height};
     if (int e = sift_check("xrsfm_ba_debug_sift_offsets", opt, 1, &width, &height, ptr, pixels)) return e;
     if (!n_keys || capacity < 0 || (capacity > 0 && (!loc || !offsets))) return XRSFM_BA_EINVAL;
-    if (int e = sift_no_device()) return e;
+    if (int e = require_device("keypoint detection")) return e;
     SiftResult R;
     if (int e = sift_run(opt, 1, &width, &height, ptr, pixels, nullptr, &R)) return e;
     *n_keys = R.count[0];
@@ -5075,10 +4971,6 @@ struct xrsfm_ba_frames {
 };
 
 namespace {
-struct FramesPin { unsigned char* p = nullptr; size_t cap = 0; ~FramesPin() { if (p) g_pinned.put(p, cap); } bool get(size_t bytes) { p = (unsigned char*)g_pinned.get(bytes ? bytes : 8, &cap); return p != nullptr; } };
-struct FramesDev { void* p = nullptr; size_t cls = 0; ~FramesDev() { if (p) g_cache.put(0, p, cls); } bool get(size_t bytes) { p = g_cache.get(0, bytes, &cls); return p != nullptr; } };
-struct FramesStream { HostBundle hb; bool ok; FramesStream() { ok = g_bundles.get(0, &hb); } ~FramesStream() { if (ok) g_bundles.put(0, hb); } };
-
 int frames_no_device() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -5097,40 +4989,38 @@ int frames_prep(hipStream_t st, const FramesBlock& b) {
 }
 
 int frames_create_impl(int32_t n_frames, const int64_t* key_ptr, const float* keys, const uint8_t* desc, xrsfm_ba_frames** out) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_create: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!out) return bad("NULL out");
-    if (n_frames < 0) return bad("negative count");
-    if (n_frames > 0 && !key_ptr) return bad("NULL key_ptr");
-    if (n_frames > 0 && key_ptr[0] != 0) return bad("key_ptr does not start at 0");
-    for (int f = 0; f < n_frames; ++f)
-        if (key_ptr[f + 1] < key_ptr[f]) return bad("key_ptr decreases");
+    const char* who = "xrsfm_ba_frames_create";
+    if (!out) return complain(who, "NULL out");
+    if (n_frames < 0) return complain(who, "negative count");
+    if (n_frames > 0 && !key_ptr) return complain(who, "NULL key_ptr");
+    if (n_frames > 0) if (int e = check_offsets(who, "key_ptr", key_ptr, n_frames)) return e;
     for (int f = 0; f < n_frames; ++f)
         if (key_ptr[f + 1] - key_ptr[f] > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_create: a frame above INT32_MAX key points\n"); return XRSFM_BA_ETOOBIG; }
     const int64_t N = n_frames > 0 ? key_ptr[n_frames] : 0;
-    if (N > 0 && (!keys || !desc)) return bad("NULL keys or desc");
+    if (N > 0 && (!keys || !desc)) return complain(who, "NULL keys or desc");
     for (int64_t k = 0; k < N; ++k)
-        if (!std::isfinite(keys[4 * k]) || !std::isfinite(keys[4 * k + 1])) return bad("non-finite coordinate");
+        if (!std::isfinite(keys[4 * k]) || !std::isfinite(keys[4 * k + 1])) return complain(who, "non-finite coordinate");
     std::unique_ptr<xrsfm_ba_frames> fs(new xrsfm_ba_frames);
     fs->n_frames = n_frames;
     if (n_frames > 0) fs->key_ptr.assign(key_ptr, key_ptr + n_frames + 1);
     if (N > 0) {
         if (int e = frames_no_device()) return e;
         HIPCHK(hipSetDevice(0));
-        FramesStream s;
+        StreamLease s(0);
         if (!s.ok) return XRSFM_BA_ENODEV;
         FramesBlock& b = fs->blk;
         b.n = N; b.L = frames_layout(N, false);
         b.p = g_cache.get(0, b.L.total, &b.cls);
-        FramesPin stage;
+        PinLease stage;
         if (!b.p || !stage.get(144 * (size_t)N)) return XRSFM_BA_ENOMEM;
         memcpy(stage.p, keys, 16 * (size_t)N);
         memcpy(stage.p + 16 * (size_t)N, desc, 128 * (size_t)N);
-        if (hipMemcpyAsync(b.at(b.L.o_keys), stage.p, 16 * (size_t)N, hipMemcpyHostToDevice, s.hb.stream) != hipSuccess ||
-            hipMemcpyAsync(b.at(b.L.o_desc), stage.p + 16 * (size_t)N, 128 * (size_t)N, hipMemcpyHostToDevice, s.hb.stream) != hipSuccess) {
-            (void)hipStreamSynchronize(s.hb.stream);
+        if (hipMemcpyAsync(b.at(b.L.o_keys), stage.p, 16 * (size_t)N, hipMemcpyHostToDevice, s.stream()) != hipSuccess ||
+            hipMemcpyAsync(b.at(b.L.o_desc), stage.p + 16 * (size_t)N, 128 * (size_t)N, hipMemcpyHostToDevice, s.stream()) != hipSuccess) {
+            (void)hipStreamSynchronize(s.stream());
             return XRSFM_BA_ENODEV;
         }
-        if (int e = frames_prep(s.hb.stream, b)) { (void)hipStreamSynchronize(s.hb.stream); return e; }
+        if (int e = frames_prep(s.stream(), b)) { (void)hipStreamSynchronize(s.stream()); return e; }
     }
     *out = fs.release();
     return XRSFM_BA_OK;
@@ -5139,15 +5029,14 @@ int frames_create_impl(int32_t n_frames, const int64_t* key_ptr, const float* ke
 int frames_from_images_impl(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sift_desc_options* dopt, int32_t n_images, const int32_t* width, const int32_t* height,
                             const int64_t* pixel_ptr, const uint8_t* pixels, xrsfm_ba_frames** out) {
     const char* who = "xrsfm_ba_frames_from_images";
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (opt && !dopt) return bad("NULL descriptor options");
-    if (opt && dopt->upright != 0 && dopt->upright != 1) return bad("upright outside {0, 1}");
+    if (opt && !dopt) return complain(who, "NULL descriptor options");
+    if (opt && dopt->upright != 0 && dopt->upright != 1) return complain(who, "upright outside {0, 1}");
     if (int e = sift_check(who, opt, n_images, width, height, pixel_ptr, pixels)) return e;
-    if (!out) return bad("NULL out");
+    if (!out) return complain(who, "NULL out");
     std::unique_ptr<xrsfm_ba_frames> fs(new xrsfm_ba_frames);
     fs->n_frames = n_images; fs->from_images = true; fs->nl = opt->num_octaves * xsift::kKeyLevels;
     if (n_images > 0) {
-        if (int e = sift_no_device()) return e;
+        if (int e = require_device("keypoint detection")) return e;
         SiftResult R;
         SiftSink sink;
         const SiftDescRequest dq{(int)dopt->upright, false, false};
@@ -5160,9 +5049,9 @@ int frames_from_images_impl(const xrsfm_ba_sift_options* opt, const xrsfm_ba_sif
         for (const FramesBlock& c : sink.chunks) held += c.n;
         if (held != N) return XRSFM_BA_EINTERNAL;
         if (N > 0) {
-            FramesStream s;
+            StreamLease s(0);
             if (!s.ok) return XRSFM_BA_ENODEV;
-            hipStream_t st = s.hb.stream;
+            hipStream_t st = s.stream();
             FramesBlock& b = fs->blk;
             if (sink.chunks.size() == 1) {
                 b = sink.chunks[0];
@@ -5200,9 +5089,9 @@ int frames_info_impl(const xrsfm_ba_frames* fs, int32_t* n_frames, int64_t* key_
 }
 
 int frames_download_impl(const xrsfm_ba_frames* fs, int64_t capacity, float* keys, uint8_t* desc, int32_t* loc, int8_t* sign, int32_t* level_count) {
-    auto bad = [](const char* what) { fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_download: %s\n", what); return XRSFM_BA_EINVAL; };
-    if (!fs) return bad("NULL frame set");
-    if (!fs->from_images && (loc || sign || level_count)) return bad("loc, sign and level_count exist only for sets made from images");
+    const char* who = "xrsfm_ba_frames_download";
+    if (!fs) return complain(who, "NULL frame set");
+    if (!fs->from_images && (loc || sign || level_count)) return complain(who, "loc, sign and level_count exist only for sets made from images");
     const int64_t N = fs->key_ptr.back();
     if (capacity < N) {
         fprintf(stderr, "[xrsfm_ba] xrsfm_ba_frames_download: capacity %lld is below the %lld keypoints of the set\n", (long long)capacity, (long long)N);
@@ -5210,12 +5099,12 @@ int frames_download_impl(const xrsfm_ba_frames* fs, int64_t capacity, float* key
     }
     if (N > 0 && (keys || desc || loc || sign)) {
         HIPCHK(hipSetDevice(0));
-        FramesStream s;
+        StreamLease s(0);
         if (!s.ok) return XRSFM_BA_ENODEV;
-        hipStream_t st = s.hb.stream;
+        hipStream_t st = s.stream();
         const FramesBlock& b = fs->blk;
         const size_t n = (size_t)N, h_keys = 0, h_desc = 16 * n, h_loc = h_desc + 128 * n, h_sign = h_loc + 16 * n, h_w = h_sign + ((n + 15) & ~(size_t)15), h_total = h_w + 4 * n;
-        FramesPin back;
+        PinLease back;
         if (!back.get(h_total)) return XRSFM_BA_ENOMEM;
         bool ok = true;
         if (keys) ok = ok && hipMemcpyAsync(back.p + h_keys, b.at(b.L.o_keys), 16 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
@@ -5242,8 +5131,8 @@ int frames_download_impl(const xrsfm_ba_frames* fs, int64_t capacity, float* key
 // sub-batch's own; frames_verify then puts the blocks behind one another and runs k_verify_pairs ONCE on every pair of the call: a
 // pair keeps a workgroup busy for its whole scan, and a launch per sub-batch would leave most of the device idle for that long.
 struct FramesGathered {                        // of one sub-batch
-    FramesDev blk;                             // [records | coordinates double[4] per match | matches]
-    FramesPin stage;
+    DevLease blk;                             // [records | coordinates double[4] per match | matches]
+    PinLease stage;
     size_t o_m = 0, o_mt = 0;
     int64_t first = 0, n = 0;                  // its matches in the call's arrays
 };
@@ -5270,7 +5159,7 @@ int frames_gather(hipStream_t st, const xrsfm_ba_frames* fs, int np, const int32
     if (Nm == 0) return XRSFM_BA_OK;
     const size_t rec_bytes = sizeof(FramesGatherPair) * (size_t)np;
     g->o_m = al(rec_bytes); g->o_mt = g->o_m + al(sizeof(double) * 4 * (size_t)Nm);
-    if (!g->blk.get(g->o_mt + al(sizeof(int32_t) * 2 * (size_t)Nm)) || !g->stage.get(rec_bytes)) return XRSFM_BA_ENOMEM;
+    if (!g->blk.get(0, g->o_mt + al(sizeof(int32_t) * 2 * (size_t)Nm)) || !g->stage.get(rec_bytes)) return XRSFM_BA_ENOMEM;
     FramesGatherPair* gp = (FramesGatherPair*)g->stage.p;
     for (int q = 0; q < np; ++q)
         gp[q] = FramesGatherPair{prs[q].row_off, prs[q].a_off, prs[q].b_off, beg[(size_t)q], count[(size_t)q], prs[q].n_a, prs[q].n_b};
@@ -5287,27 +5176,27 @@ int frames_gather(hipStream_t st, const xrsfm_ba_frames* fs, int np, const int32
 // records and dyn rows up, the gathered blocks into place, k_verify_pairs, one read-back of matches, masks and per-pair results
 int frames_verify(hipStream_t st, const xrsfm_ba_fund_options* vopt, int32_t n_pairs, const double* pair_max_error, const uint32_t* pair_seed, int64_t Nm,
                   const std::vector<std::unique_ptr<FramesGathered>>& held, hipEvent_t* ev, const MatchResult& R, FramesVerdict* V) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int Np = n_pairs;
     std::vector<FundPair> fp((size_t)Np);
-    FundDyn dyn;
+    xstage::TrialRows dyn;
     for (int j = 0; j < Np; ++j)
         fp[(size_t)j] = fund_pair_record(vopt, V->beg[(size_t)j], R.count[(size_t)j], pair_max_error ? pair_max_error + j : nullptr, pair_seed ? pair_seed + j : nullptr, dyn);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes ? bytes : 8); return o; };
-    const size_t o_pr = take(sizeof(FundPair) * (size_t)Np), o_dyn = take(sizeof(int32_t) * dyn.rows.size());
-    const size_t in_bytes = off, o_m = take(sizeof(double) * 4 * (size_t)Nm), out0 = off;
-    const size_t o_F = take(sizeof(double) * 9 * (size_t)Np), o_ninl = take(sizeof(int) * (size_t)Np), o_ntr = take(sizeof(int) * (size_t)Np),
-                 o_best = take(sizeof(int) * (size_t)Np), o_stat = take((size_t)Np), o_mask = take((size_t)Nm), o_mt = take(sizeof(int32_t) * 2 * (size_t)Nm);
-    const size_t out_bytes = off - out0;
-    FramesDev blk;
-    FramesPin stage, back;
-    if (!blk.get(off) || !stage.get(in_bytes) || !back.get(out_bytes)) return XRSFM_BA_ENOMEM;
+    xstage::Layout L;
+    const size_t o_pr = L.take(sizeof(FundPair) * (size_t)Np), o_dyn = L.take(sizeof(int32_t) * dyn.rows.size());
+    L.end_inputs();
+    const size_t o_m = L.take(sizeof(double) * 4 * (size_t)Nm);          // device only: the gathered blocks land here
+    L.begin_outputs();
+    const size_t o_F = L.take(sizeof(double) * 9 * (size_t)Np), o_ninl = L.take(sizeof(int) * (size_t)Np), o_ntr = L.take(sizeof(int) * (size_t)Np),
+                 o_best = L.take(sizeof(int) * (size_t)Np), o_stat = L.take((size_t)Np), o_mask = L.take((size_t)Nm), o_mt = L.take(sizeof(int32_t) * 2 * (size_t)Nm);
+    L.end_outputs();
+    DevLease blk;
+    PinLease stage, back;
+    if (!blk.get(0, L.total()) || !stage.get(L.in_bytes) || !back.get(L.out_bytes)) return XRSFM_BA_ENOMEM;
     unsigned char* base = (unsigned char*)blk.p;
     memcpy(stage.p + o_pr, fp.data(), sizeof(FundPair) * (size_t)Np);
     if (!dyn.rows.empty()) memcpy(stage.p + o_dyn, dyn.rows.data(), sizeof(int32_t) * dyn.rows.size());
     int e = 0;
-    if (hipMemcpyAsync(base, stage.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (hipMemcpyAsync(base, stage.p, L.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) e = XRSFM_BA_ENODEV;
     for (const auto& g : held) {
         if (e) break;
         const unsigned char* src = (const unsigned char*)g->blk.p;
@@ -5322,17 +5211,17 @@ int frames_verify(hipStream_t st, const xrsfm_ba_fund_options* vopt, int32_t n_p
         if (hipGetLastError() != hipSuccess) e = XRSFM_BA_ENODEV;
     }
     if (ev) (void)hipEventRecord(ev[1], st);
-    if (!e && hipMemcpyAsync(back.p, base + out0, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
+    if (!e && hipMemcpyAsync(back.p, base + L.out0, L.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) e = XRSFM_BA_ENODEV;
     if (hipStreamSynchronize(st) != hipSuccess) e = XRSFM_BA_ENODEV;
     if (e) return e;
-    const unsigned char* o = back.p - out0;                // (offsets above are relative to the block)
-    V->stat.assign(o + o_stat, o + o_stat + Np);
-    V->F.assign((const double*)(o + o_F), (const double*)(o + o_F) + 9 * (size_t)Np);
-    V->ninl.assign((const int32_t*)(o + o_ninl), (const int32_t*)(o + o_ninl) + Np);
-    V->ntr.assign((const int32_t*)(o + o_ntr), (const int32_t*)(o + o_ntr) + Np);
-    V->best.assign((const int32_t*)(o + o_best), (const int32_t*)(o + o_best) + Np);
-    V->mask.assign(o + o_mask, o + o_mask + (size_t)Nm);
-    V->matches.assign((const int32_t*)(o + o_mt), (const int32_t*)(o + o_mt) + 2 * (size_t)Nm);
+    const xstage::View o{back.p, L.out0};
+    V->stat.assign(o.at<unsigned char>(o_stat), o.at<unsigned char>(o_stat) + Np);
+    V->F.assign(o.at<double>(o_F), o.at<double>(o_F) + 9 * (size_t)Np);
+    V->ninl.assign(o.at<int32_t>(o_ninl), o.at<int32_t>(o_ninl) + Np);
+    V->ntr.assign(o.at<int32_t>(o_ntr), o.at<int32_t>(o_ntr) + Np);
+    V->best.assign(o.at<int32_t>(o_best), o.at<int32_t>(o_best) + Np);
+    V->mask.assign(o.at<unsigned char>(o_mask), o.at<unsigned char>(o_mask) + (size_t)Nm);
+    V->matches.assign(o.at<int32_t>(o_mt), o.at<int32_t>(o_mt) + 2 * (size_t)Nm);
     return XRSFM_BA_OK;
 }
 
@@ -5341,18 +5230,17 @@ int frames_match_impl(const xrsfm_ba_frames* fs, const xrsfm_ba_match_options* m
                       int32_t* num_row, int32_t* num_col, uint8_t* status, double* F, uint8_t* inlier_mask, int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial,
                       uint8_t* accepted) {
     const char* who = "xrsfm_ba_frames_match";
-    auto bad = [who](const char* what) { fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, what); return XRSFM_BA_EINVAL; };
-    if (!fs) return bad("NULL frame set");
+    if (!fs) return complain(who, "NULL frame set");
     if (int e = match_check_options(who, mopt, n_pairs, fs->n_frames, matches_capacity)) return e;
     if (vopt) { if (int e = fund_check_options(who, vopt, n_pairs)) return e; }
-    else if (status || F || inlier_mask || num_inliers || num_trials || best_trial || accepted) return bad("verification outputs without verification options");
+    else if (status || F || inlier_mask || num_inliers || num_trials || best_trial || accepted) return complain(who, "verification outputs without verification options");
     if (n_pairs == 0) return XRSFM_BA_OK;
-    if (!match_ptr) return bad("NULL match_ptr");
-    if (!pair_a || !pair_b) return bad("NULL pair_a or pair_b");
+    if (!match_ptr) return complain(who, "NULL match_ptr");
+    if (!pair_a || !pair_b) return complain(who, "NULL pair_a or pair_b");
     for (int p = 0; p < n_pairs; ++p)
-        if (pair_a[p] < 0 || pair_a[p] >= fs->n_frames || pair_b[p] < 0 || pair_b[p] >= fs->n_frames) return bad("frame index out of range");
-    if (matches_capacity > 0 && !matches) return bad("NULL matches");
-    if (vopt && (!status || !F || !inlier_mask)) return bad("NULL status, F or inlier_mask");
+        if (pair_a[p] < 0 || pair_a[p] >= fs->n_frames || pair_b[p] < 0 || pair_b[p] >= fs->n_frames) return complain(who, "frame index out of range");
+    if (matches_capacity > 0 && !matches) return complain(who, "NULL matches");
+    if (vopt && (!status || !F || !inlier_mask)) return complain(who, "NULL status, F or inlier_mask");
     if (vopt) if (int e = fund_check_pair_errors(who, n_pairs, pair_max_error)) return e;
     if (int e = frames_no_device()) return e;
     const int n_frames = fs->n_frames;
@@ -5370,12 +5258,12 @@ int frames_match_impl(const xrsfm_ba_frames* fs, const xrsfm_ba_match_options* m
         HIPCHK(hipSetDevice(0));
         const float* tab = match_table_device();
         if (!tab) return XRSFM_BA_ENOMEM;
-        FramesStream s;
+        StreamLease s(0);
         if (!s.ok) return XRSFM_BA_ENODEV;
-        hipStream_t st = s.hb.stream;
-        FramesDev ws;
-        FramesPin stage, back;
-        if (!plan.live.empty() && (!ws.get(plan.ws_bytes) || !stage.get(plan.in_max) || !back.get(plan.back_max))) return XRSFM_BA_ENOMEM;
+        hipStream_t st = s.stream();
+        DevLease ws;
+        PinLease stage, back;
+        if (!plan.live.empty() && (!ws.get(0, plan.ws_bytes) || !stage.get(plan.in_max) || !back.get(plan.back_max))) return XRSFM_BA_ENOMEM;
         // XRSFM_BA_MATCH_TIMING: the kernels' times from events on the stream, one line on stderr (tools/frame_set_timing.py)
         struct Events { hipEvent_t ev[7] = {}; bool on = false; ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); } } tm;
         if (getenv("XRSFM_BA_MATCH_TIMING")) { tm.on = true; for (hipEvent_t& x : tm.ev) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; tm.on = false; } }
