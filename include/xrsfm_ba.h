@@ -976,6 +976,70 @@ int xrsfm_ba_frames_match(const xrsfm_ba_frames *fs, const xrsfm_ba_match_option
 
 void xrsfm_ba_frames_destroy(xrsfm_ba_frames *fs);   /* NULL is fine */
 
+/* Match expansion: from the verified pairs so far to the pairs to try next (reference MatchExpansionSolver::Run,
+ * src/feature/match_expansion.cc:407-454, the first half of every iteration of ExpansionAndMatching).  One call is one
+ * Run of a freshly constructed solver: the component of the initial pair, the simulated incremental reconstruction in synchronous
+ * rounds (a frame registers with min_visible marks), the tracks of AddTrack in list order with every quirk of the original, the
+ * per-patch covisibility of every connected frame, the covisibility candidates and the similarity candidates.  All of it is integer
+ * work and every output is exact.  The second simulation of the reference (100 marks) feeds only a printf and is not computed.
+ *
+ * Frames: key_ptr [n_frames+1], keys [N][4] float (x and y are read), width and height [n_frames].  Verified pairs: pair_a, pair_b
+ * [n_pairs] (id1, id2 as stored: the order matters to the tracks and to the first step of the simulation), match_ptr [n_pairs+1],
+ * matches [M][2] (key point in pair_a's frame, key point in pair_b's frame), as xrsfm_ba_frames_match returns them for the accepted
+ * pairs with the inliers alone.  rank_ptr [n_frames+1], rank_ids: the retrieval list of every frame, best first; a rank is the 1-based
+ * position, the last one for an id listed twice.  tried_a, tried_b [n_tried]: pairs not to propose again, in either order.
+ * init_a, init_b: the initial pair, in either order; it must be among the pairs.
+ *
+ * Outputs: *n_out unordered pairs out_a < out_b ascending in (out_a, out_b), each once, out_source 1 (covisibility) or 2 (similarity);
+ * capacity is their room.  Per frame, each may be NULL: connected, registered, may_register (0 / 1), visible (the final mark counts).
+ * cand (may be NULL, then cand_capacity and n_cand are not read): one row (id1, id2, shared matches, covisible patches) for every
+ * directed candidate that passed the tests before GetMatcheNum (id2 in the list of id1, not itself, not tried, one of them
+ * registered, both connected), ascending in (id1, id2).  The number of rank_ids bounds both *n_out and *n_cand.  stats [8], may be
+ * NULL: rounds that registered a frame, tracks, valid tracks, correspondence entries, observations walked by the covisibility kernel
+ * per pass, codes kept, passes per frame, 0.
+ *
+ * Errors: every check runs on the host before the device is touched and prints one line on stderr that names the entry; on any
+ * negative code no output is touched.  XRSFM_BA_EINVAL: NULL opt or needed array; options out of range (patch_cols * patch_rows
+ * outside 1..128, min_patch_obs outside {1, 2}, min_visible < 1, a negative threshold, ranks not ascending); an index out of range; a
+ * pair with a == b; an unordered pair listed twice; a width or height below the patch grid; a key point whose patch index would be
+ * negative or whose coordinate no int holds; the initial pair not among the pairs; a capacity below the need (the line names the
+ * need).  XRSFM_BA_ETOOBIG: key points, matches or observations above INT32_MAX, or more frames than one workgroup's LDS holds
+ * bits for.  n_frames == 0 is success with nothing out and needs no device; otherwise XRSFM_BA_ENODEV without one (no CPU path).
+ * XRSFM_BA_EXPAND_WINDOW=W (read per call) lowers the third frames per pass of the covisibility kernel: a test aid. */
+typedef struct {
+    int32_t patch_cols;            /* 10  col_num                                                 */
+    int32_t patch_rows;            /* 10  row_num                                                 */
+    int32_t min_patch_obs;         /* 2   _T_: observations that make a (frame, patch) covisible  */
+    int32_t min_visible;           /* 30  marks that register a frame in the simulation           */
+    int32_t max_shared_matches;    /* 50  GetMatcheNum above this: the pair is skipped            */
+    int32_t min_covisible_patches; /* 1                                                           */
+    int32_t similarity_rank_max;   /* 40                                                          */
+    int32_t mayreg_rank_lo;        /* 5   ranks up to here are counted and unused                 */
+    int32_t mayreg_rank_mid;       /* 25  count2: ranks lo+1 .. mid                               */
+    int32_t mayreg_rank_hi;        /* 50  count3: ranks mid+1 .. hi                               */
+    int32_t mayreg_count_mid;      /* 15  count2 >= this, or                                      */
+    int32_t mayreg_count_sum;      /* 35  count2 + count3 >= this                                 */
+} xrsfm_ba_expand_options;
+void xrsfm_ba_expand_options_default(xrsfm_ba_expand_options *opt);   /* the values above */
+
+int xrsfm_ba_expand_candidates(const xrsfm_ba_expand_options *opt, int32_t n_frames, const int64_t *key_ptr, const float *keys,
+                               const int32_t *width, const int32_t *height, int32_t n_pairs, const int32_t *pair_a,
+                               const int32_t *pair_b, const int64_t *match_ptr, const int32_t *matches, const int64_t *rank_ptr,
+                               const int32_t *rank_ids, int32_t n_tried, const int32_t *tried_a, const int32_t *tried_b,
+                               int32_t init_a, int32_t init_b, int64_t capacity, int64_t *n_out, int32_t *out_a, int32_t *out_b,
+                               uint8_t *out_source, uint8_t *connected, uint8_t *registered, uint8_t *may_register,
+                               int32_t *visible, int64_t cand_capacity, int64_t *n_cand, int32_t *cand, int64_t *stats);
+
+/* The same call on a resident frame set: the patches come from the key points on the device and no key point is uploaded.  The
+ * patch check of the key points is made by the kernel here: XRSFM_BA_EINVAL after its launch, outputs untouched. */
+int xrsfm_ba_frames_expand(const xrsfm_ba_frames *fs, const xrsfm_ba_expand_options *opt, const int32_t *width,
+                           const int32_t *height, int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                           const int64_t *match_ptr, const int32_t *matches, const int64_t *rank_ptr, const int32_t *rank_ids,
+                           int32_t n_tried, const int32_t *tried_a, const int32_t *tried_b, int32_t init_a, int32_t init_b,
+                           int64_t capacity, int64_t *n_out, int32_t *out_a, int32_t *out_b, uint8_t *out_source,
+                           uint8_t *connected, uint8_t *registered, uint8_t *may_register, int32_t *visible,
+                           int64_t cand_capacity, int64_t *n_cand, int32_t *cand, int64_t *stats);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */
@@ -1102,6 +1166,24 @@ int xrsfm_ba_debug_stored_j(xrsfm_ba_context *ctx, int32_t *stored);
  * xrsfm_ba_run fetches them after iteration 0: a fused context reads what the tail of the linearisation left, an unfused or
  * bal9 context launches the camera gradient kernel. */
 int xrsfm_ba_debug_lin_scalars(xrsfm_ba_context *ctx, double out[4]);
+
+/* TEST ENTRY, host only (needs no device).  The tracks that match expansion builds from the pairs in list order (MakeTrack /
+ * AddTrack): key_track [N] (-1, or a track, which may be invalid), *n_tracks, track_ptr [track_capacity+1], invalid
+ * [track_capacity], obs_frame and obs_key [obs_capacity] ascending by frame within a track (obs_key: the key point within its
+ * frame).  *n_tracks <= M and *n_obs <= 2 M for M matches.  Argument checks as in xrsfm_ba_expand_candidates; a capacity below the
+ * need is XRSFM_BA_EINVAL and the line names it. */
+int xrsfm_ba_debug_expand_tracks(int32_t n_frames, const int64_t *key_ptr, int32_t n_pairs, const int32_t *pair_a,
+                                 const int32_t *pair_b, const int64_t *match_ptr, const int32_t *matches, int32_t *key_track,
+                                 int64_t track_capacity, int64_t *n_tracks, int64_t *track_ptr, uint8_t *invalid,
+                                 int64_t obs_capacity, int64_t *n_obs, int32_t *obs_frame, int32_t *obs_key);
+
+/* TEST ENTRY.  What k_expand_covis leaves: per frame (unconnected frames: nothing) the ascending codes t * patches + patch of
+ * the (third frame t, patch) seen min_patch_obs times or more: code_ptr [n_frames+1], codes [code_capacity].  Arguments and checks
+ * as in xrsfm_ba_expand_candidates. */
+int xrsfm_ba_debug_expand_covis(const xrsfm_ba_expand_options *opt, int32_t n_frames, const int64_t *key_ptr, const float *keys,
+                                const int32_t *width, const int32_t *height, int32_t n_pairs, const int32_t *pair_a,
+                                const int32_t *pair_b, const int64_t *match_ptr, const int32_t *matches, int32_t init_a,
+                                int32_t init_b, int64_t code_capacity, int64_t *code_ptr, int32_t *codes);
 
 #ifdef __cplusplus
 }

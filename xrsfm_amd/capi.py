@@ -117,6 +117,11 @@ class CSummary(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CExpandOptions(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("patch_cols", "patch_rows", "min_patch_obs", "min_visible", "max_shared_matches", "min_covisible_patches",
+                                         "similarity_rank_max", "mayreg_rank_lo", "mayreg_rank_mid", "mayreg_rank_hi", "mayreg_count_mid", "mayreg_count_sum")]
+
+
 # every symbol include/xrsfm_ba.h declares
 EXPORTS = [
     "xrsfm_ba_default_options", "xrsfm_ba_version", "xrsfm_ba_create", "xrsfm_ba_comm_unique_id",
@@ -138,6 +143,8 @@ EXPORTS = [
     "xrsfm_ba_sift_desc_options_default", "xrsfm_ba_extract_features", "xrsfm_ba_debug_sift_gradient", "xrsfm_ba_debug_sift_describe",
     "xrsfm_ba_frames_create", "xrsfm_ba_frames_from_images", "xrsfm_ba_frames_info", "xrsfm_ba_frames_download", "xrsfm_ba_frames_match",
     "xrsfm_ba_frames_destroy",
+    "xrsfm_ba_expand_options_default", "xrsfm_ba_expand_candidates", "xrsfm_ba_frames_expand", "xrsfm_ba_debug_expand_tracks",
+    "xrsfm_ba_debug_expand_covis",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -349,6 +356,21 @@ def load(path: str | None = None):
     lib.xrsfm_ba_frames_match.restype = C.c_int
     lib.xrsfm_ba_frames_destroy.argtypes = [vp]
     lib.xrsfm_ba_frames_destroy.restype = None
+    _eo = C.POINTER(CExpandOptions)
+    _expand_tail = [C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_int32_p, _c_int64_p, _c_int32_p, C.c_int32, _c_int32_p, _c_int32_p, C.c_int32, C.c_int32,
+                    C.c_int64, _c_int64_p, _c_int32_p, _c_int32_p, _c_uint8_p, _c_uint8_p, _c_uint8_p, _c_uint8_p, _c_int32_p, C.c_int64, _c_int64_p, _c_int32_p, _c_int64_p]
+    lib.xrsfm_ba_expand_options_default.argtypes = [_eo]
+    lib.xrsfm_ba_expand_options_default.restype = None
+    lib.xrsfm_ba_expand_candidates.argtypes = [_eo, C.c_int32, _c_int64_p, _c_float_p, _c_int32_p, _c_int32_p] + _expand_tail
+    lib.xrsfm_ba_expand_candidates.restype = C.c_int
+    lib.xrsfm_ba_frames_expand.argtypes = [vp, _eo, _c_int32_p, _c_int32_p] + _expand_tail
+    lib.xrsfm_ba_frames_expand.restype = C.c_int
+    lib.xrsfm_ba_debug_expand_tracks.argtypes = [C.c_int32, _c_int64_p, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_int32_p, _c_int32_p, C.c_int64, _c_int64_p,
+                                                 _c_int64_p, _c_uint8_p, C.c_int64, _c_int64_p, _c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_debug_expand_tracks.restype = C.c_int
+    lib.xrsfm_ba_debug_expand_covis.argtypes = [_eo, C.c_int32, _c_int64_p, _c_float_p, _c_int32_p, _c_int32_p, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_int32_p,
+                                                C.c_int32, C.c_int32, C.c_int64, _c_int64_p, _c_int32_p]
+    lib.xrsfm_ba_debug_expand_covis.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1594,6 +1616,171 @@ def frames_match(frames: Frames, pair_a, pair_b, match_options: CMatchOptions | 
         v["inlier_mask"] = v["inlier_mask"][:int(mp[-1])].copy()
         r.update(v)
     return r
+
+
+def expand_options(**overrides) -> CExpandOptions:
+    """xrsfm_ba_expand_options_default: the constants of the reference's MatchExpansionSolver."""
+    o = CExpandOptions()
+    load().xrsfm_ba_expand_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+EXPAND_STATS = ("rounds", "tracks", "valid_tracks", "corr_entries", "items_walked", "codes_kept", "passes")
+
+
+class _ExpandArgs:
+    """the arrays the expansion entries share, kept alive for the call"""
+
+    def __init__(self, name, n_frames, pair_a, pair_b, match_ptr, matches, sizes=None, rank_ptr=None, rank_ids=None, tried=None):
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)
+        self.n = int(n_frames)
+        self.pa, self.pb = i32(pair_a).reshape(-1), i32(pair_b).reshape(-1)
+        self.mp = np.ascontiguousarray(match_ptr, np.int64).reshape(-1) if len(self.pa) else np.zeros(1, np.int64)
+        self.m = i32(matches).reshape(-1, 2)
+        if self.pa.shape != self.pb.shape or len(self.mp) != len(self.pa) + 1 or self.mp[-1] != len(self.m):
+            raise ValueError(name + ": inconsistent pair and match arrays")
+        if sizes is not None:
+            sizes = i32(sizes).reshape(-1, 2)
+            if len(sizes) != self.n:
+                raise ValueError(name + ": one (width, height) per frame")
+            self.w, self.h = np.ascontiguousarray(sizes[:, 0]), np.ascontiguousarray(sizes[:, 1])
+        if rank_ptr is not None:
+            self.rp = np.ascontiguousarray(rank_ptr, np.int64).reshape(-1)
+            self.ri = i32(rank_ids).reshape(-1)
+            if len(self.rp) != self.n + 1 or self.rp[-1] != len(self.ri):
+                raise ValueError(name + ": inconsistent rank arrays")
+            t = i32(tried if tried is not None else np.zeros((0, 2))).reshape(-1, 2)
+            self.ta, self.tb = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
+
+    @staticmethod
+    def ip(a):
+        return a.ctypes.data_as(_c_int32_p)
+
+    @staticmethod
+    def lp(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def pairs(self):
+        return [len(self.pa), self.ip(self.pa), self.ip(self.pb), self.lp(self.mp), self.ip(self.m)]
+
+
+def _expand_call(name, head, a: _ExpandArgs, init_a, init_b, with_cand):
+    n, cap = a.n, len(a.ri)
+    r = dict(connected=np.zeros(n, np.uint8), registered=np.zeros(n, np.uint8), may_register=np.zeros(n, np.uint8), visible=np.zeros(n, np.int32))
+    oa, ob, src = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+    cand = np.zeros((cap, 4), np.int32)
+    n_out, n_cand = C.c_int64(0), C.c_int64(0)
+    stats = np.zeros(8, np.int64)
+    up = lambda x: x.ctypes.data_as(_c_uint8_p)
+    check(getattr(load(), name)(*head, *a.pairs(), a.lp(a.rp), a.ip(a.ri), len(a.ta), a.ip(a.ta), a.ip(a.tb), int(init_a), int(init_b), cap, C.byref(n_out), a.ip(oa),
+                                a.ip(ob), up(src), up(r["connected"]), up(r["registered"]), up(r["may_register"]), a.ip(r["visible"]), cap if with_cand else 0,
+                                C.byref(n_cand) if with_cand else None, a.ip(cand) if with_cand else None, a.lp(stats)), name)
+    k = int(n_out.value)
+    r.update(pair_a=oa[:k].copy(), pair_b=ob[:k].copy(), source=src[:k].copy(), stats=dict(zip(EXPAND_STATS, (int(x) for x in stats))))
+    if with_cand:
+        r["cand"] = cand[:int(n_cand.value)].copy()
+    return r
+
+
+def expand_candidates(key_ptr, keys, sizes, pair_a, pair_b, match_ptr, matches, rank_ptr, rank_ids, init_a, init_b, tried=None,
+                      options: CExpandOptions | None = None, with_cand: bool = True) -> dict:
+    """xrsfm_ba_expand_candidates: one MatchExpansionSolver::Run.  keys [N][4] or [N][2] float32, sizes [n][2] (width, height), the
+    verified pairs with their inlier matches (verified_matches), the retrieval lists as a CSR, tried [k][2].  Returns pair_a, pair_b,
+    source (1 covisibility, 2 similarity), connected, registered, may_register, visible, cand [k][4] and stats."""
+    o = options if options is not None else expand_options()
+    key_ptr = np.ascontiguousarray(key_ptr, np.int64).reshape(-1)
+    k = np.asarray(keys, np.float32).reshape(len(keys), -1) if len(keys) else np.zeros((0, 4), np.float32)
+    if k.shape[1] == 2:
+        k = np.concatenate([k, np.zeros((len(k), 2), np.float32)], axis=1)
+    k = np.ascontiguousarray(k, np.float32)
+    if k.shape[1] != 4 or key_ptr[-1] != len(k):
+        raise ValueError("expand_candidates: inconsistent key arrays")
+    a = _ExpandArgs("expand_candidates", len(key_ptr) - 1, pair_a, pair_b, match_ptr, matches, sizes, rank_ptr, rank_ids, tried)
+    head = [C.byref(o), a.n, a.lp(key_ptr), k.ctypes.data_as(C.POINTER(C.c_float)), a.ip(a.w), a.ip(a.h)]
+    return _expand_call("xrsfm_ba_expand_candidates", head, a, init_a, init_b, with_cand)
+
+
+def frames_expand(frames: Frames, sizes, pair_a, pair_b, match_ptr, matches, rank_ptr, rank_ids, init_a, init_b, tried=None,
+                  options: CExpandOptions | None = None, with_cand: bool = True) -> dict:
+    """xrsfm_ba_frames_expand: expand_candidates on a resident set; no key point is uploaded."""
+    o = options if options is not None else expand_options()
+    a = _ExpandArgs("frames_expand", frames_info(frames)["n_frames"], pair_a, pair_b, match_ptr, matches, sizes, rank_ptr, rank_ids, tried)
+    return _expand_call("xrsfm_ba_frames_expand", [frames._h(), C.byref(o), a.ip(a.w), a.ip(a.h)], a, init_a, init_b, with_cand)
+
+
+def debug_expand_tracks(key_ptr, pair_a, pair_b, match_ptr, matches) -> dict:
+    """xrsfm_ba_debug_expand_tracks (no GPU): key_track [N], track_ptr [T + 1], obs_frame, obs_key, invalid [T]."""
+    key_ptr = np.ascontiguousarray(key_ptr, np.int64).reshape(-1)
+    a = _ExpandArgs("debug_expand_tracks", len(key_ptr) - 1, pair_a, pair_b, match_ptr, matches)
+    M = len(a.m)
+    kt = np.zeros(max(int(key_ptr[-1]), 1), np.int32); tp = np.zeros(M + 1, np.int64); inv = np.zeros(max(M, 1), np.uint8)
+    of, ok = np.zeros(max(2 * M, 1), np.int32), np.zeros(max(2 * M, 1), np.int32)
+    nt, no = C.c_int64(0), C.c_int64(0)
+    check(load().xrsfm_ba_debug_expand_tracks(a.n, a.lp(key_ptr), *a.pairs(), a.ip(kt), M, C.byref(nt), a.lp(tp), inv.ctypes.data_as(_c_uint8_p), 2 * M, C.byref(no),
+                                              a.ip(of), a.ip(ok)), "xrsfm_ba_debug_expand_tracks")
+    T, O = int(nt.value), int(no.value)
+    return dict(key_track=kt[:int(key_ptr[-1])].copy(), track_ptr=tp[:T + 1].copy(), obs_frame=of[:O].copy(), obs_key=ok[:O].copy(), invalid=inv[:T].copy())
+
+
+def debug_expand_covis(key_ptr, keys, sizes, pair_a, pair_b, match_ptr, matches, init_a, init_b, options: CExpandOptions | None = None) -> tuple:
+    """xrsfm_ba_debug_expand_covis: (code_ptr [n + 1], codes) of k_expand_covis."""
+    o = options if options is not None else expand_options()
+    key_ptr = np.ascontiguousarray(key_ptr, np.int64).reshape(-1)
+    k = np.ascontiguousarray(np.asarray(keys, np.float32).reshape(-1, 4))
+    a = _ExpandArgs("debug_expand_covis", len(key_ptr) - 1, pair_a, pair_b, match_ptr, matches, sizes)
+    cap = 2 * len(a.m) * max(a.n, 1)                  # (every observation of a track can be walked from each of its frames)
+    cp = np.zeros(a.n + 1, np.int64); codes = np.zeros(max(cap, 1), np.int32)
+    check(load().xrsfm_ba_debug_expand_covis(C.byref(o), a.n, a.lp(key_ptr), k.ctypes.data_as(C.POINTER(C.c_float)), a.ip(a.w), a.ip(a.h), *a.pairs(), int(init_a),
+                                             int(init_b), cap, a.lp(cp), a.ip(codes)), "xrsfm_ba_debug_expand_covis")
+    return cp, codes[:int(cp[-1])].copy()
+
+
+def expansion_and_matching(frames: Frames, sizes, rank_ptr, rank_ids, init_pairs, init_a, init_b, num_iteration: int = 5,
+                           options: CExpandOptions | None = None, match_options: CMatchOptions | None = None, fund_options: CFundOptions | None = None,
+                           expand=None) -> dict:
+    """The reference's ExpansionAndMatching (feature_processing.cc:324-377) on a resident set.  init_pairs [k][2]: the pairs of the
+    first FeatureMatching (the retrieval's best); they are matched and verified first, then num_iteration times: expand, drop what was
+    tried, frames_match, verified_matches, append the accepted pairs.  `expand` replaces frames_expand (a test passes its yardstick).
+    Returns pair_a, pair_b, match_ptr, matches of the verified pairs in the order they were accepted, tried [k][2], and per iteration
+    the counts the reference prints (candidates, accepted, pairs, matches)."""
+    fo = fund_options if fund_options is not None else verify_pairs_options()
+    expand = expand if expand is not None else frames_expand
+    pa, pb, rows = [], [], []
+    tried, seen, log = [], set(), []
+
+    def match(a, b):
+        r = frames_match(frames, a, b, match_options, fo)
+        kept, m, _ = verified_matches(r, r["match_ptr"], r["matches"])
+        mp = r["match_ptr"]
+        mask = r["inlier_mask"].astype(bool)
+        for p in kept:
+            pa.append(int(a[p])); pb.append(int(b[p])); rows.append(r["matches"][mp[p]:mp[p + 1]][mask[mp[p]:mp[p + 1]]])
+        for x, y in zip(a, b):
+            tried.append((int(x), int(y))); seen.add((min(int(x), int(y)), max(int(x), int(y))))
+        return len(kept)
+
+    def state():
+        ptr = np.zeros(len(rows) + 1, np.int64)
+        if rows:
+            ptr[1:] = np.cumsum([len(x) for x in rows])
+        m = np.concatenate(rows).reshape(-1, 2) if rows else np.zeros((0, 2), np.int32)
+        return np.array(pa, np.int32), np.array(pb, np.int32), ptr, np.ascontiguousarray(m, np.int32)
+
+    ini = np.asarray(init_pairs, np.int32).reshape(-1, 2)
+    accepted = match(ini[:, 0].copy(), ini[:, 1].copy())
+    log.append(dict(candidates=len(ini), accepted=accepted, pairs=len(pa), matches=int(sum(len(x) for x in rows))))
+    for _ in range(int(num_iteration)):
+        a, b, ptr, m = state()
+        r = expand(frames, sizes, a, b, ptr, m, rank_ptr, rank_ids, init_a, init_b, np.array(tried, np.int32).reshape(-1, 2), options)
+        new = [(int(x), int(y)) for x, y in zip(r["pair_a"], r["pair_b"]) if (int(x), int(y)) not in seen]
+        accepted = match(np.array([x for x, _ in new], np.int32), np.array([y for _, y in new], np.int32)) if new else 0
+        log.append(dict(candidates=len(new), accepted=accepted, pairs=len(pa), matches=int(sum(len(x) for x in rows))))
+    a, b, ptr, m = state()
+    return dict(pair_a=a, pair_b=b, match_ptr=ptr, matches=m, tried=np.array(tried, np.int32).reshape(-1, 2), iterations=log)
 
 
 def debug_sift_gradient(image, octave: int, options: CSiftOptions | None = None) -> np.ndarray:

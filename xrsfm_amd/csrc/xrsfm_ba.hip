@@ -29,6 +29,7 @@
 #include "../../include/xrsfm_ba.h"
 #include "ba_chol.h"
 #include "ba_cov.h"
+#include "ba_expand.h"
 #include "ba_filter.h"
 #include "ba_kernels.h"
 #include "ba_lba.h"
@@ -5375,6 +5376,487 @@ int xrsfm_ba_frames_match(const xrsfm_ba_frames* fs, const xrsfm_ba_match_option
 void xrsfm_ba_frames_destroy(xrsfm_ba_frames* fs) {
     if (!fs) return;
     (void)no_throw([&] { if (fs->blk.p) (void)hipSetDevice(0); delete fs; return XRSFM_BA_OK; });
+}
+
+// ---------------------------------------------------------------- match expansion (ba_expand.h)
+static_assert(sizeof(xrsfm_ba_expand_options) == sizeof(xexpand::Opt), "xexpand::Opt mirrors xrsfm_ba_expand_options field for field");
+
+void xrsfm_ba_expand_options_default(xrsfm_ba_expand_options* opt) {
+    if (!opt) return;
+    const xexpand::Opt o = xexpand::default_options();          // match_expansion.h / .cc: col_num, row_num, _T_, 30, 50, 1, 40, 5 / 25 / 50, 15, 35
+    memcpy(opt, &o, sizeof(o));
+}
+
+namespace {
+struct ExpandIn {
+    const char* who;
+    const xrsfm_ba_expand_options* opt;
+    int32_t n_frames;
+    const int64_t* key_ptr;
+    const float* keys;                        // host key points, or null with a resident set
+    const xrsfm_ba_frames* fs;
+    const int32_t *width, *height;
+    int32_t n_pairs;
+    const int32_t *pair_a, *pair_b;
+    const int64_t* match_ptr;
+    const int32_t* matches;
+    const int64_t* rank_ptr;
+    const int32_t* rank_ids;
+    int32_t n_tried;
+    const int32_t *tried_a, *tried_b;
+    int32_t init_a, init_b;
+    bool with_frames, with_search;            // debug_expand_tracks reads neither sizes nor key points; only the search reads ranks and tried pairs
+};
+
+struct ExpandPrep {
+    xexpand::Opt o;
+    int64_t n_keys = 0, n_matches = 0;
+    int32_t window = 0, init_first = 0, init_second = 0;
+    std::vector<int32_t> first;               // key_ptr in 32 bits
+    xexpand::PairIndex ix;
+    xexpand::RankTable rt;
+    std::vector<int64_t> tried;
+    std::vector<uint8_t> connected;
+};
+
+// every check of the entries, on the host; n_frames == 0 passes with nothing prepared
+int expand_check(const ExpandIn& in, ExpandPrep* P) {
+    const char* who = in.who;
+    const int32_t n = in.n_frames;
+    if (in.with_frames || in.with_search) {
+        if (!in.opt) return complain(who, "NULL options");
+        memcpy(&P->o, in.opt, sizeof(P->o));
+        if (const char* fault = xexpand::options_fault(P->o)) return complain(who, fault);
+    } else {
+        P->o = xexpand::default_options();
+    }
+    const xexpand::Opt& o = P->o;
+    if (n < 0 || in.n_pairs < 0 || in.n_tried < 0) return complain(who, "negative count");
+    if (n == 0) {
+        if (in.n_pairs > 0) return complain(who, "pairs without frames");
+        return XRSFM_BA_OK;
+    }
+    if (!in.key_ptr) return complain(who, "NULL key_ptr");
+    if (int e = check_offsets(who, "key_ptr", in.key_ptr, n)) return e;
+    P->n_keys = in.key_ptr[n];
+    if (P->n_keys > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] %s: %lld key points, above INT32_MAX\n", who, (long long)P->n_keys); return XRSFM_BA_ETOOBIG; }
+    if ((int64_t)n * o.patch_cols * o.patch_rows > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] %s: frames times patches above INT32_MAX\n", who); return XRSFM_BA_ETOOBIG; }
+    P->first.resize((size_t)n + 1);
+    for (int32_t f = 0; f <= n; ++f) P->first[(size_t)f] = (int32_t)in.key_ptr[f];
+    if (in.with_frames) {
+        if (!in.width || !in.height) return complain(who, "NULL width or height");
+        for (int32_t f = 0; f < n; ++f)
+            if (in.width[f] < o.patch_cols || in.height[f] < o.patch_rows) return complain(who, "a width or height below the patch grid");
+        if (!in.fs) {
+            if (P->n_keys > 0 && !in.keys) return complain(who, "NULL keys");
+            for (int32_t f = 0; f < n; ++f)
+                for (int64_t k = in.key_ptr[f]; k < in.key_ptr[f + 1]; ++k)
+                    if (xexpand::patch_of(in.keys[4 * k], in.keys[4 * k + 1], in.width[f], in.height[f], o.patch_cols, o.patch_rows) < 0)
+                        return complain(who, "a key point whose patch index is negative or whose coordinate no int holds");
+        }
+        int forced = 0;
+        if (const char* w = getenv("XRSFM_BA_EXPAND_WINDOW")) forced = atoi(w);
+        P->window = xexpand::window_frames(kExpandLdsBytes, n, forced);
+        if (P->window < 1) { fprintf(stderr, "[xrsfm_ba] %s: %d frames, more than one workgroup's LDS holds a bit for\n", who, n); return XRSFM_BA_ETOOBIG; }
+    }
+    if (in.n_pairs > 0 && (!in.pair_a || !in.pair_b || !in.match_ptr)) return complain(who, "NULL pair_a, pair_b or match_ptr");
+    if (in.n_pairs > 0) if (int e = check_offsets(who, "match_ptr", in.match_ptr, in.n_pairs)) return e;
+    P->n_matches = in.n_pairs > 0 ? in.match_ptr[in.n_pairs] : 0;
+    if (P->n_matches > 0x3fffffff) { fprintf(stderr, "[xrsfm_ba] %s: %lld matches, their two entries each above INT32_MAX\n", who, (long long)P->n_matches); return XRSFM_BA_ETOOBIG; }
+    if (P->n_matches > 0 && !in.matches) return complain(who, "NULL matches");
+    for (int32_t p = 0; p < in.n_pairs; ++p) {
+        const int32_t a = in.pair_a[p], b = in.pair_b[p];
+        if (a < 0 || a >= n || b < 0 || b >= n) return complain(who, "frame index of a pair out of range");
+        if (a == b) return complain(who, "a pair of a frame with itself");
+        const int64_t na = in.key_ptr[a + 1] - in.key_ptr[a], nb = in.key_ptr[b + 1] - in.key_ptr[b];
+        for (int64_t m = in.match_ptr[p]; m < in.match_ptr[p + 1]; ++m)
+            if (in.matches[2 * m] < 0 || in.matches[2 * m] >= na || in.matches[2 * m + 1] < 0 || in.matches[2 * m + 1] >= nb) return complain(who, "key point index of a match out of range");
+    }
+    if (!xexpand::pair_index(n, in.n_pairs, in.pair_a, in.pair_b, &P->ix)) return complain(who, "a pair listed twice");
+    if (in.with_search) {
+        if (!in.rank_ptr) return complain(who, "NULL rank_ptr");
+        if (int e = check_offsets(who, "rank_ptr", in.rank_ptr, n)) return e;
+        if (in.rank_ptr[n] > 0 && !in.rank_ids) return complain(who, "NULL rank_ids");
+        for (int64_t k = 0; k < in.rank_ptr[n]; ++k)
+            if (in.rank_ids[k] < 0 || in.rank_ids[k] >= n) return complain(who, "frame index of a rank list out of range");
+        if (in.n_tried > 0 && (!in.tried_a || !in.tried_b)) return complain(who, "NULL tried_a or tried_b");
+        for (int32_t k = 0; k < in.n_tried; ++k)
+            if (in.tried_a[k] < 0 || in.tried_a[k] >= n || in.tried_b[k] < 0 || in.tried_b[k] >= n) return complain(who, "frame index of a tried pair out of range");
+        P->rt = xexpand::rank_table(n, in.rank_ptr, in.rank_ids);
+        P->tried = xexpand::tried_set(in.n_tried, in.tried_a, in.tried_b);
+    }
+    if (in.with_frames) {
+        if (in.init_a < 0 || in.init_a >= n || in.init_b < 0 || in.init_b >= n) return complain(who, "frame index of the initial pair out of range");
+        const int32_t p = xexpand::pair_find(P->ix, in.init_a, in.init_b);
+        if (p < 0) return complain(who, "the initial pair is not among the pairs");
+        P->init_first = in.pair_a[p]; P->init_second = in.pair_b[p];
+        P->connected = xexpand::connected_frames(n, P->ix, P->init_first);
+    }
+    return XRSFM_BA_OK;
+}
+
+struct ExpandDevOut {
+    std::vector<int32_t> visible;             // [n]
+    std::vector<int32_t> cand;                // rows (id1, id2, shared matches, covisible patches)
+    std::vector<int64_t> code_ptr;            // want_codes: [n + 1]
+    std::vector<int32_t> codes;
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+double expand_ms(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); }
+
+// The device half of a call whose arguments have passed expand_check: patches, correspondence lists, the rounds of the simulation,
+// (on the host meanwhile: the tracks), the covisibility codes, and with `search` the counts of the directed candidates.
+int expand_device(const ExpandIn& in, const ExpandPrep& P, bool search, bool want_codes, ExpandDevOut* out) {
+    const char* who = in.who;
+    const int32_t n = in.n_frames;
+    const xexpand::Opt& o = P.o;
+    const int64_t N = P.n_keys, M = P.n_matches;
+    const int32_t patches = o.patch_cols * o.patch_rows;
+    if (int e = require_device("match expansion")) return e;
+    HIPCHK(hipSetDevice(0));
+    StreamLease s(0);
+    if (!s.ok) return XRSFM_BA_ENODEV;
+    const hipStream_t st = s.stream();
+    // XRSFM_BA_EXPAND_TIMING: host clocks per phase (the stream is drained at every phase boundary then) and the kernels' times from
+    // events, one line on stderr (tools/match_expansion_timing.py)
+    const bool timing = getenv("XRSFM_BA_EXPAND_TIMING") != nullptr;
+    struct Events { hipEvent_t ev[8] = {}; bool on = false; ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); } } tm;
+    if (timing) { tm.on = true; for (hipEvent_t& x : tm.ev) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; tm.on = false; } }
+    auto stamp = [&](int k) { if (tm.on) (void)hipEventRecord(tm.ev[k], st); };
+    auto between = [&](int a, int b) { float ms = 0.f; return tm.on && hipEventElapsedTime(&ms, tm.ev[a], tm.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+    double t_upload = 0, t_tracks = 0, t_rounds = 0, t_back = 0;
+    auto t0 = std::chrono::steady_clock::now();
+
+    // ---- block A: frames, matches and pairs up; patches, correspondence lists and the state of the simulation
+    xstage::Layout A;
+    const size_t a_first = A.take(4 * ((size_t)n + 1)), a_size = A.take(8 * (size_t)n), a_keys = in.fs ? 0 : A.take(16 * (size_t)N), a_mkeys = A.take(8 * (size_t)M),
+                 a_reg = A.take((size_t)n), a_work = A.take(4 * (size_t)n), a_adjp = A.take(4 * ((size_t)n + 1)), a_adj = A.take(4 * P.ix.nbr.size());
+    A.end_inputs();
+    const size_t a_patch = A.take((size_t)N), a_kframe = A.take(4 * (size_t)N), a_ptr = A.take(4 * ((size_t)N + 1)), a_ent = A.take(8 * (size_t)M);
+    const size_t a_zero = A.total();                                   // zeroed in one memset: counts, cursors, marks, mark counts, the round words, the error word
+    const size_t a_cnt = A.take(4 * ((size_t)N + 1)), a_cur = A.take(4 * (size_t)N), a_mark = A.take(4 * (size_t)N), a_vis = A.take(4 * (size_t)n),
+                 a_round = A.take(4 * ((size_t)n + 2));
+    const size_t a_zero_bytes = A.total() - a_zero;
+    DevLease blkA;
+    PinLease stage, back;
+    if (!blkA.get(0, A.total()) || !stage.get(A.in_bytes) || !back.get(std::max<size_t>(4 * ((size_t)n + 2), 256))) return XRSFM_BA_ENOMEM;
+    unsigned char* const base = blkA.data();
+    {
+        unsigned char* h = stage.data();
+        memcpy(h + a_first, P.first.data(), 4 * ((size_t)n + 1));
+        int32_t* sz = (int32_t*)(h + a_size);
+        for (int32_t f = 0; f < n; ++f) { sz[2 * f] = in.width[f]; sz[2 * f + 1] = in.height[f]; }
+        if (!in.fs && N > 0) memcpy(h + a_keys, in.keys, 16 * (size_t)N);
+        int32_t* mk = (int32_t*)(h + a_mkeys);
+        for (int32_t p = 0; p < in.n_pairs; ++p)
+            for (int64_t m = in.match_ptr[p]; m < in.match_ptr[p + 1]; ++m) {
+                mk[2 * m] = P.first[(size_t)in.pair_a[p]] + in.matches[2 * m];
+                mk[2 * m + 1] = P.first[(size_t)in.pair_b[p]] + in.matches[2 * m + 1];
+            }
+        memset(h + a_reg, 0, (size_t)n);
+        h[a_reg + (size_t)P.init_first] = 1; h[a_reg + (size_t)P.init_second] = 1;
+        memset(h + a_work, 0, 4 * (size_t)n);
+        ((int32_t*)(h + a_work))[0] = P.init_first;
+        memcpy(h + a_adjp, P.ix.ptr.data(), 4 * ((size_t)n + 1));
+        if (!P.ix.nbr.empty()) memcpy(h + a_adj, P.ix.nbr.data(), 4 * P.ix.nbr.size());
+    }
+    const float4* d_keys = in.fs ? (const float4*)(in.fs->blk.p ? in.fs->blk.at(in.fs->blk.L.o_keys) : nullptr) : (const float4*)(base + a_keys);
+    int32_t* const d_first = (int32_t*)(base + a_first);
+    int32_t* const d_kframe = (int32_t*)(base + a_kframe);
+    int32_t* const d_ptr = (int32_t*)(base + a_ptr);
+    int32_t* const d_ent = (int32_t*)(base + a_ent);
+    int32_t* const d_vis = (int32_t*)(base + a_vis);
+    int32_t* const d_round = (int32_t*)(base + a_round);           // [r]: frames registered by round r; [n + 1]: the error word
+    uint8_t* const d_reg = base + a_reg;
+    int32_t* const d_work = (int32_t*)(base + a_work);
+    auto fail = [&](int code) { (void)hipStreamSynchronize(st); return code; };
+    if (hipMemcpyAsync(base, stage.data(), A.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(base + a_zero, 0, a_zero_bytes, st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    if (timing) { (void)hipStreamSynchronize(st); t_upload += expand_ms(t0); }
+    stamp(0);
+    if (N > 0) hipLaunchKernelGGL(k_expand_patch, dim3((unsigned)cdiv(N, kExpandThreads)), dim3(kExpandThreads), 0, st, n, (int32_t)N, (const int32_t*)d_first,
+                                  (const int2*)(base + a_size), d_keys, o.patch_cols, o.patch_rows, base + a_patch, d_kframe, d_round + n + 1);
+    stamp(1);
+    if (M > 0) hipLaunchKernelGGL(k_expand_count, dim3((unsigned)cdiv(M, kExpandThreads)), dim3(kExpandThreads), 0, st, M, (const int2*)(base + a_mkeys), (int32_t*)(base + a_cnt));
+    DevLease scan_tmp;
+    {
+        size_t q = 0;
+        if (rocprim::exclusive_scan(nullptr, q, (int32_t*)(base + a_cnt), d_ptr, 0, (size_t)N + 1, rocprim::plus<int>(), st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+        if (!scan_tmp.get(0, std::max<size_t>(q, 1))) return fail(XRSFM_BA_ENOMEM);
+        if (rocprim::exclusive_scan(scan_tmp.data(), q, (int32_t*)(base + a_cnt), d_ptr, 0, (size_t)N + 1, rocprim::plus<int>(), st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    }
+    if (M > 0) hipLaunchKernelGGL(k_expand_fill, dim3((unsigned)cdiv(M, kExpandThreads)), dim3(kExpandThreads), 0, st, M, (const int2*)(base + a_mkeys), (const int32_t*)d_ptr,
+                                  (int32_t*)(base + a_cur), d_ent);
+    stamp(2);
+    if (hipGetLastError() != hipSuccess) return fail(XRSFM_BA_ENODEV);
+
+    // ---- the tracks, on the host while the device builds its lists
+    auto t1 = std::chrono::steady_clock::now();
+    const xexpand::Tracks T = xexpand::make_tracks(n, in.key_ptr, in.n_pairs, in.pair_a, in.pair_b, in.match_ptr, in.matches);
+    t_tracks = expand_ms(t1);
+    const int64_t n_tracks = (int64_t)T.invalid.size(), n_obs = (int64_t)T.obs_frame.size();
+    if (n_obs > 0x7fffffff) { fprintf(stderr, "[xrsfm_ba] %s: %lld observations, above INT32_MAX\n", who, (long long)n_obs); return fail(XRSFM_BA_ETOOBIG); }
+
+    // ---- the rounds: one word comes back per round
+    auto t2 = std::chrono::steady_clock::now();
+    int32_t max_keys = 0;
+    for (int32_t f = 0; f < n; ++f) max_keys = std::max(max_keys, P.first[(size_t)f + 1] - P.first[(size_t)f]);
+    const unsigned fire_x = (unsigned)std::max<long long>(cdiv(max_keys, kExpandThreads), 1);
+    int32_t n_new = 1, rounds = 0;
+    for (int32_t r = 0;; ++r) {
+        for (int32_t y0 = 0; y0 < n_new; y0 += 65535)                  // (a grid's y holds 65535)
+            hipLaunchKernelGGL(k_expand_fire, dim3(fire_x, (unsigned)std::min(n_new - y0, 65535)), dim3(kExpandThreads), 0, st, (const int32_t*)d_work + y0, (const int32_t*)d_first,
+                               (const int32_t*)d_ptr, (const int32_t*)d_ent, (const int32_t*)d_kframe, (const uint8_t*)d_reg, (int32_t*)(base + a_mark), d_vis);
+        hipLaunchKernelGGL(k_expand_select, dim3((unsigned)cdiv(n, kExpandThreads)), dim3(kExpandThreads), 0, st, n, o.min_visible, (const int32_t*)d_vis, d_reg, d_work, d_round + r);
+        if (hipGetLastError() != hipSuccess) return fail(XRSFM_BA_ENODEV);
+        if (hipMemcpyAsync(back.data(), d_round + r, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+        n_new = *(const int32_t*)back.data();
+        if (n_new <= 0) break;
+        if (n_new > n || r >= n) return fail(XRSFM_BA_EINTERNAL);      // (every round registers a frame that was not: at most n - 2 rounds)
+        rounds += 1;
+    }
+    out->visible.resize((size_t)n);
+    if (hipMemcpyAsync(back.data(), d_vis, 4 * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(back.data() + 4 * (size_t)n, d_round + n + 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    memcpy(out->visible.data(), back.data(), 4 * (size_t)n);
+    if (*(const int32_t*)(back.data() + 4 * (size_t)n) != 0) return complain(who, "a key point of the set whose patch index is negative or whose coordinate no int holds");
+    t_rounds = expand_ms(t2);
+
+    // ---- block B: the tracks up; the codes of every connected frame
+    auto t3 = std::chrono::steady_clock::now();
+    std::vector<int32_t> list;
+    std::vector<int64_t> code_off((size_t)n + 1, 0);
+    int64_t items_total = 0;
+    for (int32_t f = 0; f < n; ++f) {
+        int64_t room = 0;
+        if (P.connected[(size_t)f]) {
+            list.push_back(f);
+            const int64_t items = xexpand::covis_items(f, P.first.data(), T);
+            items_total += items;
+            room = items / o.min_patch_obs;                            // a code needs min_patch_obs items of its own
+        }
+        code_off[(size_t)f + 1] = code_off[(size_t)f] + room;
+    }
+    const int64_t code_room = code_off[(size_t)n];
+    const int32_t passes = xexpand::window_passes(n, P.window);
+    xstage::Layout B;
+    const size_t b_kt = B.take(4 * (size_t)N), b_tp = B.take(4 * ((size_t)n_tracks + 1)), b_of = B.take(4 * (size_t)n_obs), b_ok = B.take(4 * (size_t)n_obs),
+                 b_list = B.take(4 * list.size()), b_off = B.take(8 * ((size_t)n + 1));
+    B.end_inputs();
+    const size_t b_codes = B.take(4 * (size_t)code_room), b_count = B.take(4 * (size_t)n);
+    DevLease blkB;
+    PinLease stageB;
+    if (!blkB.get(0, B.total()) || !stageB.get(B.in_bytes)) return fail(XRSFM_BA_ENOMEM);
+    unsigned char* const bb = blkB.data();
+    {
+        unsigned char* h = stageB.data();
+        int32_t* kt = (int32_t*)(h + b_kt);
+        for (int64_t k = 0; k < N; ++k) kt[k] = xexpand::valid_track(T, k);
+        int32_t* tp = (int32_t*)(h + b_tp);
+        for (int64_t t = 0; t <= n_tracks; ++t) tp[t] = (int32_t)T.track_ptr[(size_t)t];
+        if (n_obs > 0) memcpy(h + b_of, T.obs_frame.data(), 4 * (size_t)n_obs);
+        int32_t* ok = (int32_t*)(h + b_ok);
+        for (int64_t q = 0; q < n_obs; ++q) ok[q] = P.first[(size_t)T.obs_frame[(size_t)q]] + T.obs_key[(size_t)q];
+        if (!list.empty()) memcpy(h + b_list, list.data(), 4 * list.size());
+        memcpy(h + b_off, code_off.data(), 8 * ((size_t)n + 1));
+    }
+    if (hipMemcpyAsync(bb, stageB.data(), B.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(bb + b_count, 0, std::max<size_t>(4 * (size_t)n, 8), st) != hipSuccess)
+        return fail(XRSFM_BA_ENODEV);
+    if (timing) { (void)hipStreamSynchronize(st); t_upload += expand_ms(t3); }
+    const size_t lds = (size_t)xexpand::window_fixed_bytes(n) + 32 * (size_t)P.window;
+    ExpandCovisArgs ca{};
+    ca.list = (const int32_t*)(bb + b_list); ca.first = d_first; ca.adj_ptr = (const int32_t*)(base + a_adjp); ca.adj = (const int32_t*)(base + a_adj);
+    ca.key_track = (const int32_t*)(bb + b_kt); ca.track_ptr = (const int32_t*)(bb + b_tp); ca.obs_frame = (const int32_t*)(bb + b_of); ca.obs_key = (const int32_t*)(bb + b_ok);
+    ca.patch = base + a_patch; ca.code_off = (const int64_t*)(bb + b_off); ca.codes = (int32_t*)(bb + b_codes); ca.code_count = (int32_t*)(bb + b_count);
+    ca.n_frames = n; ca.window = P.window; ca.patches = patches; ca.min_obs = o.min_patch_obs;
+    stamp(3);
+    if (!list.empty()) {
+        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_expand_covis, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+        hipLaunchKernelGGL(k_expand_covis, dim3((unsigned)list.size()), dim3(kExpandThreads), lds, st, ca);
+    }
+    stamp(4);
+    if (hipGetLastError() != hipSuccess) return fail(XRSFM_BA_ENODEV);
+
+    // ---- block C: the directed candidates up, their two counts back
+    std::vector<int32_t> cand;
+    if (search) {
+        std::vector<uint8_t> registered((size_t)n);
+        for (int32_t f = 0; f < n; ++f) registered[(size_t)f] = out->visible[(size_t)f] >= o.min_visible ? 1 : 0;
+        cand = xexpand::directed_candidates(n, P.rt, P.tried, registered.data(), P.connected.data());
+    }
+    const size_t nd = cand.size() / 2;
+    xstage::Layout C;
+    const size_t c_cand = C.take(8 * nd);
+    C.end_inputs();
+    C.begin_outputs();
+    const size_t c_out = C.take(8 * nd), c_count = C.take(4 * (size_t)n);
+    C.end_outputs();
+    DevLease blkC;
+    PinLease stageC, backC;
+    if (!blkC.get(0, C.total()) || !stageC.get(C.in_bytes) || !backC.get(C.out_bytes + (want_codes ? 4 * (size_t)code_room : 0))) return fail(XRSFM_BA_ENOMEM);
+    unsigned char* const cb = blkC.data();
+    if (nd) memcpy(stageC.data() + c_cand, cand.data(), 8 * nd);
+    if (hipMemcpyAsync(cb, stageC.data(), C.in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    stamp(5);
+    if (nd) {
+        ExpandPairsArgs pa{};
+        pa.cand = (const int2*)(cb + c_cand); pa.first = d_first; pa.key_track = ca.key_track; pa.track_ptr = ca.track_ptr; pa.obs_frame = ca.obs_frame;
+        pa.code_off = ca.code_off; pa.codes = ca.codes; pa.code_count = ca.code_count; pa.out = (int2*)(cb + c_out); pa.n_cand = (int32_t)nd;
+        hipLaunchKernelGGL(k_expand_pairs, dim3((unsigned)cdiv((long long)nd, kExpandThreads / kExpandWave)), dim3(kExpandThreads), 0, st, pa);
+    }
+    stamp(6);
+    if (hipGetLastError() != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    auto t4 = std::chrono::steady_clock::now();
+    if (hipMemcpyAsync(cb + c_count, bb + b_count, 4 * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(backC.data(), cb + C.out0, C.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    if (want_codes && code_room > 0 && hipMemcpyAsync(backC.data() + C.out_bytes, bb + b_codes, 4 * (size_t)code_room, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(XRSFM_BA_ENODEV);
+    if (hipStreamSynchronize(st) != hipSuccess) return XRSFM_BA_ENODEV;
+    t_back = expand_ms(t4);
+    const xstage::View view{backC.data(), C.out0};
+    const int32_t* cnt = view.at<int32_t>(c_count);
+    const int32_t* pc = view.at<int32_t>(c_out);
+    out->cand.resize(4 * nd);
+    for (size_t c = 0; c < nd; ++c) { out->cand[4 * c] = cand[2 * c]; out->cand[4 * c + 1] = cand[2 * c + 1]; out->cand[4 * c + 2] = pc[2 * c]; out->cand[4 * c + 3] = pc[2 * c + 1]; }
+    int64_t kept = 0;
+    for (int32_t f = 0; f < n; ++f) {
+        if (cnt[f] < 0 || cnt[f] > code_off[(size_t)f + 1] - code_off[(size_t)f]) return XRSFM_BA_EINTERNAL;
+        kept += cnt[f];
+    }
+    if (want_codes) {
+        const int32_t* all = (const int32_t*)(backC.data() + C.out_bytes);
+        out->code_ptr.assign((size_t)n + 1, 0);
+        out->codes.clear();
+        for (int32_t f = 0; f < n; ++f) {
+            out->codes.insert(out->codes.end(), all + code_off[(size_t)f], all + code_off[(size_t)f] + cnt[f]);
+            out->code_ptr[(size_t)f + 1] = (int64_t)out->codes.size();
+        }
+    }
+    const int64_t stats[8] = {rounds, n_tracks, T.valid_tracks, 2 * M, items_total, kept, passes, 0};
+    memcpy(out->stats, stats, sizeof(stats));
+    if (timing)
+        fprintf(stderr, "[xrsfm_ba] expand timing: tracks %.4f ms, uploads %.4f ms, patch %.4f ms, lists %.4f ms, rounds %.4f ms (%d), covis %.4f ms, pairs %.4f ms, back %.4f ms\n",
+                t_tracks, t_upload, between(0, 1), between(1, 2), t_rounds, rounds, between(3, 4), between(5, 6), t_back);
+    return XRSFM_BA_OK;
+}
+
+int expand_impl(ExpandIn in, int64_t capacity, int64_t* n_out, int32_t* out_a, int32_t* out_b, uint8_t* out_source, uint8_t* connected, uint8_t* registered,
+                uint8_t* may_register, int32_t* visible, int64_t cand_capacity, int64_t* n_cand, int32_t* cand, int64_t* stats) {
+    const char* who = in.who;
+    in.with_frames = in.with_search = true;
+    if (in.fs) { in.n_frames = in.fs->n_frames; in.key_ptr = in.fs->key_ptr.data(); in.keys = nullptr; }
+    if (!n_out) return complain(who, "NULL n_out");
+    if (capacity < 0 || (capacity > 0 && (!out_a || !out_b || !out_source))) return complain(who, "negative capacity, or NULL out_a, out_b or out_source with one");
+    if (cand && (cand_capacity < 0 || !n_cand)) return complain(who, "negative cand_capacity or NULL n_cand");
+    ExpandPrep P;
+    if (int e = expand_check(in, &P)) return e;
+    if (in.n_frames == 0) { *n_out = 0; if (cand) *n_cand = 0; if (stats) memset(stats, 0, 8 * sizeof(int64_t)); return XRSFM_BA_OK; }
+    ExpandDevOut D;
+    if (int e = expand_device(in, P, true, false, &D)) return e;
+    xexpand::Result R;
+    const int64_t nd = (int64_t)D.cand.size() / 4;
+    xexpand::finish(in.n_frames, P.o, P.rt, P.tried, P.connected.data(), D.visible.data(), D.cand.data(), nd, &R);
+    if ((int64_t)R.out_a.size() > capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: capacity %lld is below the %lld pairs of the call\n", who, (long long)capacity, (long long)R.out_a.size());
+        return XRSFM_BA_EINVAL;
+    }
+    if (cand && nd > cand_capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: cand_capacity %lld is below the %lld directed candidates of the call\n", who, (long long)cand_capacity, (long long)nd);
+        return XRSFM_BA_EINVAL;
+    }
+    const size_t n = (size_t)in.n_frames, no = R.out_a.size();
+    *n_out = (int64_t)no;
+    if (no) { memcpy(out_a, R.out_a.data(), 4 * no); memcpy(out_b, R.out_b.data(), 4 * no); memcpy(out_source, R.out_source.data(), no); }
+    if (connected) memcpy(connected, P.connected.data(), n);
+    if (registered) memcpy(registered, R.registered.data(), n);
+    if (may_register) memcpy(may_register, R.may_register.data(), n);
+    if (visible) memcpy(visible, D.visible.data(), 4 * n);
+    if (cand) { *n_cand = nd; if (nd) memcpy(cand, D.cand.data(), 16 * (size_t)nd); }
+    if (stats) memcpy(stats, D.stats, sizeof(D.stats));
+    return XRSFM_BA_OK;
+}
+
+int debug_expand_tracks_impl(ExpandIn in, int32_t* key_track, int64_t track_capacity, int64_t* n_tracks, int64_t* track_ptr, uint8_t* invalid, int64_t obs_capacity,
+                             int64_t* n_obs, int32_t* obs_frame, int32_t* obs_key) {
+    const char* who = in.who;
+    in.with_frames = in.with_search = false;
+    if (!n_tracks || !n_obs || !track_ptr) return complain(who, "NULL n_tracks, n_obs or track_ptr");
+    if (track_capacity < 0 || obs_capacity < 0) return complain(who, "negative capacity");
+    ExpandPrep P;
+    if (int e = expand_check(in, &P)) return e;
+    if (in.n_frames == 0) { *n_tracks = 0; *n_obs = 0; track_ptr[0] = 0; return XRSFM_BA_OK; }
+    if (P.n_keys > 0 && !key_track) return complain(who, "NULL key_track");
+    const xexpand::Tracks T = xexpand::make_tracks(in.n_frames, in.key_ptr, in.n_pairs, in.pair_a, in.pair_b, in.match_ptr, in.matches);
+    const int64_t nt = (int64_t)T.invalid.size(), no = (int64_t)T.obs_frame.size();
+    if (nt > track_capacity || no > obs_capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: capacities %lld and %lld are below the %lld tracks and %lld observations of the call\n", who, (long long)track_capacity,
+                (long long)obs_capacity, (long long)nt, (long long)no);
+        return XRSFM_BA_EINVAL;
+    }
+    if ((nt > 0 && !invalid) || (no > 0 && (!obs_frame || !obs_key))) return complain(who, "NULL invalid, obs_frame or obs_key");
+    if (P.n_keys > 0) memcpy(key_track, T.key_track.data(), 4 * (size_t)P.n_keys);
+    *n_tracks = nt; *n_obs = no;
+    memcpy(track_ptr, T.track_ptr.data(), 8 * ((size_t)nt + 1));
+    if (nt) memcpy(invalid, T.invalid.data(), (size_t)nt);
+    if (no) { memcpy(obs_frame, T.obs_frame.data(), 4 * (size_t)no); memcpy(obs_key, T.obs_key.data(), 4 * (size_t)no); }
+    return XRSFM_BA_OK;
+}
+
+int debug_expand_covis_impl(ExpandIn in, int64_t code_capacity, int64_t* code_ptr, int32_t* codes) {
+    const char* who = in.who;
+    in.with_frames = true; in.with_search = false;
+    if (!code_ptr) return complain(who, "NULL code_ptr");
+    if (code_capacity < 0 || (code_capacity > 0 && !codes)) return complain(who, "negative capacity, or NULL codes with one");
+    ExpandPrep P;
+    if (int e = expand_check(in, &P)) return e;
+    if (in.n_frames == 0) { code_ptr[0] = 0; return XRSFM_BA_OK; }
+    ExpandDevOut D;
+    if (int e = expand_device(in, P, false, true, &D)) return e;
+    if ((int64_t)D.codes.size() > code_capacity) {
+        fprintf(stderr, "[xrsfm_ba] %s: code_capacity %lld is below the %lld codes of the call\n", who, (long long)code_capacity, (long long)D.codes.size());
+        return XRSFM_BA_EINVAL;
+    }
+    memcpy(code_ptr, D.code_ptr.data(), 8 * ((size_t)in.n_frames + 1));
+    if (!D.codes.empty()) memcpy(codes, D.codes.data(), 4 * D.codes.size());
+    return XRSFM_BA_OK;
+}
+}  // namespace
+
+int xrsfm_ba_expand_candidates(const xrsfm_ba_expand_options* opt, int32_t n_frames, const int64_t* key_ptr, const float* keys, const int32_t* width, const int32_t* height,
+                               int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* match_ptr, const int32_t* matches, const int64_t* rank_ptr,
+                               const int32_t* rank_ids, int32_t n_tried, const int32_t* tried_a, const int32_t* tried_b, int32_t init_a, int32_t init_b, int64_t capacity,
+                               int64_t* n_out, int32_t* out_a, int32_t* out_b, uint8_t* out_source, uint8_t* connected, uint8_t* registered, uint8_t* may_register,
+                               int32_t* visible, int64_t cand_capacity, int64_t* n_cand, int32_t* cand, int64_t* stats) {
+    const ExpandIn in{"xrsfm_ba_expand_candidates", opt, n_frames, key_ptr, keys, nullptr, width, height, n_pairs, pair_a, pair_b, match_ptr, matches, rank_ptr, rank_ids,
+                      n_tried, tried_a, tried_b, init_a, init_b, true, true};
+    return no_throw([&] { return expand_impl(in, capacity, n_out, out_a, out_b, out_source, connected, registered, may_register, visible, cand_capacity, n_cand, cand, stats); });
+}
+
+int xrsfm_ba_frames_expand(const xrsfm_ba_frames* fs, const xrsfm_ba_expand_options* opt, const int32_t* width, const int32_t* height, int32_t n_pairs, const int32_t* pair_a,
+                           const int32_t* pair_b, const int64_t* match_ptr, const int32_t* matches, const int64_t* rank_ptr, const int32_t* rank_ids, int32_t n_tried,
+                           const int32_t* tried_a, const int32_t* tried_b, int32_t init_a, int32_t init_b, int64_t capacity, int64_t* n_out, int32_t* out_a, int32_t* out_b,
+                           uint8_t* out_source, uint8_t* connected, uint8_t* registered, uint8_t* may_register, int32_t* visible, int64_t cand_capacity, int64_t* n_cand,
+                           int32_t* cand, int64_t* stats) {
+    if (!fs) return complain("xrsfm_ba_frames_expand", "NULL frame set");
+    const ExpandIn in{"xrsfm_ba_frames_expand", opt, 0, nullptr, nullptr, fs, width, height, n_pairs, pair_a, pair_b, match_ptr, matches, rank_ptr, rank_ids,
+                      n_tried, tried_a, tried_b, init_a, init_b, true, true};
+    return no_throw([&] { return expand_impl(in, capacity, n_out, out_a, out_b, out_source, connected, registered, may_register, visible, cand_capacity, n_cand, cand, stats); });
+}
+
+int xrsfm_ba_debug_expand_tracks(int32_t n_frames, const int64_t* key_ptr, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* match_ptr,
+                                 const int32_t* matches, int32_t* key_track, int64_t track_capacity, int64_t* n_tracks, int64_t* track_ptr, uint8_t* invalid,
+                                 int64_t obs_capacity, int64_t* n_obs, int32_t* obs_frame, int32_t* obs_key) {
+    const ExpandIn in{"xrsfm_ba_debug_expand_tracks", nullptr, n_frames, key_ptr, nullptr, nullptr, nullptr, nullptr, n_pairs, pair_a, pair_b, match_ptr, matches, nullptr, nullptr,
+                      0, nullptr, nullptr, 0, 0, false, false};
+    return no_throw([&] { return debug_expand_tracks_impl(in, key_track, track_capacity, n_tracks, track_ptr, invalid, obs_capacity, n_obs, obs_frame, obs_key); });
+}
+
+int xrsfm_ba_debug_expand_covis(const xrsfm_ba_expand_options* opt, int32_t n_frames, const int64_t* key_ptr, const float* keys, const int32_t* width, const int32_t* height,
+                                int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* match_ptr, const int32_t* matches, int32_t init_a, int32_t init_b,
+                                int64_t code_capacity, int64_t* code_ptr, int32_t* codes) {
+    const ExpandIn in{"xrsfm_ba_debug_expand_covis", opt, n_frames, key_ptr, keys, nullptr, width, height, n_pairs, pair_a, pair_b, match_ptr, matches, nullptr, nullptr,
+                      0, nullptr, nullptr, init_a, init_b, true, false};
+    return no_throw([&] { return debug_expand_covis_impl(in, code_capacity, code_ptr, codes); });
 }
 
 // ---------------------------------------------------------------- diagnostics
