@@ -1040,6 +1040,62 @@ int xrsfm_ba_frames_expand(const xrsfm_ba_frames *fs, const xrsfm_ba_expand_opti
                            uint8_t *connected, uint8_t *registered, uint8_t *may_register, int32_t *visible,
                            int64_t cand_capacity, int64_t *n_cand, int32_t *cand, int64_t *stats);
 
+/* ---- track completion and merging ----
+ * Point3dProcessor::ContinueTrack and MergeTrack over every track (run_triangulation.cc:151-164) or MergeTracks(frame) of the
+ * incremental mapper (incremental_mapper.cc:65-66; track_processor.cc:426-618), on three flat arrays that are read and written:
+ * track_of_key [N] (Frame::track_ids_, frame-major as key_ptr; -1: none), points [n_tracks][3], track_outlier [n_tracks].  No track
+ * is created.  One wave per connected component (key points; edges: correspondence entries and "same track") runs the reference's
+ * own sequential program, so a track's and a key point's outputs do not depend on what else is in the call: the call may be given
+ * any union of whole components of a map.
+ *
+ * Inputs: key_ptr [n_frames+1], key_xy [N][2] pixels; per frame registered (0 / 1), cam_q [n_frames][4] (x, y, z, w), cam_t
+ * [n_frames][3], cam_intr (its camera); n_intr cameras with intr_model (0..4) and intr_params [n_intr][8] as in xrsfm_ba_problem;
+ * corr_ptr [N+1] and corr_key [E]: the correspondence list of every key point in stored order, entries as global key indices
+ * (CorrespondenceGraph::corrs_vector; symmetric, never into the key point's own frame).
+ *
+ * Outputs besides the three arrays, each may be NULL: track_status [n_tracks] (0 not in a processed component, 1 processed and
+ * alive, 2 merged away, 3 in a component above the limits: such a component is not attempted and its state stays bit for bit);
+ * corr_have_point3d [N] (the entries of a key point's list whose key point carries a track), visible [n_frames] (key points with
+ * such an entry), measured [n_frames] (key points that carry a track), all three of the final state; stats [8]: merged tracks,
+ * connected tracks, continued measurements, connected measurements (the counters MergeTracks prints), components processed,
+ * components above the limits, key points of the largest processed component, 0.  Map modes process every component that holds
+ * a track; frame mode those that hold a key point of the frame with a track.
+ *
+ * Errors: every check runs on the host before the device is touched and prints one line on stderr that names the entry; on any
+ * negative code no output is touched.  XRSFM_BA_EINVAL: NULL opt or needed array; offsets not starting at 0 or decreasing; a key
+ * or track index out of range; a key point carrying an outlier track; two key points of one frame on one track; a list entry
+ * pointing into the key point's own frame; a non-symmetric list; a non-finite pose, point, coordinate or parameter;
+ * max_reproj_error not positive; a mode outside {1, 2, 3, 4}; in frame mode a frame out of range or not registered; a model
+ * outside 0..4.  XRSFM_BA_ETOOBIG: key points or entries above INT32_MAX.  Nothing to do (no key point, no track, or frame mode
+ * on a frame without a track) is success and needs no device; otherwise XRSFM_BA_ENODEV without one (no CPU path). */
+#define XRSFM_BA_MERGE_CONTINUE 1   /* ContinueTrack over every track                */
+#define XRSFM_BA_MERGE_MERGE    2   /* MergeTrack over every track (3 = both, in the reference's order) */
+#define XRSFM_BA_MERGE_FRAME    4   /* MergeTracks(frame)                             */
+#define XRSFM_BA_MERGE_MAX_KEYS 1024   /* key points of a component k_merge_components attempts */
+#define XRSFM_BA_MERGE_MAX_TRACKS 512  /* tracks of such a component                            */
+typedef struct {
+    double max_reproj_error;       /* 8.0  pixels (th_rpe_lba in the mapper)                      */
+    int32_t mode;                  /* 3    XRSFM_BA_MERGE_*                                       */
+    int32_t frame;                 /* -1   the frame of XRSFM_BA_MERGE_FRAME                      */
+} xrsfm_ba_merge_options;
+void xrsfm_ba_merge_options_default(xrsfm_ba_merge_options *opt);   /* 8.0, 3, -1: run_triangulation */
+
+int xrsfm_ba_merge_tracks(const xrsfm_ba_merge_options *opt, int32_t n_frames, const int64_t *key_ptr, const double *key_xy,
+                          const uint8_t *registered, const double *cam_q, const double *cam_t, const int32_t *cam_intr,
+                          int32_t n_intr, const int32_t *intr_model, const double *intr_params, const int64_t *corr_ptr,
+                          const int32_t *corr_key, int32_t n_tracks, double *points, uint8_t *track_outlier,
+                          int32_t *track_of_key, uint8_t *track_status, int32_t *corr_have_point3d, int32_t *visible,
+                          int32_t *measured, int64_t *stats);
+
+/* TEST ENTRY, host only (needs no device).  The host's labelling of the components: comp_of_key [N], components numbered by size
+ * (largest first, then by first key point), and their number.  Inputs and checks as in xrsfm_ba_merge_tracks. */
+int xrsfm_ba_debug_merge_components(const xrsfm_ba_merge_options *opt, int32_t n_frames, const int64_t *key_ptr,
+                                    const double *key_xy, const uint8_t *registered, const double *cam_q, const double *cam_t,
+                                    const int32_t *cam_intr, int32_t n_intr, const int32_t *intr_model,
+                                    const double *intr_params, const int64_t *corr_ptr, const int32_t *corr_key,
+                                    int32_t n_tracks, const double *points, const uint8_t *track_outlier,
+                                    const int32_t *track_of_key, int32_t *comp_of_key, int32_t *n_comp);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

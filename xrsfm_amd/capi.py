@@ -122,6 +122,10 @@ class CExpandOptions(C.Structure):
                                          "similarity_rank_max", "mayreg_rank_lo", "mayreg_rank_mid", "mayreg_rank_hi", "mayreg_count_mid", "mayreg_count_sum")]
 
 
+class CMergeOptions(C.Structure):
+    _fields_ = [("max_reproj_error", C.c_double), ("mode", C.c_int32), ("frame", C.c_int32)]
+
+
 # every symbol include/xrsfm_ba.h declares
 EXPORTS = [
     "xrsfm_ba_default_options", "xrsfm_ba_version", "xrsfm_ba_create", "xrsfm_ba_comm_unique_id",
@@ -145,6 +149,7 @@ EXPORTS = [
     "xrsfm_ba_frames_destroy",
     "xrsfm_ba_expand_options_default", "xrsfm_ba_expand_candidates", "xrsfm_ba_frames_expand", "xrsfm_ba_debug_expand_tracks",
     "xrsfm_ba_debug_expand_covis",
+    "xrsfm_ba_merge_options_default", "xrsfm_ba_merge_tracks", "xrsfm_ba_debug_merge_components",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -371,6 +376,15 @@ def load(path: str | None = None):
     lib.xrsfm_ba_debug_expand_covis.argtypes = [_eo, C.c_int32, _c_int64_p, _c_float_p, _c_int32_p, _c_int32_p, C.c_int32, _c_int32_p, _c_int32_p, _c_int64_p, _c_int32_p,
                                                 C.c_int32, C.c_int32, C.c_int64, _c_int64_p, _c_int32_p]
     lib.xrsfm_ba_debug_expand_covis.restype = C.c_int
+    _mo = C.POINTER(CMergeOptions)
+    _merge_head = [_mo, C.c_int32, _c_int64_p, _c_double_p, _c_uint8_p, _c_double_p, _c_double_p, _c_int32_p, C.c_int32, _c_int32_p, _c_double_p, _c_int64_p, _c_int32_p,
+                   C.c_int32, _c_double_p, _c_uint8_p, _c_int32_p]
+    lib.xrsfm_ba_merge_options_default.argtypes = [_mo]
+    lib.xrsfm_ba_merge_options_default.restype = None
+    lib.xrsfm_ba_merge_tracks.argtypes = _merge_head + [_c_uint8_p, _c_int32_p, _c_int32_p, _c_int32_p, _c_int64_p]
+    lib.xrsfm_ba_merge_tracks.restype = C.c_int
+    lib.xrsfm_ba_debug_merge_components.argtypes = _merge_head + [_c_int32_p, _c_int32_p]
+    lib.xrsfm_ba_debug_merge_components.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1816,3 +1830,129 @@ def debug_sift_describe(image, options: CSiftOptions | None = None, desc_options
     check(code, "xrsfm_ba_debug_sift_describe")
     m = n.value
     return dict(loc=l[:m].copy(), okeys=k[:m].copy(), raw=r[:m].copy(), unit=u[:m].copy())
+
+
+# ---------------------------------------------------------------------------------------------------- track completion and merging
+MERGE_CONTINUE, MERGE_MERGE, MERGE_FRAME = 1, 2, 4
+MERGE_MAX_KEYS, MERGE_MAX_TRACKS = 1024, 512   # XRSFM_BA_MERGE_MAX_KEYS / _TRACKS: the largest component that is attempted
+MERGE_STATS = ("merged", "connected_tracks", "continued", "connected_measurements", "components", "skipped", "largest")
+
+
+def merge_options(**overrides) -> CMergeOptions:
+    """xrsfm_ba_merge_options_default: 8.0 px, ContinueTrack then MergeTrack over every track (run_triangulation)."""
+    o = CMergeOptions()
+    load().xrsfm_ba_merge_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class _MergeArgs:
+    """the inputs the two merge entries share, kept alive for the call"""
+
+    def __init__(self, name, key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, intr_model, intr_params, corr_ptr, corr_key, points, track_outlier, track_of_key, options):
+        c = np.ascontiguousarray
+        self.o = options if options is not None else merge_options()
+        self.key_ptr = c(key_ptr, np.int64).reshape(-1)
+        self.n = len(self.key_ptr) - 1
+        self.xy = c(key_xy, np.float64).reshape(-1, 2)
+        self.reg, self.q, self.t = c(registered, np.uint8).reshape(-1), c(cam_q, np.float64).reshape(-1, 4), c(cam_t, np.float64).reshape(-1, 3)
+        self.ci, self.im, self.ip = c(cam_intr, np.int32).reshape(-1), c(intr_model, np.int32).reshape(-1), c(intr_params, np.float64).reshape(-1, 8)
+        self.cp = c(corr_ptr, np.int64).reshape(-1) if len(self.xy) else np.zeros(1, np.int64)
+        self.ck = c(corr_key, np.int32).reshape(-1)
+        self.points = np.array(points, np.float64, order="C").reshape(-1, 3)             # copies: the call writes them
+        self.outlier = np.array(track_outlier, np.uint8).reshape(-1)
+        self.tok = np.array(track_of_key, np.int32).reshape(-1)
+        N = len(self.xy)
+        if self.n < 0 or len(self.reg) != self.n or len(self.q) != self.n or len(self.t) != self.n or len(self.ci) != self.n or len(self.im) != len(self.ip) or \
+                len(self.tok) != N or len(self.cp) != N + 1 or len(self.outlier) != len(self.points) or (N and (self.key_ptr[-1] != N or self.cp[-1] != len(self.ck))):
+            raise ValueError(name + ": inconsistent array lengths")
+
+    def head(self):
+        lp, ip, up = (lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))), (lambda a: a.ctypes.data_as(_c_int32_p)), (lambda a: a.ctypes.data_as(_c_uint8_p))
+        return [C.byref(self.o), self.n, lp(self.key_ptr), _dp(self.xy), up(self.reg), _dp(self.q), _dp(self.t), ip(self.ci), len(self.im), ip(self.im), _dp(self.ip),
+                lp(self.cp), ip(self.ck), len(self.points), _dp(self.points), up(self.outlier), ip(self.tok)]
+
+
+def merge_tracks(key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, intr_model, intr_params, corr_ptr, corr_key, points, track_outlier, track_of_key,
+                 options: CMergeOptions | None = None) -> dict:
+    """xrsfm_ba_merge_tracks: ContinueTrack / MergeTrack over every track, or MergeTracks(frame), by options.mode.  The three state
+    arrays are not changed; the result holds their new values (points, track_outlier, track_of_key) and track_status,
+    corr_have_point3d [N], visible and measured [n_frames], stats."""
+    a = _MergeArgs("merge_tracks", key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, intr_model, intr_params, corr_ptr, corr_key, points, track_outlier, track_of_key,
+                   options)
+    status, have = np.zeros(len(a.points), np.uint8), np.zeros(len(a.tok), np.int32)
+    vis, mea, stats = np.zeros(a.n, np.int32), np.zeros(a.n, np.int32), np.zeros(8, np.int64)
+    ip = lambda x: x.ctypes.data_as(_c_int32_p)
+    check(load().xrsfm_ba_merge_tracks(*a.head(), status.ctypes.data_as(_c_uint8_p), ip(have), ip(vis), ip(mea), stats.ctypes.data_as(C.POINTER(C.c_int64))),
+          "xrsfm_ba_merge_tracks")
+    return dict(points=a.points, track_outlier=a.outlier, track_of_key=a.tok, track_status=status, corr_have_point3d=have, visible=vis, measured=mea,
+                stats=dict(zip(MERGE_STATS, (int(x) for x in stats))))
+
+
+def debug_merge_components(key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, intr_model, intr_params, corr_ptr, corr_key, points, track_outlier, track_of_key,
+                           options: CMergeOptions | None = None) -> tuple:
+    """xrsfm_ba_debug_merge_components (no GPU): (comp_of_key [N], number of components), largest component first."""
+    a = _MergeArgs("debug_merge_components", key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, intr_model, intr_params, corr_ptr, corr_key, points, track_outlier,
+                   track_of_key, options)
+    comp, n = np.zeros(len(a.tok), np.int32), C.c_int32(0)
+    check(load().xrsfm_ba_debug_merge_components(*a.head(), comp.ctypes.data_as(_c_int32_p), C.byref(n)), "xrsfm_ba_debug_merge_components")
+    return comp, int(n.value)
+
+
+def _csr_entries(ptr, rows):
+    """the entries ptr[r] .. ptr[r + 1] of every row in rows, behind one another"""
+    cnt = ptr[rows + 1] - ptr[rows]
+    if cnt.sum() == 0:
+        return np.zeros(0, np.int64)
+    return np.repeat(ptr[rows] - np.concatenate([[0], np.cumsum(cnt)[:-1]]), cnt) + np.arange(cnt.sum())
+
+
+def correspondence_graph(key_ptr, pair_a, pair_b, match_ptr, matches) -> tuple:
+    """The lists of Map::Init (src/base/map.cc:55-83) as a CSR over global key indices, in its insertion order: pairs in list order,
+    a pair's matches in order, each match appended to both key points' lists.  matches [M][2]: the inliers alone.  -> (corr_ptr, corr_key)"""
+    key_ptr = np.asarray(key_ptr, np.int64).reshape(-1)
+    pa, pb = np.asarray(pair_a, np.int64).reshape(-1), np.asarray(pair_b, np.int64).reshape(-1)
+    mp, m = np.asarray(match_ptr, np.int64).reshape(-1), np.asarray(matches, np.int64).reshape(-1, 2)
+    N = int(key_ptr[-1])
+    pair_of = np.repeat(np.arange(len(pa)), np.diff(mp)) if len(pa) else np.zeros(0, np.int64)
+    ka, kb = key_ptr[pa[pair_of]] + m[:, 0], key_ptr[pb[pair_of]] + m[:, 1]
+    src, dst = np.stack([ka, kb], axis=1).reshape(-1), np.stack([kb, ka], axis=1).reshape(-1)
+    order = np.argsort(src, kind="stable")
+    ptr = np.zeros(N + 1, np.int64)
+    np.cumsum(np.bincount(src, minlength=N), out=ptr[1:])
+    return ptr, dst[order].astype(np.int32)
+
+
+def merge_closure(frame: int, key_ptr, corr_ptr, corr_key, track_of_key) -> dict:
+    """The sub-map made of the whole components (key points; edges: list entries and "same track") that hold a key point of `frame`
+    with a track: what xrsfm_ba_merge_tracks processes in frame mode on that frame.  -> keys (the global key indices, ascending),
+    tracks (the global track ids, ascending), and the sub-map's key_ptr (every frame kept), corr_ptr, corr_key and track_of_key in
+    its own indices.  A caller gathers key_xy[keys], points[tracks] and track_outlier[tracks], calls merge_tracks, and scatters
+    track_of_key (through tracks), points and outliers back."""
+    key_ptr, cp = np.asarray(key_ptr, np.int64).reshape(-1), np.asarray(corr_ptr, np.int64).reshape(-1)
+    ck, tok = np.asarray(corr_key, np.int64).reshape(-1), np.asarray(track_of_key, np.int64).reshape(-1)
+    N = len(tok)
+    inside, track_in = np.zeros(N, bool), np.zeros(int(tok.max()) + 2 if N else 1, bool)
+    front = np.arange(key_ptr[frame], key_ptr[frame + 1])
+    front = front[tok[front] >= 0]
+    while len(front):
+        inside[front] = True
+        t = np.unique(tok[front][tok[front] >= 0])
+        t = t[~track_in[t]]
+        track_in[t] = True
+        same = np.nonzero(np.isin(tok, t))[0] if len(t) else np.zeros(0, np.int64)
+        front = np.unique(np.concatenate([ck[_csr_entries(cp, front)], same]))
+        front = front[~inside[front]]
+    keys = np.nonzero(inside)[0]
+    local = np.full(N, -1, np.int64)
+    local[keys] = np.arange(len(keys))
+    tracks = np.nonzero(track_in)[0]
+    tlocal = np.full(len(track_in), -1, np.int64)
+    tlocal[tracks] = np.arange(len(tracks))
+    sub_ptr = np.concatenate([[0], np.cumsum(cp[keys + 1] - cp[keys])]).astype(np.int64)
+    sub_tok = np.where(tok[keys] >= 0, tlocal[np.maximum(tok[keys], 0)], -1).astype(np.int32)
+    return dict(keys=keys, tracks=tracks, key_ptr=np.searchsorted(keys, key_ptr).astype(np.int64), corr_ptr=sub_ptr,
+                corr_key=local[ck[_csr_entries(cp, keys)]].astype(np.int32), track_of_key=sub_tok)

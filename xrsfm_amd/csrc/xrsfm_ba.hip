@@ -30,6 +30,7 @@
 #include "ba_chol.h"
 #include "ba_cov.h"
 #include "ba_expand.h"
+#include "ba_merge.h"
 #include "ba_filter.h"
 #include "ba_kernels.h"
 #include "ba_lba.h"
@@ -5857,6 +5858,168 @@ int xrsfm_ba_debug_expand_covis(const xrsfm_ba_expand_options* opt, int32_t n_fr
     const ExpandIn in{"xrsfm_ba_debug_expand_covis", opt, n_frames, key_ptr, keys, nullptr, width, height, n_pairs, pair_a, pair_b, match_ptr, matches, nullptr, nullptr,
                       0, nullptr, nullptr, init_a, init_b, true, false};
     return no_throw([&] { return debug_expand_covis_impl(in, code_capacity, code_ptr, codes); });
+}
+
+// ---------------------------------------------------------------- track completion and merging (ba_merge.h)
+static_assert(sizeof(xrsfm_ba_merge_options) == sizeof(xmerge::Opt), "xmerge::Opt mirrors xrsfm_ba_merge_options field for field");
+static_assert(XRSFM_BA_MERGE_MAX_KEYS == xmerge::kMaxKeys && XRSFM_BA_MERGE_MAX_TRACKS == xmerge::kMaxTracks, "the limits of k_merge_components");
+static_assert(sizeof(xmerge::Cam) == 128, "a frame's record is uploaded as it stands");
+
+void xrsfm_ba_merge_options_default(xrsfm_ba_merge_options* opt) {
+    if (!opt) return;
+    const xmerge::Opt o = xmerge::default_options();            // run_triangulation.cc:151-164: 8.0, ContinueTrack then MergeTrack over every track
+    memcpy(opt, &o, sizeof(o));
+}
+
+namespace {
+// every check of the two entries, on the host
+int merge_check(const char* who, const xmerge::In& in, std::vector<int32_t>* frame_of_key) {
+    bool too_big = false;
+    if (const char* fault = xmerge::fault(in, frame_of_key, &too_big)) {
+        if (!too_big) return complain(who, fault);
+        fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, fault);
+        return XRSFM_BA_ETOOBIG;
+    }
+    return XRSFM_BA_OK;
+}
+
+int merge_tracks_impl(const xmerge::In& in, double* points, uint8_t* track_outlier, int32_t* track_of_key, uint8_t* track_status, int32_t* corr_have_point3d, int32_t* visible,
+                      int32_t* measured, int64_t* stats) {
+    const char* who = "xrsfm_ba_merge_tracks";
+    const bool timing = getenv("XRSFM_BA_MERGE_TIMING") != nullptr;
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::vector<int32_t> frame_of_key;
+    if (int e = merge_check(who, in, &frame_of_key)) return e;
+    const xmerge::Opt o = *in.opt;
+    const int32_t n = in.n_frames, T = in.n_tracks;
+    const int64_t N = in.key_ptr[n];
+    auto finish_without_device = [&] {         // nothing to do: the state stands, the counts follow from it
+        if (track_status && T > 0) memset(track_status, 0, (size_t)T);
+        if (N > 0) xmerge::counts_host(in, track_of_key, corr_have_point3d, visible, measured);
+        else { if (visible && n > 0) memset(visible, 0, sizeof(int32_t) * (size_t)n); if (measured && n > 0) memset(measured, 0, sizeof(int32_t) * (size_t)n); }
+        if (stats) memset(stats, 0, sizeof(int64_t) * 8);
+        return XRSFM_BA_OK;
+    };
+    if (N == 0 || T == 0) return finish_without_device();
+    if (o.mode == xmerge::kFrame) {
+        bool any = false;
+        for (int64_t k = in.key_ptr[o.frame]; k < in.key_ptr[o.frame + 1] && !any; ++k) any = track_of_key[k] >= 0;
+        if (!any) return finish_without_device();
+    }
+    if (int e = require_device("track merge")) return e;
+    const xmerge::Labels lab = xmerge::label_components(in);
+    const xmerge::Plan P = xmerge::make_plan(in, frame_of_key, lab);
+    const size_t NK = P.key_glob.size(), NT = P.trk_glob.size(), NE = P.lidx.size(), E = (size_t)in.corr_ptr[N];
+    std::vector<xmerge::Cam> cams((size_t)n);
+    for (int32_t f = 0; f < n; ++f) cams[(size_t)f] = xmerge::cam_of(in, f);
+    const double ms_host = expand_ms(t_begin);
+    HIPCHK(hipSetDevice(0));
+    // one block, one upload, the two launches, one read-back (staged_call)
+    xstage::Layout L;
+    const size_t i32 = sizeof(int32_t);
+    const size_t o_key0 = L.take(i32 * ((size_t)P.n_comp + 1)), o_trk0 = L.take(i32 * ((size_t)P.n_comp + 1)), o_seed = L.take(i32 * 2 * (size_t)P.n_comp),
+                 o_kglob = L.take(i32 * NK), o_kframe = L.take(i32 * NK), o_ktrk = L.take(i32 * NK), o_lptr = L.take(i32 * (NK + 1)), o_lidx = L.take(i32 * NE),
+                 o_tglob = L.take(i32 * NT), o_kxy = L.take(sizeof(double) * 2 * NK), o_pts = L.take(sizeof(double) * 3 * NT), o_cams = L.take(sizeof(xmerge::Cam) * (size_t)n),
+                 o_first = L.take(i32 * ((size_t)n + 1)), o_cptr = L.take(i32 * ((size_t)N + 1)), o_ckey = L.take(i32 * E), o_tok_in = L.take(i32 * (size_t)N);
+    L.end_inputs();
+    L.begin_outputs();
+    const size_t o_cnt = L.take(i32 * 4), o_tok = L.take(i32 * (size_t)N), o_pout = L.take(sizeof(double) * 3 * NT), o_oout = L.take(NT), o_have = L.take(i32 * (size_t)N),
+                 o_vis = L.take(i32 * (size_t)n), o_mea = L.take(i32 * (size_t)n);
+    L.end_outputs();
+    double ms_upload = 0, ms_comp = 0, ms_counts = 0;
+    std::chrono::steady_clock::time_point t_mark;
+    const int e = staged_call(L,
+        [&](unsigned char* stage) {
+            auto put = [&](size_t at, const void* h, size_t bytes) { if (bytes) memcpy(stage + at, h, bytes); };
+            put(o_key0, P.key0.data(), i32 * P.key0.size()); put(o_trk0, P.trk0.data(), i32 * P.trk0.size()); put(o_seed, P.seed.data(), i32 * P.seed.size());
+            put(o_kglob, P.key_glob.data(), i32 * NK); put(o_kframe, P.key_frame.data(), i32 * NK); put(o_ktrk, P.key_trk.data(), i32 * NK);
+            put(o_lptr, P.lptr.data(), i32 * (NK + 1)); put(o_lidx, P.lidx.data(), i32 * NE); put(o_tglob, P.trk_glob.data(), i32 * NT);
+            put(o_kxy, P.key_xy.data(), sizeof(double) * 2 * NK); put(o_cams, cams.data(), sizeof(xmerge::Cam) * (size_t)n);
+            double* pts = reinterpret_cast<double*>(stage + o_pts);
+            for (size_t j = 0; j < NT; ++j) for (int q = 0; q < 3; ++q) pts[3 * j + q] = in.points[3 * (size_t)P.trk_glob[j] + q];
+            int32_t* first = reinterpret_cast<int32_t*>(stage + o_first);
+            for (int32_t f = 0; f <= n; ++f) first[f] = (int32_t)in.key_ptr[f];
+            int32_t* cptr = reinterpret_cast<int32_t*>(stage + o_cptr);
+            for (int64_t k = 0; k <= N; ++k) cptr[k] = (int32_t)in.corr_ptr[k];
+            put(o_ckey, in.corr_key, i32 * E); put(o_tok_in, track_of_key, i32 * (size_t)N);
+            t_mark = std::chrono::steady_clock::now();
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
+            if (timing) { (void)hipStreamSynchronize(st); ms_upload = expand_ms(t_mark); t_mark = std::chrono::steady_clock::now(); }
+            if (hipMemsetAsync(base + o_cnt, 0, i32 * 4, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            if (hipMemcpyAsync(base + o_tok, base + o_tok_in, i32 * (size_t)N, hipMemcpyDeviceToDevice, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            auto at = [&](size_t off) { return reinterpret_cast<const int32_t*>(base + off); };
+            MergeArgs a;
+            a.key0 = at(o_key0); a.trk0 = at(o_trk0); a.seed = at(o_seed); a.key_glob = at(o_kglob); a.key_frame = at(o_kframe); a.key_trk = at(o_ktrk); a.lptr = at(o_lptr);
+            a.lidx = at(o_lidx); a.trk_glob = at(o_tglob); a.key_xy = (const double*)(base + o_kxy); a.pts_in = (const double*)(base + o_pts);
+            a.cams = (const xmerge::Cam*)(base + o_cams); a.max_re = o.max_reproj_error; a.mode = o.mode; a.track_of_key = (int32_t*)(base + o_tok);
+            a.pts_out = (double*)(base + o_pout); a.outlier_out = base + o_oout; a.counters = (int32_t*)(base + o_cnt);
+            if (P.n_comp > 0) hipLaunchKernelGGL(k_merge_components, dim3((unsigned)P.n_comp), dim3(kMergeWave), 0, st, a);
+            if (timing) { (void)hipStreamSynchronize(st); ms_comp = expand_ms(t_mark); t_mark = std::chrono::steady_clock::now(); }
+            hipLaunchKernelGGL(k_merge_counts, dim3((unsigned)(cdiv((long long)N, kMergeCountThreads) + n)), dim3(kMergeCountThreads), 0, st, (int32_t)N, n, at(o_first), at(o_cptr),
+                               at(o_ckey), at(o_tok), (int32_t*)(base + o_have), (int32_t*)(base + o_vis), (int32_t*)(base + o_mea));
+            if (timing) { (void)hipStreamSynchronize(st); ms_counts = expand_ms(t_mark); t_mark = std::chrono::steady_clock::now(); }
+            return 0;
+        },
+        [&](const xstage::View& v) {
+            memcpy(track_of_key, v.at<int32_t>(o_tok), i32 * (size_t)N);
+            if (track_status) memset(track_status, 0, (size_t)T);
+            // (the keys were written on the device; here only what is kept per plan track goes to its place)
+            const double* pts = v.at<double>(o_pout);
+            const uint8_t* out = v.at<uint8_t>(o_oout);
+            for (size_t j = 0; j < NT; ++j) {
+                const int32_t g = P.trk_glob[j];
+                for (int q = 0; q < 3; ++q) points[3 * (size_t)g + q] = pts[3 * j + q];
+                if (out[j]) track_outlier[g] = 1;
+                if (track_status) track_status[g] = out[j] ? 2 : 1;
+            }
+            if (track_status) for (int32_t g : P.skipped_tracks) track_status[g] = 3;
+            if (corr_have_point3d) memcpy(corr_have_point3d, v.at<int32_t>(o_have), i32 * (size_t)N);
+            if (visible) memcpy(visible, v.at<int32_t>(o_vis), i32 * (size_t)n);
+            if (measured) memcpy(measured, v.at<int32_t>(o_mea), i32 * (size_t)n);
+            if (stats) {
+                const int32_t* c = v.at<int32_t>(o_cnt);
+                for (int q = 0; q < 4; ++q) stats[q] = c[q];
+                stats[4] = P.n_comp; stats[5] = P.n_skipped; stats[6] = P.largest; stats[7] = 0;
+            }
+        });
+    if (timing && !e)
+        fprintf(stderr, "[xrsfm_ba] merge timing: host %.4f ms, upload %.4f ms, components %.4f ms, counts %.4f ms, back %.4f ms, total %.4f ms\n", ms_host, ms_upload, ms_comp,
+                ms_counts, expand_ms(t_mark), expand_ms(t_begin));
+    return e;
+}
+
+int debug_merge_components_impl(const xmerge::In& in, int32_t* comp_of_key, int32_t* n_comp) {
+    const char* who = "xrsfm_ba_debug_merge_components";
+    if (!n_comp) return complain(who, "NULL n_comp");
+    std::vector<int32_t> frame_of_key;
+    if (int e = merge_check(who, in, &frame_of_key)) return e;
+    const int64_t N = in.key_ptr[in.n_frames];
+    if (N > 0 && !comp_of_key) return complain(who, "NULL comp_of_key");
+    const xmerge::Labels lab = xmerge::label_components(in);
+    if (N > 0) memcpy(comp_of_key, lab.comp_of_key.data(), sizeof(int32_t) * (size_t)N);
+    *n_comp = (int32_t)lab.size.size();
+    return XRSFM_BA_OK;
+}
+}  // namespace
+
+int xrsfm_ba_merge_tracks(const xrsfm_ba_merge_options* opt, int32_t n_frames, const int64_t* key_ptr, const double* key_xy, const uint8_t* registered, const double* cam_q,
+                          const double* cam_t, const int32_t* cam_intr, int32_t n_intr, const int32_t* intr_model, const double* intr_params, const int64_t* corr_ptr,
+                          const int32_t* corr_key, int32_t n_tracks, double* points, uint8_t* track_outlier, int32_t* track_of_key, uint8_t* track_status,
+                          int32_t* corr_have_point3d, int32_t* visible, int32_t* measured, int64_t* stats) {
+    const xmerge::In in{reinterpret_cast<const xmerge::Opt*>(opt), n_frames, key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, n_intr, intr_model, intr_params, corr_ptr, corr_key,
+                        n_tracks, points, track_outlier, track_of_key};
+    return no_throw([&] { return merge_tracks_impl(in, points, track_outlier, track_of_key, track_status, corr_have_point3d, visible, measured, stats); });
+}
+
+int xrsfm_ba_debug_merge_components(const xrsfm_ba_merge_options* opt, int32_t n_frames, const int64_t* key_ptr, const double* key_xy, const uint8_t* registered,
+                                    const double* cam_q, const double* cam_t, const int32_t* cam_intr, int32_t n_intr, const int32_t* intr_model, const double* intr_params,
+                                    const int64_t* corr_ptr, const int32_t* corr_key, int32_t n_tracks, const double* points, const uint8_t* track_outlier,
+                                    const int32_t* track_of_key, int32_t* comp_of_key, int32_t* n_comp) {
+    const xmerge::In in{reinterpret_cast<const xmerge::Opt*>(opt), n_frames, key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, n_intr, intr_model, intr_params, corr_ptr, corr_key,
+                        n_tracks, points, track_outlier, track_of_key};
+    return no_throw([&] { return debug_merge_components_impl(in, comp_of_key, n_comp); });
 }
 
 // ---------------------------------------------------------------- diagnostics
