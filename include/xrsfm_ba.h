@@ -1096,6 +1096,64 @@ int xrsfm_ba_debug_merge_components(const xrsfm_ba_merge_options *opt, int32_t n
                                     int32_t n_tracks, const double *points, const uint8_t *track_outlier,
                                     const int32_t *track_of_key, int32_t *comp_of_key, int32_t *n_comp);
 
+/* ---- frame triangulation ----
+ * Point3dProcessor::TriangulateFramePoint (track_processor.cc:163-251) for a list of frames in the caller's order: the mapper passes
+ * the frame it has just registered (incremental_mapper.cc:60), run_triangulation every registered frame ascending
+ * (run_triangulation.cc:141-148).  The frames are processed one after another and each sees the state the earlier ones left; the
+ * result is that of the sequential program.  The state is that of xrsfm_ba_merge_tracks, read and written: track_of_key [N], points
+ * [track_capacity][3], track_outlier [track_capacity], of which the first n_tracks are in use; new tracks are appended.
+ *
+ * Within a frame the key points p with track_of_key == -1 are visited ascending.  The observations of p are the entries of its
+ * correspondence list, in stored order, whose frame is registered, then (frame, p); with fewer than two p is skipped (status 2).
+ *   create   no observation carries a track: CreatePoint3d1 on the observations, exactly what xrsfm_ba_triangulate_tracks computes
+ *            for that list (status 3 above XRSFM_BA_TRI_MAX_OBS observations, 4 without a model).  On success (status 1) the new
+ *            track gets the id "current number of tracks", its point is the model, its outlier flag 0, and track_of_key is set
+ *            for the INLIER observations only (AddTrack).
+ *   extend   otherwise (GetMaxAngle, ContinueTrackUpdate): candidates are the distinct tracks of the observations; one that already
+ *            has a key point in this frame is skipped.  ray1 = (q X + t).normalized(), ray2 = (x_n, y_n, 1).normalized() (Eigen: a
+ *            zero vector stays zero); the best candidate has the smallest angle acos(ray1 . ray2), the smaller id on equal angles;
+ *            a NaN angle (a dot product above 1) is never best.  Below extend_angle_rad track_of_key[p] = best (status 5), else
+ *            nothing happens (status 6).  No track is created in this branch, even when no track is eligible.
+ * Documented deviation: no acos is evaluated on the device.  Candidates are ordered by the dot product (larger is better, the
+ * smaller id on equal dot products) and accepted by dot >= the smallest double whose acos, by the host's libm, is below
+ * extend_angle_rad.  The acceptance is the literal one; the order differs only where two different dot products have the same
+ * acos (csrc/ba_trif_rule.h).
+ *
+ * Inputs as for xrsfm_ba_merge_tracks, but key_xyn [N][2] are NORMALISED coordinates (undistortion stays with the caller, as for
+ * xrsfm_ba_triangulate_tracks) and no camera model is needed.  frame_list [n_list]: registered frames, none twice.
+ * track_capacity must cover n_tracks plus the key points without a track of the listed frames that have two or more observations.
+ *
+ * Outputs besides the three arrays, each may be NULL: n_tracks_out; key_status [N] (0 not visited, 1 created, 2 fewer than two
+ * observations, 3 above the observation limit, 4 no model, 5 extended, 6 tracks seen, none accepted); num_inliers, num_trials,
+ * best_trial [N]: the diagnostics of xrsfm_ba_triangulate_tracks for the key points of the create branch with status 1 or 4
+ * (elsewhere 0, 0, -1); corr_have_point3d [N], visible and measured [n_frames] of the final state, as for xrsfm_ba_merge_tracks;
+ * stats [8]: created, key points of the create branch, extended, key points that saw one track, that saw several (the five
+ * counters the reference prints), steps, listed frames that needed more than one step, the most claim rounds of a step.
+ *
+ * Two key points of a frame whose lists share an entry are coupled (a track the first creates changes the second's branch): the
+ * host cuts a frame into maximal runs without a coupled pair, one step each; one-to-one matches give one step per frame.
+ *
+ * Errors: every check runs on the host before the device is touched and prints one line on stderr that names the entry; on any
+ * negative code no output is touched.  XRSFM_BA_EINVAL: NULL opt or needed array; a negative count; offsets not starting at 0 or
+ * decreasing; a key or track index out of range; a listed frame out of range, not registered or listed twice; a key point carrying
+ * an outlier track; a list entry pointing into the key point's own frame; a non-symmetric list; a non-finite pose, point,
+ * coordinate or option; extend_angle_rad outside [0, 3.2]; the option faults of xrsfm_ba_triangulate_tracks; track_capacity below
+ * the bound above.  XRSFM_BA_ETOOBIG: key points or entries above INT32_MAX.  Nothing to do (no listed frame, or none of their key
+ * points without a track has two observations) is success and needs no device; otherwise XRSFM_BA_ENODEV without one. */
+typedef struct xrsfm_ba_trif_options {
+    double extend_angle_rad;       /* DegToRad(8.0)   run_triangulation.cc:144 */
+    xrsfm_ba_tri_options tri;      /* xrsfm_ba_triangulate_options: CreatePoint3d1 */
+} xrsfm_ba_trif_options;
+void xrsfm_ba_trif_options_default(xrsfm_ba_trif_options *opt);
+
+int xrsfm_ba_triangulate_frames(const xrsfm_ba_trif_options *opt, int32_t n_frames, const int64_t *key_ptr, const double *key_xyn,
+                                const uint8_t *registered, const double *cam_q, const double *cam_t, const int64_t *corr_ptr,
+                                const int32_t *corr_key, int32_t n_list, const int32_t *frame_list, int32_t n_tracks,
+                                int32_t track_capacity, double *points, uint8_t *track_outlier, int32_t *track_of_key,
+                                int32_t *n_tracks_out, uint8_t *key_status, int32_t *num_inliers, int32_t *num_trials,
+                                int32_t *best_trial, int32_t *corr_have_point3d, int32_t *visible, int32_t *measured,
+                                int64_t *stats);
+
 /* profile != 0 in the last xrsfm_ba_run: per-kernel totals measured with HIP events on the
  * library's stream.  Returns 0 and fills the outputs for index < number of kernel classes,
  * XRSFM_BA_EINVAL past the end. */

@@ -126,6 +126,10 @@ class CMergeOptions(C.Structure):
     _fields_ = [("max_reproj_error", C.c_double), ("mode", C.c_int32), ("frame", C.c_int32)]
 
 
+class CTrifOptions(C.Structure):
+    _fields_ = [("extend_angle_rad", C.c_double), ("tri", CTriOptions)]
+
+
 # every symbol include/xrsfm_ba.h declares
 EXPORTS = [
     "xrsfm_ba_default_options", "xrsfm_ba_version", "xrsfm_ba_create", "xrsfm_ba_comm_unique_id",
@@ -150,6 +154,7 @@ EXPORTS = [
     "xrsfm_ba_expand_options_default", "xrsfm_ba_expand_candidates", "xrsfm_ba_frames_expand", "xrsfm_ba_debug_expand_tracks",
     "xrsfm_ba_debug_expand_covis",
     "xrsfm_ba_merge_options_default", "xrsfm_ba_merge_tracks", "xrsfm_ba_debug_merge_components",
+    "xrsfm_ba_trif_options_default", "xrsfm_ba_triangulate_frames",
 ]
 # declared too, but kept apart: tests/test_capi_cpu.py collects the header's names with a pattern of letters and underscores only
 EXPORTS_WITH_DIGITS = ["xrsfm_ba_debug_match_top2"]
@@ -385,6 +390,12 @@ def load(path: str | None = None):
     lib.xrsfm_ba_merge_tracks.restype = C.c_int
     lib.xrsfm_ba_debug_merge_components.argtypes = _merge_head + [_c_int32_p, _c_int32_p]
     lib.xrsfm_ba_debug_merge_components.restype = C.c_int
+    lib.xrsfm_ba_trif_options_default.argtypes = [C.POINTER(CTrifOptions)]
+    lib.xrsfm_ba_trif_options_default.restype = None
+    lib.xrsfm_ba_triangulate_frames.argtypes = [C.POINTER(CTrifOptions), C.c_int32, _c_int64_p, _c_double_p, _c_uint8_p, _c_double_p, _c_double_p, _c_int64_p, _c_int32_p,
+                                                C.c_int32, _c_int32_p, C.c_int32, C.c_int32, _c_double_p, _c_uint8_p, _c_int32_p, _c_int32_p, _c_uint8_p, _c_int32_p,
+                                                _c_int32_p, _c_int32_p, _c_int32_p, _c_int32_p, _c_int32_p, _c_int64_p]
+    lib.xrsfm_ba_triangulate_frames.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1956,3 +1967,70 @@ def merge_closure(frame: int, key_ptr, corr_ptr, corr_key, track_of_key) -> dict
     sub_tok = np.where(tok[keys] >= 0, tlocal[np.maximum(tok[keys], 0)], -1).astype(np.int32)
     return dict(keys=keys, tracks=tracks, key_ptr=np.searchsorted(keys, key_ptr).astype(np.int64), corr_ptr=sub_ptr,
                 corr_key=local[ck[_csr_entries(cp, keys)]].astype(np.int32), track_of_key=sub_tok)
+
+
+TRIF_STATS = ("created", "zero_track", "extended", "one_track", "multi_track", "steps", "split_frames", "claim_rounds")
+
+
+def trif_options(**overrides) -> CTrifOptions:
+    """xrsfm_ba_trif_options_default: DegToRad(8.0) and the settings of CreatePoint3d1.  extend_angle_rad, or a field of the embedded
+    CTriOptions by its name."""
+    o = CTrifOptions()
+    load().xrsfm_ba_trif_options_default(C.byref(o))
+    for k, v in overrides.items():
+        if k == "extend_angle_rad":
+            o.extend_angle_rad = v
+        elif hasattr(o.tri, k):
+            setattr(o.tri, k, v)
+        else:
+            raise AttributeError(k)
+    return o
+
+
+def trif_capacity(key_ptr, registered, corr_ptr, corr_key, frames, n_tracks, track_of_key) -> int:
+    """the bound xrsfm_ba_triangulate_frames asks of track_capacity: n_tracks plus the key points without a track of the listed
+    frames that have an entry in a registered frame"""
+    key_ptr, cp = np.asarray(key_ptr, np.int64).reshape(-1), np.asarray(corr_ptr, np.int64).reshape(-1)
+    ck, tok, reg = np.asarray(corr_key, np.int64).reshape(-1), np.asarray(track_of_key).reshape(-1), np.asarray(registered).reshape(-1) != 0
+    frame_of_key = np.repeat(np.arange(len(key_ptr) - 1), np.diff(key_ptr))
+    entry_reg = reg[frame_of_key[ck]].astype(np.int64) if len(ck) else np.zeros(0, np.int64)
+    has = np.diff(np.concatenate([[0], np.cumsum(entry_reg)])[cp]) > 0 if len(tok) else np.zeros(0, bool)
+    listed = np.zeros(len(key_ptr) - 1, bool)
+    listed[np.asarray(frames, np.int64).reshape(-1)] = True
+    return int(n_tracks) + int((listed[frame_of_key] & (tok == -1) & has).sum())
+
+
+def triangulate_frames(key_ptr, key_xyn, registered, cam_q, cam_t, corr_ptr, corr_key, frames, points, track_outlier, track_of_key,
+                       options: CTrifOptions | None = None, capacity: int | None = None) -> dict:
+    """xrsfm_ba_triangulate_frames: TriangulateFramePoint for the listed frames, one after another.  The three state arrays are not
+    changed; the result holds their new values (points and track_outlier cut to n_tracks), key_status and the create diagnostics
+    [N], corr_have_point3d [N], visible and measured [n_frames], stats.  The capacity is the call's bound unless given."""
+    c = np.ascontiguousarray
+    o = options if options is not None else trif_options()
+    key_ptr = c(key_ptr, np.int64).reshape(-1)
+    n = len(key_ptr) - 1
+    xy = c(key_xyn, np.float64).reshape(-1, 2)
+    N = len(xy)
+    reg, q, t = c(registered, np.uint8).reshape(-1), c(cam_q, np.float64).reshape(-1, 4), c(cam_t, np.float64).reshape(-1, 3)
+    cp = c(corr_ptr, np.int64).reshape(-1) if N else np.zeros(1, np.int64)
+    ck = c(corr_key, np.int32).reshape(-1)
+    frames = c(frames, np.int32).reshape(-1)
+    p0, out0, tok = c(points, np.float64).reshape(-1, 3), c(track_outlier, np.uint8).reshape(-1), np.array(track_of_key, np.int32).reshape(-1)
+    T = len(p0)
+    if n < 0 or len(reg) != n or len(q) != n or len(t) != n or len(tok) != N or len(cp) != N + 1 or len(out0) != T or (N and (key_ptr[-1] != N or cp[-1] != len(ck))):
+        raise ValueError("triangulate_frames: inconsistent array lengths")
+    if capacity is None:
+        ok = len(frames) == 0 or (frames.min() >= 0 and frames.max() < n)
+        capacity = trif_capacity(key_ptr, reg, cp, ck, frames, T, tok) if ok and N else T        # (a bad list is the call's to refuse)
+    cap = max(int(capacity), 0)
+    pts, outl = np.zeros((max(cap, T), 3)), np.zeros(max(cap, T), np.uint8)
+    pts[:T] = p0; outl[:T] = out0
+    status, ninl, ntr, best = np.zeros(N, np.uint8), np.zeros(N, np.int32), np.zeros(N, np.int32), np.full(N, -1, np.int32)
+    have, vis, mea, stats, nout = np.zeros(N, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(8, np.int64), C.c_int32(T)
+    ip, up, lp = (lambda a: a.ctypes.data_as(_c_int32_p)), (lambda a: a.ctypes.data_as(_c_uint8_p)), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)))
+    check(load().xrsfm_ba_triangulate_frames(C.byref(o), n, lp(key_ptr), _dp(xy), up(reg), _dp(q), _dp(t), lp(cp), ip(ck), len(frames), ip(frames), T, int(capacity), _dp(pts),
+                                             up(outl), ip(tok), C.byref(nout), up(status), ip(ninl), ip(ntr), ip(best), ip(have), ip(vis), ip(mea), lp(stats)),
+          "xrsfm_ba_triangulate_frames")
+    T1 = int(nout.value)
+    return dict(points=pts[:T1].copy(), track_outlier=outl[:T1].copy(), track_of_key=tok, n_tracks=T1, key_status=status, num_inliers=ninl, num_trials=ntr,
+                best_trial=best, corr_have_point3d=have, visible=vis, measured=mea, stats=dict(zip(TRIF_STATS, (int(x) for x in stats))))

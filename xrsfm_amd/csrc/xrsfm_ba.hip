@@ -31,6 +31,7 @@
 #include "ba_cov.h"
 #include "ba_expand.h"
 #include "ba_merge.h"
+#include "ba_trif.h"
 #include "ba_filter.h"
 #include "ba_kernels.h"
 #include "ba_lba.h"
@@ -6020,6 +6021,189 @@ int xrsfm_ba_debug_merge_components(const xrsfm_ba_merge_options* opt, int32_t n
     const xmerge::In in{reinterpret_cast<const xmerge::Opt*>(opt), n_frames, key_ptr, key_xy, registered, cam_q, cam_t, cam_intr, n_intr, intr_model, intr_params, corr_ptr, corr_key,
                         n_tracks, points, track_outlier, track_of_key};
     return no_throw([&] { return debug_merge_components_impl(in, comp_of_key, n_comp); });
+}
+
+// ---------------------------------------------------------------- frame triangulation (ba_trif.h)
+static_assert(sizeof(xrsfm_ba_trif_options) == sizeof(xtrif::Opt) && sizeof(xrsfm_ba_tri_options) == sizeof(xtrif::TriOpt),
+              "xtrif::Opt mirrors xrsfm_ba_trif_options field for field");
+static_assert(XRSFM_BA_TRI_MAX_OBS == xtrif::kMaxObs && xtri::kMaxObs == xtrif::kMaxObs, "the observation limit of k_tri_tracks");
+
+void xrsfm_ba_trif_options_default(xrsfm_ba_trif_options* opt) {
+    if (!opt) return;
+    opt->extend_angle_rad = xtrif::kExtendAngle;
+    xrsfm_ba_triangulate_options(&opt->tri);
+}
+
+namespace {
+int triangulate_frames_impl(const xtrif::In& in, double* points, uint8_t* track_outlier, int32_t* track_of_key, int32_t* n_tracks_out, uint8_t* key_status, int32_t* num_inliers,
+                            int32_t* num_trials, int32_t* best_trial, int32_t* corr_have_point3d, int32_t* visible, int32_t* measured, int64_t* stats) {
+    const char* who = "xrsfm_ba_triangulate_frames";
+    const bool timing = getenv("XRSFM_BA_TRIF_TIMING") != nullptr;
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::vector<int32_t> frame_of_key;
+    bool too_big = false;
+    if (const char* fault = xtrif::fault(in, &frame_of_key, &too_big)) {
+        if (!too_big) return complain(who, fault);
+        fprintf(stderr, "[xrsfm_ba] %s: %s\n", who, fault);
+        return XRSFM_BA_ETOOBIG;
+    }
+    const xtrif::Plan P = xtrif::make_plan(in, frame_of_key);
+    if (const char* fault = xtrif::capacity_fault(in, P)) return complain(who, fault);
+    const int32_t n = in.n_frames, T = in.n_tracks, NS = P.n_slots(), S = P.n_steps();
+    const int64_t N = in.key_ptr[n];
+    auto diagnostics_default = [&] {
+        if (num_inliers && N > 0) memset(num_inliers, 0, sizeof(int32_t) * (size_t)N);
+        if (num_trials && N > 0) memset(num_trials, 0, sizeof(int32_t) * (size_t)N);
+        if (best_trial) for (int64_t k = 0; k < N; ++k) best_trial[k] = -1;
+    };
+    if (NS == 0) {                             // nothing to do: the state stands, the counts follow from it
+        if (n_tracks_out) *n_tracks_out = T;
+        if (key_status && N > 0) memcpy(key_status, P.status0.data(), (size_t)N);
+        diagnostics_default();
+        xmerge::In counts{};
+        counts.n_frames = n; counts.key_ptr = in.key_ptr; counts.corr_ptr = in.corr_ptr; counts.corr_key = in.corr_key;
+        if (N > 0) xmerge::counts_host(counts, track_of_key, corr_have_point3d, visible, measured);
+        else { if (visible && n > 0) memset(visible, 0, sizeof(int32_t) * (size_t)n); if (measured && n > 0) memset(measured, 0, sizeof(int32_t) * (size_t)n); }
+        if (stats) memset(stats, 0, sizeof(int64_t) * 8);
+        return XRSFM_BA_OK;
+    }
+    if (int e = require_device("frame triangulation")) return e;
+    const xtrif::TriOpt& to = in.opt->tri;
+    TriParams prm;
+    prm.min_angle = to.min_tri_angle_rad;
+    prm.max_residual = to.max_error_rad * to.max_error_rad;
+    prm.trial_cap = std::min(to.max_num_trials, xtri::tri_ratio_trials(to.min_inlier_ratio, to.confidence));
+    prm.exhaustive_threshold = to.exhaustive_threshold;
+    const int32_t* dyn = tri_dyn_table(to.confidence);
+    const size_t dyn_bytes = sizeof(int32_t) * (size_t)(xtri::kMaxObs + 1) * (xtri::kMaxObs + 1);
+    const double dot_min = xtrif::dot_bound(in.opt->extend_angle_rad);
+    const size_t No = P.obs_key.size(), E = (size_t)in.corr_ptr[N], NT = (size_t)T + (size_t)NS, MS = (size_t)P.max_step;
+    size_t max_obs_step = 0;                   // the observations of a step's packed lists
+    for (int32_t s = 0; s < S; ++s) max_obs_step = std::max(max_obs_step, (size_t)(P.trk_ptr[(size_t)P.step_slot0[(size_t)s + 1]] - P.trk_ptr[(size_t)P.step_slot0[(size_t)s]]));
+    const double ms_host = expand_ms(t_begin);
+    HIPCHK(hipSetDevice(0));
+    // one block, one upload, the steps' launches, one read-back (staged_call); the state stays on the device between the steps
+    xstage::Layout L;
+    const size_t i32 = sizeof(int32_t), f64 = sizeof(double);
+    const size_t o_cams = L.take(sizeof(CamRec) * (size_t)n), o_first = L.take(i32 * ((size_t)n + 1)), o_skey = L.take(i32 * (size_t)NS), o_tptr = L.take(i32 * ((size_t)NS + 1)),
+                 o_ocam = L.take(i32 * No), o_okey = L.take(i32 * No), o_oxy = L.take(f64 * 2 * No), o_pold = L.take(f64 * 3 * (size_t)T), o_cptr = L.take(i32 * ((size_t)N + 1)),
+                 o_ckey = L.take(i32 * E), o_tok_in = L.take(i32 * (size_t)N), o_st_in = L.take((size_t)N), o_dyn = L.take(dyn_bytes), o_cnt_in = L.take(i32 * 12);
+    L.end_inputs();
+    const size_t o_centre = L.take(f64 * 3 * (size_t)n), o_held = L.take(i32 * NT), o_bid = L.take(i32 * NT), o_cls = L.take(i32 * (size_t)NS), o_und = L.take(i32 * (size_t)NS),
+                 o_win = L.take(i32 * (size_t)NS), o_ctrk = L.take(i32 * No), o_cdot = L.take(f64 * No), o_ccount = L.take(i32), o_csel = L.take(i32 * MS),
+                 o_cp = L.take(i32 * (MS + 1)), o_ccam = L.take(i32 * max_obs_step), o_cxy = L.take(f64 * 2 * max_obs_step), o_cpts = L.take(f64 * 3 * MS), o_cstat = L.take(MS),
+                 o_cmask = L.take(max_obs_step), o_cninl = L.take(i32 * MS), o_cntr = L.take(i32 * MS), o_cbest = L.take(i32 * MS);
+    L.begin_outputs();
+    const size_t o_cnt = L.take(i32 * 12), o_tok = L.take(i32 * (size_t)N), o_stat = L.take((size_t)N), o_pnew = L.take(f64 * 3 * (size_t)NS), o_diag = L.take(i32 * 3 * (size_t)NS),
+                 o_have = L.take(i32 * (size_t)N), o_vis = L.take(i32 * (size_t)n), o_mea = L.take(i32 * (size_t)n);
+    L.end_outputs();
+    double ms_upload = 0, ms_kernel[6] = {0, 0, 0, 0, 0, 0};      // held, classify, select, create, resolve, counts
+    std::chrono::steady_clock::time_point t_mark;
+    // (timing only) HIP events around every k_tri_tracks launch: the kernel's own time, the clock xrsfm_ba_triangulate_tracks reports
+    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) hipEventDestroy(ev0); if (ev1) hipEventDestroy(ev1); } } tm;
+    double ms_create_events = 0;
+    const int e = staged_call(L,
+        [&](unsigned char* stage) {
+            if (timing && (hipEventCreate(&tm.ev0) != hipSuccess || hipEventCreate(&tm.ev1) != hipSuccess)) return XRSFM_BA_ENODEV;
+            auto put = [&](size_t at, const void* h, size_t bytes) { if (bytes) memcpy(stage + at, h, bytes); };
+            CamRec* cams = reinterpret_cast<CamRec*>(stage + o_cams);
+            for (int32_t f = 0; f < n; ++f) cams[f] = cam_record(in.cam_q + 4 * (size_t)f, in.cam_t + 3 * (size_t)f, nullptr);
+            int32_t* first = reinterpret_cast<int32_t*>(stage + o_first);
+            for (int32_t f = 0; f <= n; ++f) first[f] = (int32_t)in.key_ptr[f];
+            put(o_skey, P.slot_key.data(), i32 * (size_t)NS); put(o_tptr, P.trk_ptr.data(), i32 * ((size_t)NS + 1)); put(o_ocam, P.obs_cam.data(), i32 * No);
+            put(o_okey, P.obs_key.data(), i32 * No); put(o_oxy, P.obs_xy.data(), f64 * 2 * No); put(o_pold, in.points, f64 * 3 * (size_t)T);
+            int32_t* cptr = reinterpret_cast<int32_t*>(stage + o_cptr);
+            for (int64_t k = 0; k <= N; ++k) cptr[k] = (int32_t)in.corr_ptr[k];
+            put(o_ckey, in.corr_key, i32 * E); put(o_tok_in, track_of_key, i32 * (size_t)N); put(o_st_in, P.status0.data(), (size_t)N); put(o_dyn, dyn, dyn_bytes);
+            const int32_t counters0[12] = {0, 0, 0, 0, 0, 0, 0, 0, T, 0, 0, 0};           // [8]: the number of tracks
+            put(o_cnt_in, counters0, sizeof(counters0));
+            t_mark = std::chrono::steady_clock::now();
+            return 0;
+        },
+        [&](hipStream_t st, unsigned char* base) {
+            auto lap = [&](double* into) { if (timing) { (void)hipStreamSynchronize(st); *into += expand_ms(t_mark); t_mark = std::chrono::steady_clock::now(); } };
+            lap(&ms_upload);
+            if (hipMemcpyAsync(base + o_cnt, base + o_cnt_in, i32 * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            if (hipMemcpyAsync(base + o_tok, base + o_tok_in, i32 * (size_t)N, hipMemcpyDeviceToDevice, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            if (hipMemcpyAsync(base + o_stat, base + o_st_in, (size_t)N, hipMemcpyDeviceToDevice, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            if (hipMemsetAsync(base + o_held, 0, i32 * NT, st) != hipSuccess || hipMemsetAsync(base + o_bid, 0x7f, i32 * NT, st) != hipSuccess ||
+                hipMemsetAsync(base + o_diag, 0, i32 * 3 * (size_t)NS, st) != hipSuccess) return XRSFM_BA_ENODEV;
+            auto ip = [&](size_t off) { return reinterpret_cast<int32_t*>(base + off); };
+            auto dp = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+            TrifArgs a;
+            a.cams = (const CamRec*)(base + o_cams); a.first = ip(o_first); a.slot_key = ip(o_skey); a.trk_ptr = ip(o_tptr); a.obs_cam = ip(o_ocam); a.obs_key = ip(o_okey);
+            a.obs_xy = dp(o_oxy); a.pts_old = dp(o_pold); a.pts_new = dp(o_pnew); a.track_of_key = ip(o_tok); a.key_status = base + o_stat; a.held = ip(o_held); a.bid = ip(o_bid);
+            a.counters = ip(o_cnt); a.cls = ip(o_cls); a.undecided = ip(o_und); a.win = ip(o_win); a.diag = ip(o_diag); a.cand_trk = ip(o_ctrk); a.cand_dot = dp(o_cdot);
+            a.c_count = ip(o_ccount); a.c_sel = ip(o_csel); a.c_ptr = ip(o_cp); a.c_cam = ip(o_ccam); a.c_xy = dp(o_cxy); a.c_pts = dp(o_cpts); a.c_stat = base + o_cstat;
+            a.c_mask = base + o_cmask; a.c_ninl = ip(o_cninl); a.c_ntr = ip(o_cntr); a.c_best = ip(o_cbest); a.n_old = T; a.dot_min = dot_min;
+            hipLaunchKernelGGL(k_cam_centres, dim3(cdiv(n, 256)), dim3(256), 0, st, a.cams, n, dp(o_centre));
+            lap(&ms_upload);
+            for (int32_t step = 0; step < S; ++step) {
+                const int32_t f = P.step_frame[(size_t)step], s0 = P.step_slot0[(size_t)step], s1 = P.step_slot0[(size_t)step + 1], stamp = step + 1, ns = s1 - s0;
+                const int32_t nk = (int32_t)(in.key_ptr[f + 1] - in.key_ptr[f]);
+                hipLaunchKernelGGL(k_trif_held, dim3(cdiv(nk, kTrifThreads)), dim3(kTrifThreads), 0, st, a, f, stamp);
+                lap(&ms_kernel[0]);
+                hipLaunchKernelGGL(k_trif_classify, dim3(cdiv(ns, kTrifThreads)), dim3(kTrifThreads), 0, st, a, f, stamp, s0, s1);
+                lap(&ms_kernel[1]);
+                hipLaunchKernelGGL(k_trif_select, dim3(1), dim3(kTrifThreads), 0, st, a, s0, s1);
+                lap(&ms_kernel[2]);
+                if (timing) (void)hipEventRecord(tm.ev0, st);
+                hipLaunchKernelGGL(k_tri_tracks, dim3(cdiv(ns, kTriWaves)), dim3(kTriWave * kTriWaves), 0, st, a.cams, (const double*)dp(o_centre), (const int*)a.c_ptr,
+                                   (const int*)a.c_cam, (const double*)a.c_xy, (int)ns, prm, (const int32_t*)(base + o_dyn), dp(o_cpts), base + o_cstat, base + o_cmask,
+                                   (int*)ip(o_cninl), (int*)ip(o_cntr), (int*)ip(o_cbest), (unsigned long long*)nullptr);
+                if (timing) (void)hipEventRecord(tm.ev1, st);
+                lap(&ms_kernel[3]);
+                float ms_ev = 0.0f;                      // (lap has drained the stream)
+                if (timing && hipEventElapsedTime(&ms_ev, tm.ev0, tm.ev1) == hipSuccess) ms_create_events += ms_ev;
+                hipLaunchKernelGGL(k_trif_resolve, dim3(1), dim3(kTrifThreads), 0, st, a, stamp, s0, s1);
+                lap(&ms_kernel[4]);
+            }
+            hipLaunchKernelGGL(k_merge_counts, dim3((unsigned)(cdiv((long long)N, kMergeCountThreads) + n)), dim3(kMergeCountThreads), 0, st, (int32_t)N, n, (const int32_t*)ip(o_first),
+                               (const int32_t*)ip(o_cptr), (const int32_t*)ip(o_ckey), (const int32_t*)ip(o_tok), ip(o_have), ip(o_vis), ip(o_mea));
+            lap(&ms_kernel[5]);
+            return 0;
+        },
+        [&](const xstage::View& v) {
+            const int32_t* c = v.at<int32_t>(o_cnt);
+            const int32_t T1 = c[8];
+            memcpy(track_of_key, v.at<int32_t>(o_tok), i32 * (size_t)N);
+            if (T1 > T) { memcpy(points + 3 * (size_t)T, v.at<double>(o_pnew), f64 * 3 * (size_t)(T1 - T)); memset(track_outlier + T, 0, (size_t)(T1 - T)); }
+            if (n_tracks_out) *n_tracks_out = T1;
+            const uint8_t* ks = v.at<uint8_t>(o_stat);
+            if (key_status) memcpy(key_status, ks, (size_t)N);
+            diagnostics_default();
+            const int32_t* diag = v.at<int32_t>(o_diag);
+            for (int32_t s = 0; s < NS; ++s) {
+                const int32_t p = P.slot_key[(size_t)s];
+                if (ks[p] != xtrif::kCreated && ks[p] != xtrif::kNoModel) continue;
+                if (num_inliers) num_inliers[p] = diag[3 * (size_t)s];
+                if (num_trials) num_trials[p] = diag[3 * (size_t)s + 1];
+                if (best_trial) best_trial[p] = diag[3 * (size_t)s + 2];
+            }
+            if (corr_have_point3d) memcpy(corr_have_point3d, v.at<int32_t>(o_have), i32 * (size_t)N);
+            if (visible) memcpy(visible, v.at<int32_t>(o_vis), i32 * (size_t)n);
+            if (measured) memcpy(measured, v.at<int32_t>(o_mea), i32 * (size_t)n);
+            if (stats) {
+                for (int q = 0; q < 5; ++q) stats[q] = c[q];
+                stats[5] = S; stats[6] = P.frames_multi; stats[7] = c[7];
+            }
+        });
+    if (timing && !e)
+        fprintf(stderr, "[xrsfm_ba] trif timing: host %.4f ms, upload %.4f ms, held %.4f ms, classify %.4f ms, select %.4f ms, create %.4f ms, resolve %.4f ms, counts %.4f ms, "
+                "back %.4f ms, total %.4f ms, steps %d, slots %d, create_events %.4f ms\n", ms_host, ms_upload, ms_kernel[0], ms_kernel[1], ms_kernel[2], ms_kernel[3], ms_kernel[4],
+                ms_kernel[5], expand_ms(t_mark), expand_ms(t_begin), (int)S, (int)NS, ms_create_events);
+    return e;
+}
+}  // namespace
+
+int xrsfm_ba_triangulate_frames(const xrsfm_ba_trif_options* opt, int32_t n_frames, const int64_t* key_ptr, const double* key_xyn, const uint8_t* registered, const double* cam_q,
+                                const double* cam_t, const int64_t* corr_ptr, const int32_t* corr_key, int32_t n_list, const int32_t* frame_list, int32_t n_tracks,
+                                int32_t track_capacity, double* points, uint8_t* track_outlier, int32_t* track_of_key, int32_t* n_tracks_out, uint8_t* key_status,
+                                int32_t* num_inliers, int32_t* num_trials, int32_t* best_trial, int32_t* corr_have_point3d, int32_t* visible, int32_t* measured, int64_t* stats) {
+    const xtrif::In in{reinterpret_cast<const xtrif::Opt*>(opt), n_frames, key_ptr, key_xyn, registered, cam_q, cam_t, corr_ptr, corr_key, n_list, frame_list, n_tracks,
+                       (int64_t)track_capacity, points, track_outlier, track_of_key};
+    return no_throw([&] { return triangulate_frames_impl(in, points, track_outlier, track_of_key, n_tracks_out, key_status, num_inliers, num_trials, best_trial, corr_have_point3d,
+                                                         visible, measured, stats); });
 }
 
 // ---------------------------------------------------------------- diagnostics
