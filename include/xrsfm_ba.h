@@ -1281,6 +1281,13 @@ int xrsfm_ba_debug_stored_j(xrsfm_ba_context *ctx, int32_t *stored);
  * bal9 context launches the camera gradient kernel. */
 int xrsfm_ba_debug_lin_scalars(xrsfm_ba_context *ctx, double out[4]);
 
+/* TEST ENTRY.  xrsfm_ba_run with linear_solver = XRSFM_BA_SOLVER_RESIDENT (the field of opt is ignored): the same single launch,
+ * the same state and summary bit for bit, plus the iteration rows the kernel keeps for the progress table.  rows
+ * [max_iterations + 1][7] = {cost, cost change, gradient max-norm, step norm, rho, radius after the decision, iteration}: one row
+ * per evaluated point (iteration 0 and every accepted step) and one per rejected or invalid step; a tolerance exit writes none.
+ * *n_rows: how many were written.  The refusals of the resident solver apply (XRSFM_BA_EINVAL, nothing written). */
+int xrsfm_ba_debug_resident_rows(xrsfm_ba_context *ctx, const xrsfm_ba_options *opt, xrsfm_ba_summary *summary, double *rows, int32_t *n_rows);
+
 /* TEST ENTRY, host only (needs no device).  The tracks that match expansion builds from the pairs in list order (MakeTrack /
  * AddTrack): key_track [N] (-1, or a track, which may be invalid), *n_tracks, track_ptr [track_capacity+1], invalid
  * [track_capacity], obs_frame and obs_key [obs_capacity] ascending by frame within a track (obs_key: the key point within its

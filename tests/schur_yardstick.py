@@ -199,14 +199,24 @@ def _track_pairs(ci, pi):
     return pa, pb
 
 
-def prepare(arr, lin):
-    """The radius-independent part.  lin: r [No][2], Jc [No][2][cw], Jp [No][2][3] (float64, taken as exact)."""
+def prepare(arr, lin, bars=None):
+    """The radius-independent part.  lin: r [No][2], Jc [No][2][cw], Jp [No][2][3] (float64, taken as exact).
+    bars (tests/lba_step_yardstick.py): the same three keys, the bars of a linearisation that is itself a computed quantity; lin may
+    then hold long-double values.  They travel through Hpp, g_p, diag Hcc and g_c by the (value, bar) arithmetic and, to first
+    order, through W = F^T E and F^T F (dW, dFtF: system() adds them where W and F^T F enter)."""
     ci = np.asarray(arr["obs_cam"], np.int64); pi = np.asarray(arr["obs_pt"], np.int64)
     Nc, Np = arr["cam_q"].shape[0], arr["points"].shape[0]
     Jc, Jp, r = (np.ascontiguousarray(lin[k], np.float64) for k in ("Jc", "Jp", "r"))
     cw = Jc.shape[2]
-    F, E = Jc.astype(LD), Jp.astype(LD)
-    Fv, Ev, rv = V(Jc), V(Jp), V(r)
+    F, E = np.asarray(lin["Jc"], LD), np.asarray(lin["Jp"], LD)
+    Fv, Ev, rv = V(F), V(E), V(np.asarray(lin["r"], LD))
+    extra = {}
+    if bars is not None:
+        eF, eE = np.asarray(bars["Jc"], np.float64), np.asarray(bars["Jp"], np.float64)
+        Fv, Ev, rv = V(F, bars["Jc"]), V(E, bars["Jp"]), V(rv.v, bars["r"])
+        aF, aE = np.abs(Jc), np.abs(Jp)
+        extra = dict(dW=np.einsum("nki,nkj->nij", aF, eE) + np.einsum("nki,nkj->nij", eF, aE),
+                     dFtF=np.einsum("nki,nkj->nij", aF, eF) + np.einsum("nki,nkj->nij", eF, aF))
     r0, r1 = rv[:, 0:1], rv[:, 1:2]
     pairs = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
     Hpp = seg_sum(V.stack([Ev[:, 0, a] * Ev[:, 0, b] + Ev[:, 1, a] * Ev[:, 1, b] for a, b in pairs]), pi, Np)
@@ -220,16 +230,18 @@ def prepare(arr, lin):
                 Wabs=np.einsum("nki,nkj->nij", np.abs(Jc), np.abs(Jp)), FtF=np.einsum("nki,nkj->nij", F, F),
                 FtFabs=np.einsum("nki,nkj->nij", np.abs(Jc), np.abs(Jc)), Hpp=Hpp, gp=gp, Hcc_diag=Hcc_diag, gc=gc,
                 pa=pa, pb=pb, pid=np.asarray(pid).reshape(-1), keys=keys, n_obs_cam=np.bincount(ci, minlength=Nc),
-                track_len=np.bincount(pi, minlength=Np))
+                track_len=np.bincount(pi, minlength=Np), **extra)
 
 
 def _damping(h, radius):
-    """d = clip(h) / radius as (value, bar) and the fragile flags, h a V."""
+    """d = clip(h) / radius as (value, bar) and the fragile flags, h a V.  radius: a float64 taken as exact, or a 0-d V whose bar
+    passes through the quotient."""
     lo, hi = LD(LM_MIN), LD(LM_MAX)
-    d = np.clip(h.v, lo, hi) / LD(radius)
+    rv, re = (radius.v, radius.e) if isinstance(radius, V) else (LD(radius), LD(0))
+    d = np.clip(h.v, lo, hi) / rv
     passes = (h.v > lo) & (h.v < hi)
     fragile = ((np.abs(h.v - lo) <= h.e) | (np.abs(h.v - hi) <= h.e)) & ~((h.v == 0) & (h.e == 0))
-    return V(d, np.where(passes, h.e, 0) / LD(radius) + C_DAMP * EPS * np.abs(d)), fragile
+    return V(d, np.where(passes, h.e, 0) / rv + np.abs(d) * re / rv + C_DAMP * EPS * np.abs(d)), fragile
 
 
 def _seg(x, idx, n):
@@ -270,10 +282,13 @@ def system(prep, radius):
         YP = nz(np.matmul(aY, P[pi]))
         R = nz(np.matmul(aW, Q[pi])) + C_W * E64 * nz(np.matmul(Wabs, aC[pi]))      # |V^ - V|
     dead = aW.max(axis=(1, 2)) == 0                                  # observations of a constant block pair: exact zeros
+    dW = p.get("dW")                                                 # the bars of a computed linearisation (prepare(bars=...))
 
     def term_bar(a, b, form):                                         # observations a, b of one track
         with np.errstate(over="ignore", invalid="ignore"):
             out = np.matmul(YP[a], _t(aY[b])) + np.matmul(R[a], _t(aV[b])) + np.matmul(aV[a], _t(R[b])) + C_VV * E64 * np.matmul(aV[a], _t(aV[b]))
+            if dW is not None:                                        # dW_a |X W_b^T| + |W_a X| dW_b^T
+                out = out + np.matmul(dW[a], _t(aY[b])) + np.matmul(aY[a], _t(dW[b]))
             if form == "inverse":
                 out = out + nz(_mm(aW[a], M_inv[pi[a]], _t(aW[b]))) + C_PROD * E64 * nz(_mm(Wabs[a], K_inv[pi[a]], _t(Wabs[b])))
         return np.where((dead[a] | dead[b])[:, None, None], 0.0, nz(out))
@@ -289,6 +304,8 @@ def system(prep, radius):
     diag_bar = {}
     for form in forms:
         e = _seg(2 * E64 * p["FtFabs"] + term_bar(allo, allo, form) + E64 * mag, ci, Nc) + sum_c
+        if dW is not None:
+            e = e + _seg(p["dFtF"], ci, Nc)
         e[:, ar, ar] += f64(dc.e) + E64 * (f64(np.abs(diag[:, ar, ar])) + f64(np.abs(dc.v)))
         diag_bar[form] = e
     diag[:, ar, ar] += dc.v
@@ -312,6 +329,8 @@ def system(prep, radius):
         duc = nz(np.einsum("nji,nj->ni", Q + C_VV * E64 * aC, ag))    # |(C^T g)^ - C^T g|
         tb_f = np.einsum("nij,nj->ni", YP, axg[pi]) + np.einsum("nij,nj->ni", aY, f64(gp.e)[pi]) + np.einsum("nij,nj->ni", R, auc[pi]) \
             + np.einsum("nij,nj->ni", aV, duc[pi] + C_VV * E64 * auc[pi])
+        if dW is not None:
+            tb_f = tb_f + np.einsum("nij,nj->ni", dW, axg[pi])
         tb_i = tb_f + nz(np.einsum("nij,njk,nk->ni", aW, M_inv[pi], ag[pi])) + C_PROD * E64 * nz(np.einsum("nij,njk,nk->ni", Wabs, K_inv[pi], ag[pi]))
     b_bar = {}
     for form, tb in (("factor", tb_f), ("inverse", tb_i)):
@@ -320,7 +339,7 @@ def system(prep, radius):
             + E64 * (f64(np.abs(gc.v)) + f64(np.abs(ssum)))
     return dict(diag=diag, blk=blk, b=b, keys=keys, diag_bar=diag_bar, blk_bar=blk_bar, b_bar=b_bar, cw=cw, radius=radius,
                 fragile=int(frag_p[p["track_len"] > 0].sum()) + int(frag_c.sum()), X=X, aX=aX, CCt=CCt,
-                damp_c=np.asarray(dc.v, np.float64))
+                damp_c=np.asarray(dc.v, np.float64), A=A, dA=dA)
 
 
 def product(prep, sysm, x):

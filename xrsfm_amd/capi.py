@@ -140,7 +140,7 @@ EXPORTS = [
     "xrsfm_ba_debug_device_pack_check", "xrsfm_ba_warmup", "xrsfm_ba_debug_stored_j", "xrsfm_ba_debug_sgroup",
     "xrsfm_ba_debug_reduced_system", "xrsfm_ba_covariance", "xrsfm_ba_point_covariance", "xrsfm_ba_joint_covariance",
     "xrsfm_ba_map_covariance", "xrsfm_ba_debug_backsub_layout", "xrsfm_ba_run_batch", "xrsfm_ba_solve_batch",
-    "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars",
+    "xrsfm_ba_triangulate_options", "xrsfm_ba_triangulate_tracks", "xrsfm_ba_debug_lin_scalars", "xrsfm_ba_debug_resident_rows",
     "xrsfm_ba_absolute_pose_options", "xrsfm_ba_absolute_pose", "xrsfm_ba_debug_pose_samples",
     "xrsfm_ba_two_view_options_default", "xrsfm_ba_two_view_init", "xrsfm_ba_debug_two_view_samples",
     "xrsfm_ba_verify_pairs_options", "xrsfm_ba_verify_pairs", "xrsfm_ba_debug_fund_samples",
@@ -619,6 +619,23 @@ class Context:
         self.lib.xrsfm_ba_debug_lin_scalars.restype = C.c_int
         check(self.lib.xrsfm_ba_debug_lin_scalars(self._h, _dp(out)), "xrsfm_ba_debug_lin_scalars")
         return dict(sum_rho=float(out[0]), xnorm2_pts=float(out[1]), gradmax_pts=float(out[2]), gradmax_cams=float(out[3]))
+
+    ROW_FIELDS = ("cost", "change", "gmax", "step", "rho", "radius", "it")
+
+    def debug_resident_rows(self, options: COptions | None = None):
+        """run() with SOLVER_RESIDENT plus the iteration rows of that launch: (summary, rows), rows a list of dicts over ROW_FIELDS
+        (one per evaluated point and per rejected step; xrsfm_ba_debug_resident_rows)."""
+        options = options or default_options()
+        s = CSummary()
+        buf = np.zeros((int(options.max_iterations) + 1, 7))
+        n = C.c_int32(0)
+        self.lib.xrsfm_ba_debug_resident_rows.argtypes = [C.c_void_p, C.POINTER(COptions), C.POINTER(CSummary), _c_double_p, C.POINTER(C.c_int32)]
+        self.lib.xrsfm_ba_debug_resident_rows.restype = C.c_int
+        check(self.lib.xrsfm_ba_debug_resident_rows(self._h, C.byref(options), C.byref(s), _dp(buf), C.byref(n)), "xrsfm_ba_debug_resident_rows")
+        rows = [dict(zip(self.ROW_FIELDS, (float(v) for v in buf[i]))) for i in range(int(n.value))]
+        for r in rows:
+            r["it"] = int(r["it"])
+        return s, rows
 
     def debug_cholesky_solve(self, radius: float, want_S: bool = False):
         n = 6 * self.problem.n_cams

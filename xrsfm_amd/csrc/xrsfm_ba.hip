@@ -2864,7 +2864,9 @@ static void lba_fill_summary(const xrsfm_ba_context* c, const LbaResult& r, xrsf
     sum->termination = r.termination; sum->termination_reason = r.reason; sum->lm_steps_attempted = r.attempted;
 }
 
-static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_summary* sum) {
+// sink (may be NULL): the iteration rows of the launch, at most max_iterations + 1 of them, and their number in *n_sink
+// (xrsfm_ba_debug_resident_rows).  The rows are written whenever verbose or a sink asks for them; they change nothing of the solve.
+static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_summary* sum, LbaRow* sink = nullptr, int32_t* n_sink = nullptr) {
     Dev& d = c->d;
     const char* why = lba_refusal(c, opt);
     if (why) {
@@ -2875,7 +2877,8 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     c->profiling = opt.profile != 0;
     for (int i = 0; i < K_COUNT; ++i) { c->prof_ms[i] = 0.0; c->prof_n[i] = 0; }
     c->recs.clear(); c->ev_used = 0;
-    const size_t n_rows_max = opt.verbose ? (size_t)opt.max_iterations + 1 : 0;
+    const bool want_rows = opt.verbose || sink;
+    const size_t n_rows_max = want_rows ? (size_t)opt.max_iterations + 1 : 0;
     const size_t bytes = sizeof(LbaResult) + sizeof(LbaRow) * n_rows_max;
     PinLease pin;
     if (!pin.get(bytes)) { c->profiling = false; return XRSFM_BA_ENOMEM; }
@@ -2884,7 +2887,7 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     LbaRow* rows = reinterpret_cast<LbaRow*>(host + sizeof(LbaResult));
     memset(res, 0, sizeof(*res));
     res->status = -1;
-    const LbaOpt lo{opt.max_iterations, opt.verbose ? 1 : 0, opt.function_tolerance, opt.parameter_tolerance, opt.gradient_tolerance,
+    const LbaOpt lo{opt.max_iterations, want_rows ? 1 : 0, opt.function_tolerance, opt.parameter_tolerance, opt.gradient_tolerance,
                     opt.initial_radius, opt.huber_a};
     c->linearized = false; c->step_valid = false; c->gradmax_done = false; c->published = false;
     LAUNCH(c, K_LBA, k_lba_resident, dim3(1), dim3(kLbaBlock), 0, lba_dev(d), lo, res, rows);
@@ -2898,8 +2901,11 @@ static int lba_run(xrsfm_ba_context* c, const xrsfm_ba_options& opt, xrsfm_ba_su
     }
     if (!e) {
         lba_fill_summary(c, r, sum);
-        for (int i = 0; i < r.n_rows && (size_t)i < n_rows_max; ++i)
-            print_progress(opt, rows[i].it, rows[i].cost, rows[i].change, rows[i].gmax, rows[i].step, rows[i].rho, rows[i].radius);
+        for (int i = 0; i < r.n_rows && (size_t)i < n_rows_max; ++i) {
+            if (opt.verbose) print_progress(opt, rows[i].it, rows[i].cost, rows[i].change, rows[i].gmax, rows[i].step, rows[i].rho, rows[i].radius);
+            if (sink) sink[i] = rows[i];
+        }
+        if (n_sink) *n_sink = (int32_t)std::min((size_t)std::max(r.n_rows, 0), n_rows_max);
         sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
         if (c->profiling) {
             profile_collect(c);
@@ -6776,6 +6782,27 @@ int xrsfm_ba_debug_stamps(unsigned long long* out) {
 
 // ---------------------------------------------------------------- exception barrier of the entry points that allocate on the host
 int xrsfm_ba_run(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum) { return no_throw([&] { return ba_run_impl(c, optp, sum); }); }
+// xrsfm_ba_run with linear_solver = XRSFM_BA_SOLVER_RESIDENT (whatever opt says), plus the iteration rows of that launch.
+int xrsfm_ba_debug_resident_rows(xrsfm_ba_context* c, const xrsfm_ba_options* optp, xrsfm_ba_summary* sum, double* rows, int32_t* n_rows) {
+    return no_throw([&] {
+        if (!c || !optp || !sum || !rows || !n_rows) return (int)XRSFM_BA_EINVAL;
+        if (c->poisoned) return (int)XRSFM_BA_ESTATE;
+        xrsfm_ba_options opt = *optp;
+        opt.linear_solver = XRSFM_BA_SOLVER_RESIDENT;
+        if (opt.max_iterations < 0) return (int)XRSFM_BA_EINVAL;
+        HIPCHK(hipSetDevice(c->device));
+        memset(sum, 0, sizeof(*sum));
+        *n_rows = 0;
+        std::vector<LbaRow> buf((size_t)opt.max_iterations + 1);
+        if (int e = lba_run(c, opt, sum, buf.data(), n_rows)) return e;
+        for (int i = 0; i < *n_rows; ++i) {
+            const LbaRow& w = buf[i];
+            double* o = rows + 7 * (size_t)i;
+            o[0] = w.cost; o[1] = w.change; o[2] = w.gmax; o[3] = w.step; o[4] = w.rho; o[5] = w.radius; o[6] = (double)w.it;
+        }
+        return 0;
+    });
+}
 int xrsfm_ba_run_batch(int32_t n_ctx, xrsfm_ba_context* const* ctxs, const xrsfm_ba_options* opt, xrsfm_ba_summary* summaries, int32_t* codes) {
     return no_throw([&] { return lba_run_batch(n_ctx, ctxs, opt, summaries, codes, nullptr, nullptr); });
 }
